@@ -2,7 +2,7 @@
 """Headline benchmark: stroke-tokens/sec of the sketch-transformer-tf2 train step
 (forward + backward + Keras-Adam/WarmupDecay) on synthetic QuickDraw-shaped batches.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1] / cfg 2): 4 layers, 8 heads, d_model 128, dff 512,
@@ -10,11 +10,14 @@ L=200, per-GPU B=128, V=1004, 345 classes, dropout 0.1, fp32.  Weak scaling: eve
 runs B=128 (global batch 128*N); one RCCL all-reduce of the flat fp32 gradient buffer
 per step.  Inputs are resident in HBM before the timed region.  Prints ONE JSON line.
 
-The line carries, beside the contract keys: `roofline` (dominant kernel by time, HIP events on the launch stream, HBM
-traffic from two rocprofv3 PMC passes of this same script), `cpu_baseline`, and - single GPU only, none of them part of
-`value` - `full_length` (no padding), `fp32_mfma_mode`, `plugin_path` (the step through train_on_batch), `kernels`
-(serialised per-kernel timing) next to `kernels_concurrent` (rocprofv3 kernel trace of the real two-stream step), `cfg3` and
-`cfg5` sub-records (BASELINE configs[2] and configs[4] per GPU).  `--workload cfg3|cfg5` makes one of those the main line.
+A plain run sets up, warms up, times the K steps and prints the line (contract keys and the step-level figures derived
+from that timing).  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs()).  `--full` adds,
+beside the contract keys: `roofline` (dominant kernel by time, HIP events on the launch stream, HBM traffic from two
+rocprofv3 PMC passes of this same script), `cpu_baseline`, and - single GPU only, none of them part of `value` -
+`full_length` (no padding), `fp32_mfma_mode`, `plugin_path` (the step through train_on_batch), `kernels` (serialised
+per-kernel timing) next to `kernels_concurrent` (rocprofv3 kernel trace of the real two-stream step), `cfg3` and `cfg5`
+sub-records (BASELINE configs[2] and configs[4] per GPU), and the full record in bench_detail.json.
+`--workload cfg3|cfg5` makes one of those the main line.
 """
 import argparse
 import csv
@@ -493,10 +496,10 @@ def detail_paths():
 COMPACT_LIMIT = 4000
 
 
-def compact_line(out):
+def compact_line(out, detail="bench_detail.json"):
     """The ONE stdout line the driver parses: the contract keys + `roofline` + `cpu_baseline` and a one-level summary of the
     optional legs, kept under COMPACT_LIMIT bytes (round 3's 20.9 KB line could not be parsed: BENCH_r03.parsed = null).
-    Kernel tables, sub-record detail and the long `sample` / `timing` strings live in bench_detail.json."""
+    Kernel tables, sub-record detail and the long `sample` / `timing` strings live in the file `detail` (None: not written)."""
     line = {k: _r(out[k], 8) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                     "vs_baseline", "dtype", "data") if k in out}
     cfg = dict(out.get("config") or {})
@@ -538,7 +541,8 @@ def compact_line(out):
             if "error" in rec:
                 s["error"] = str(rec["error"])[:80]
             line[leg] = s
-    line["detail"] = "bench_detail.json"
+    if detail:
+        line["detail"] = detail
     text = json.dumps(line, separators=(",", ":"))
     # belt and braces: drop optional legs (least important first) rather than ever exceed the limit
     for leg in ("cfg2grid", "cfg3", "cfg5", "plugin_path", "fp32_mfma_mode", "hip_graph_mode", "full_length", "final_total_loss",
@@ -551,15 +555,41 @@ def compact_line(out):
     return text
 
 
+# --dump-outputs: four flat buffers of at most DUMP_MAX_ELEMS float32 each stay under 64 MB in all (cfg 2's 2.3 M parameters are
+# written whole; the larger workloads' buffers are sampled)
+DUMP_MAX_ELEMS = 3_500_000
+
+
+def dump_outputs(eng, outdir):
+    """What the timed step hands its caller after the last timed step, as float32 `outdir/<name>.npy`: `step_metrics` (the five
+    scalars of engine.METRIC_NAMES), and the flat `params`, `grads`, `adam_m`, `adam_v` buffers.  A buffer longer than
+    DUMP_MAX_ELEMS is written as the elements at a fixed sample of positions (sorted, numpy default_rng(0) without replacement:
+    the same positions for every build at the same workload)."""
+    from sketchformer_amd.engine import METRIC_NAMES
+    os.makedirs(outdir, exist_ok=True)
+    out = {"step_metrics": eng.metrics[:len(METRIC_NAMES)]}
+    for name in ("params", "grads", "adam_m", "adam_v"):
+        out[name] = getattr(eng, name)
+    for name, t in out.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    _progress("outputs of the last timed step -> %s" % outdir)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel profile (and with it `roofline`)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sub-records, the rocprofv3 child runs and the plugin-path leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline, the per-kernel profile / roofline, the extra legs and sub-records, bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel profile (and with it `roofline`)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the sub-records, the rocprofv3 child runs and the plugin-path leg")
     ap.add_argument("--graph", type=int, nargs="?", const=1, default=0, choices=(0, 1, 2),
                     help="replay the step from hipGraphs instead of eager launches: 1 = captured on one stream, 2 = the two-stream step captured "
                          "(side stream forked / joined inside the capture)")
@@ -571,6 +601,8 @@ def main():
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS),
                     help="cfg2 = the headline config (default); cfg3 = 6L/d256/dff1024 continuous; cfg5 = 8L/d512/dff2048 L=512 bf16")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -634,6 +666,8 @@ def main():
         elapsed = float(t.item())
     metrics = eng.step_metrics()
     assert np.isfinite(metrics["total_loss"]), metrics
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * B * L * args.steps / elapsed
@@ -658,7 +692,7 @@ def main():
         "final_total_loss": metrics["total_loss"],
     }
     single = rank == 0 and world == 1
-    extras = single and not args.no_extras
+    extras = single and args.full and not args.no_extras
     _progress("headline: %.3f ms/step" % ms_per_step)
     if extras and not args.full_length:
         xf, yf = make_batch(synthetic, w, B, rank, True)
@@ -697,8 +731,9 @@ def main():
             out["hip_graph_mode"] = {"error": str(exc)[:80]}
     del eng
     torch.cuda.empty_cache()
-    _progress("full-length / fp32-MFMA / hipGraph legs done")
-    if rank == 0 and not args.no_profile:
+    if extras:
+        _progress("full-length / fp32-MFMA / hipGraph legs done")
+    if rank == 0 and args.full and not args.no_profile:
         rows, _ = kernel_profile(engine, cfg_kwargs, x, y)
         rows.sort(key=lambda r: -r["ms"])
         roof = roofline_of(rows, w["act"])
@@ -740,7 +775,7 @@ def main():
             if roof["traffic"] is not None:
                 roof["traffic_source"] = "committed profiles/*pmc_traffic.json (rocprofv3 not runnable in this invocation)"
         out["roofline"] = roof
-    if single and not args.no_cpu_baseline:
+    if single and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
         _progress("cpu baseline done")
     if extras and args.workload == "cfg2" and not args.graph:
@@ -761,14 +796,15 @@ def main():
         _progress("plugin path done")
     if rank == 0:
         out["rccl_ranks"] = rccl_ranks
-        for path in detail_paths():
-            try:
-                with open(path, "w") as f:
-                    json.dump(out, f, indent=1)
-                _progress("full record -> %s" % path)
-            except OSError as e:
-                _progress("could not write %s: %s" % (path, e))
-        print(compact_line(out), flush=True)
+        if args.full:
+            for path in detail_paths():
+                try:
+                    with open(path, "w") as f:
+                        json.dump(out, f, indent=1)
+                    _progress("full record -> %s" % path)
+                except OSError as e:
+                    _progress("could not write %s: %s" % (path, e))
+        print(compact_line(out, detail="bench_detail.json" if args.full else None), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

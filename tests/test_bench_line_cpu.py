@@ -104,3 +104,32 @@ def test_roofline_frac_follows_from_the_fields_beside_it():
     assert bench.roofline_identity_error(line) < 2e-3
     assert line["traffic_per_step"] == pytest.approx(9.5e9, rel=1e-4) and line["algorithmic_bytes_per_step"] == pytest.approx(3.2e9, rel=1e-4)
     assert line["avg_launch_us_hip_events"] == pytest.approx(hip_avg, rel=1e-4)
+
+
+class _FakeEngine:
+    """the attributes dump_outputs() reads from engine.TrainEngine, as host tensors"""
+    def __init__(self, n, seed):
+        import torch
+        g = torch.Generator().manual_seed(seed)
+        self.metrics = torch.rand(32, generator=g)
+        self.params, self.grads, self.adam_m, self.adam_v = (torch.rand(n, generator=g) for _ in range(4))
+
+
+def test_dump_outputs_names_dtypes_and_size_cap(tmp_path):
+    import numpy as np
+    small = _FakeEngine(1000, 0)
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    for name in ("step_metrics", "params", "grads", "adam_m", "adam_v"):
+        a = np.load(tmp_path / "small" / (name + ".npy"))
+        assert a.dtype == np.float32
+        want = small.metrics[:5] if name == "step_metrics" else getattr(small, name)
+        assert np.array_equal(a, want.numpy()), name                   # below the cap: the whole buffer
+    n = bench.DUMP_MAX_ELEMS + 12345
+    for tag in ("a", "b"):
+        bench.dump_outputs(_FakeEngine(n, 1), str(tmp_path / tag))
+    total = sum(os.path.getsize(p) for p in glob.glob(str(tmp_path / "a" / "*.npy")))
+    assert total <= 64 * 10 ** 6, total
+    for name in ("params", "grads", "adam_m", "adam_v"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)    # a fixed sample: the same positions every run
+        assert np.isin(a, getattr(_FakeEngine(n, 1), name).numpy()).all()
