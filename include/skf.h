@@ -665,10 +665,24 @@ int skf_model_apply_gradients_range(SkfModel* m, size_t offset, size_t count, fl
  *   out: device buffer (B, max_steps+1) int64 tokens [column 0 = SOS] or (B, max_steps+1, 5) float stroke-5 rows
  *   [row 0 = (0,0,1,0,0)]; *out_len_host = number of valid columns (the reference's output length).
  *   Blocking: synchronises the stream every 8 tokens to test the stop condition. */
+/* skf_model_greedy_decode_attn: the same, plus the decoder's attention weights (models/sketchformer.py:204,220,306
+ *   out['attn_weights'] = the Decoder's dict decoder_layer{i}_block1 / _block2, builders/layers/transformer.py:245-262,328-344).
+ *   attn_weights: NULL (= skf_model_greedy_decode), or a device buffer of (2 * num_layers, B, H, max_steps, seq_len) floats:
+ *   index 2l = layer l's block1 (self attention), 2l + 1 its block2 (cross attention over pre_decoder); row t of (b, h) = the
+ *   softmax row of position t (builders/utils.py:101-105), block1 zero from key t + 1 on.  Every row of a decoded position is
+ *   written in full (no memset needed); rows of positions not decoded are left as they were.
+ *   With T = *out_len_host - 1, rows [0, T) of a block are what the reference's last decoder pass returns over recon[:, :T]:
+ *   block1[..., :T, :T] (look-ahead | target padding mask), block2[..., :T, :] (keys >= expected_len masked unless blind;
+ *   masked entries exactly 0).  Capturing during the KV-cached decode is exact because both masks stay the same from step
+ *   to step - except with blind_decoder_mask == 0 and expected_len_host == NULL (nattn = i + 1 changes every iteration):
+ *   that combination is refused (SKF_EINVAL).  The weights-off path is unchanged (captured step, one launch per position). */
 int skf_model_encode(SkfModel* m, const void* inp, skf_stream_t stream);
 int skf_model_greedy_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
                             long long sos, long long eos, int max_steps, void* out, int* out_len_host,
                             skf_stream_t stream);
+int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
+                                 long long sos, long long eos, int max_steps, void* out, int* out_len_host,
+                                 float* attn_weights, skf_stream_t stream);
 /* look up an internal activation by name ("logits", "class_probs", "embedding", "enc_output", ...); skf_model_buffer serves
  * fp32 buffers, skf_model_buffer_info any buffer with its row pitch (elements) and element type (bf16 models keep their
  * activations in bf16) */

@@ -4,6 +4,7 @@
 // and attention is one query row per (sample, head).
 #include "skf_common.h"
 #include "../../include/skf.h"
+#include "skf_decode_fused.h"
 
 namespace {
 
@@ -19,6 +20,7 @@ struct AttnDecodeParams {
   const float* K_new; const float* V_new; int ld_new;   // non-null: row Lk-1 comes from here and is appended to the cache
   float* K_cache; float* V_cache;                       // writable aliases of K / V for the append
   int limit_from_step;            // cross attention without per-sample limits: keys >= step + 1 are masked
+  float* W; int w_rows, w_ld;     // non-null: softmax row of (b, h) -> W[((b * H + h) * w_rows + *step_dev) * w_ld ...], zero-padded to w_ld
 };
 
 // One wave per (sample, head): lane j owns keys j, j+64, ... (Lk <= 64*MAXJ).
@@ -79,6 +81,15 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeParams p) {
   for (int jj = 0; jj < MAXJ; ++jj) { s[jj] = __expf(s[jj] - mx); se += s[jj]; }   // exp(-inf) = 0 past Lk
   se = wave_sum(se);
   const float rinv = 1.0f / se;
+  if (p.W) {                     // uniform branch (kernel argument); s[] is exactly 0 past Lk
+    float* wr = p.W + ((size_t)bh * p.w_rows + step) * p.w_ld;
+#pragma unroll
+    for (int jj = 0; jj < MAXJ; ++jj) {
+      const int j = lane + 64 * jj;
+      if (j < p.w_ld) wr[j] = s[jj] * rinv;
+    }
+    for (int j = lane + 64 * MAXJ; j < p.w_ld; j += 64) wr[j] = 0.f;
+  }
   float acc[DH];
 #pragma unroll
   for (int c = 0; c < DH; ++c) acc[c] = 0.f;
@@ -146,6 +157,10 @@ __global__ __launch_bounds__(256) void attn_decode_any_kernel(AttnDecodeParams p
   for (int j = lane; j < Lk; j += 64) { const float e = __expf(ps[wave][j] - mx); ps[wave][j] = e; se += e; }
   se = wave_sum(se);
   const float rinv = 1.0f / se;
+  if (active && p.W) {           // a lane reads back only the entries it wrote
+    float* wr = p.W + ((size_t)bh * p.w_rows + step) * p.w_ld;
+    for (int j = lane; j < p.w_ld; j += 64) wr[j] = j < Lk ? ps[wave][j] * rinv : 0.f;
+  }
   __syncthreads();
   for (int c = lane; c < DH; c += 64) {
     float acc = 0.f;
@@ -270,11 +285,10 @@ __global__ void decode_init_kernel(long long* tokens, int tok_ld, float* cont, i
 
 }  // namespace
 
-extern "C" int skf_attention_decode(const float* Q, int ldq, const float* K, const float* V, int ld_kv,
-                                    long long kv_batch_stride, const unsigned char* key_mask, int key_mask_ld,
-                                    const int* key_limit, int key_limit_all, int B, int H, int Lk, int dh, float* O,
-                                    int ldo, const int* step_dev, const float* K_new, const float* V_new, int ld_new,
-                                    int limit_from_step, skf_stream_t stream) {
+int skf_attention_decode_w(const float* Q, int ldq, const float* K, const float* V, int ld_kv, long long kv_batch_stride,
+                           const unsigned char* key_mask, int key_mask_ld, const int* key_limit, int key_limit_all, int B, int H,
+                           int Lk, int dh, float* O, int ldo, const int* step_dev, const float* K_new, const float* V_new, int ld_new,
+                           int limit_from_step, float* attn, int attn_rows, int attn_ld, hipStream_t st) {
   SKF_CHECK_ARG(Q && K && V && O, "null operand");
   SKF_CHECK_ARG(B > 0 && H > 0 && Lk > 0 && Lk <= 512, "need 0 < Lk <= 512");
   SKF_CHECK_ARG(dh > 0 && dh <= 128 && (dh & 3) == 0, "head size must be a multiple of 4, at most 128");
@@ -284,9 +298,10 @@ extern "C" int skf_attention_decode(const float* Q, int ldq, const float* K, con
   SKF_CHECK_ARG(!K_new || (step_dev && (ld_new & 3) == 0 && (((uintptr_t)K_new | (uintptr_t)V_new) & 15) == 0),
                 "appending needs the device step index and 16-byte aligned new rows");
   SKF_CHECK_ARG(!limit_from_step || step_dev, "limit_from_step needs the device step index");
+  SKF_CHECK_ARG(!attn || (step_dev && attn_rows > 0 && attn_ld >= Lk), "attention weights need the device step index and rows of >= Lk");
   AttnDecodeParams p{Q, ldq, K, V, ld_kv, kv_batch_stride, key_mask, key_mask_ld, key_limit, key_limit_all, B, H, Lk, O, ldo,
-                     step_dev, K_new, V_new, ld_new, const_cast<float*>(K), const_cast<float*>(V), limit_from_step};
-  hipStream_t st = (hipStream_t)stream;
+                     step_dev, K_new, V_new, ld_new, const_cast<float*>(K), const_cast<float*>(V), limit_from_step,
+                     attn, attn_rows, attn_ld};
   dim3 grid(skf_cdiv(B * H, 4)), block(256);
   SkfProfScope ps(st, "attn_decode", 4.0 * B * H * (double)Lk * dh, 8.0 * B * H * (double)Lk * dh);
 #define SKF_AD(DHV)                                                                         \
@@ -297,6 +312,15 @@ extern "C" int skf_attention_decode(const float* Q, int ldq, const float* K, con
 #undef SKF_AD
   SKF_LAUNCH_CHECK();
   return SKF_OK;
+}
+
+extern "C" int skf_attention_decode(const float* Q, int ldq, const float* K, const float* V, int ld_kv,
+                                    long long kv_batch_stride, const unsigned char* key_mask, int key_mask_ld,
+                                    const int* key_limit, int key_limit_all, int B, int H, int Lk, int dh, float* O,
+                                    int ldo, const int* step_dev, const float* K_new, const float* V_new, int ld_new,
+                                    int limit_from_step, skf_stream_t stream) {
+  return skf_attention_decode_w(Q, ldq, K, V, ld_kv, kv_batch_stride, key_mask, key_mask_ld, key_limit, key_limit_all, B, H, Lk, dh,
+                                O, ldo, step_dev, K_new, V_new, ld_new, limit_from_step, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 extern "C" int skf_decode_init(long long* tokens, int tok_ld, float* cont, int cont_ld_rows, unsigned char* selfmask,

@@ -1,4 +1,5 @@
-// Argument block of the one-launch-per-position greedy decode (skf_decode_fused.hip); internal to libskf.
+// Argument block of the one-launch-per-position greedy decode (skf_decode_fused.hip) and the attention launcher of the
+// layer-by-layer decode (skf_decode.hip); internal to libskf.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -24,7 +25,15 @@ struct SkfDecodeFused {
   int* eos_seen; int* done_step; int* step_dev; int* ticket;
   const long long* dyn;                           // [0] n_valid, [1] eos
   const int* limit;                               // per-sample cross-attention key limit (non-blind) or null
+  float* attn; int attn_rows;                     // null, or (2N, B, H, attn_rows, Le) softmax rows: [2l] self, [2l+1] cross; row = step
 };
 
 bool skf_decode_fused_supported(int d, int H, int F, int Le, int N, int Vout);
 int skf_decode_fused_launch(const SkfDecodeFused& p, hipStream_t st);
+
+// skf_attention_decode plus an optional copy of the softmax rows: attn (B, H, attn_rows, attn_ld), row *step_dev of every
+// (sample, head) = the Lk probabilities, then zeros up to attn_ld (attn non-null needs step_dev).
+int skf_attention_decode_w(const float* Q, int ldq, const float* K, const float* V, int ld_kv, long long kv_batch_stride,
+                           const unsigned char* key_mask, int key_mask_ld, const int* key_limit, int key_limit_all, int B, int H,
+                           int Lk, int dh, float* O, int ldo, const int* step_dev, const float* K_new, const float* V_new, int ld_new,
+                           int limit_from_step, float* attn, int attn_rows, int attn_ld, hipStream_t stream);

@@ -119,10 +119,11 @@ __device__ __forceinline__ void add_ln(const float* a, const float* r, const flo
 // instruction reads whole contiguous rows (a lane per key would touch 64 cache lines per instruction: measured 10 of the
 // 11 us of this function).  Three phases through LDS: scores[h][j] (dot product folded over the DH/4 adjacent lanes of a
 // head), softmax per head (wave = head), weighted sum of V (partials per key slice, folded in a fixed order).
+// aw non-null: head h's probabilities also go to aw[h * aw_hs + j] (lanes over keys: contiguous stores), zeros from Lk to aw_len.
 template <int DH>
 __device__ __forceinline__ void attend(const float* q_lds, const float* __restrict__ Kb, const float* __restrict__ Vb, int ld_kv, int Lk,
                        const unsigned char* __restrict__ mask, int limit, int d, int H, float* sc, int LkP, float* part,
-                       float* o_lds, int tid) {
+                       float* o_lds, int tid, float* __restrict__ aw, size_t aw_hs, int aw_len) {
   const int nc4 = d >> 2, jl = tid / nc4, c4 = tid - jl * nc4, JP = NT / nc4;
   const int h = (4 * c4) / DH;
   const f32x4 q4 = *reinterpret_cast<const f32x4*>(q_lds + 4 * c4);
@@ -170,7 +171,13 @@ __device__ __forceinline__ void attend(const float* q_lds, const float* __restri
       for (int j = lane; j < Lk; j += 64) { const float e = __expf(row[j] - mx); row[j] = e; se += e; }
       se = wave_sum(se);
       const float rinv = 1.0f / se;
-      for (int j = lane; j < Lk; j += 64) row[j] *= rinv;
+      if (aw) {                  // uniform; a constant null in the weights-off instantiation (the branch folds away)
+        float* dst = aw + hh * aw_hs;
+        for (int j = lane; j < Lk; j += 64) { const float pj = row[j] * rinv; row[j] = pj; dst[j] = pj; }
+        for (int j = Lk + lane; j < aw_len; j += 64) dst[j] = 0.f;
+      } else {
+        for (int j = lane; j < Lk; j += 64) row[j] *= rinv;
+      }
     }
   }
   __syncthreads();
@@ -189,7 +196,8 @@ __device__ __forceinline__ void attend(const float* q_lds, const float* __restri
   __syncthreads();
 }
 
-template <int DH>
+// AW: the instantiation that writes the attention weights; the other one is the decoder without that output.
+template <int DH, bool AW>
 __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -228,6 +236,9 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   int limit = 0x7fffffff;          // cross attention: keys >= limit are masked (models/sketchformer.py:172,279-283)
   if (!p.blind) { limit = p.limit ? p.limit[b] : -1; if (limit < 0) limit = step + 1; }
   const unsigned char* smask = p.selfmask + (size_t)b * p.mask_ld;
+  // attention weights of the position: row `step` of (2N, B, H, attn_rows, Le); block k of layer l at + (2l + k) * blk
+  const size_t aw_hs = (size_t)p.attn_rows * p.Le, aw_blk = (size_t)p.B * p.H * aw_hs;
+  float* aw = AW && step < p.attn_rows ? p.attn + ((size_t)b * p.H * p.attn_rows + step) * p.Le : nullptr;
 
   for (int l = 0; l < p.N; ++l) {
     const SkfDecLayer& w = p.layer[l];
@@ -235,12 +246,14 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
     float* cache = w.cache + (size_t)b * p.Le * 2 * d;             // (Le, 2d): K | V of the positions so far
     for (int c = tid; c < 2 * d; c += NT) cache[(size_t)step * 2 * d + c] = qkv[d + c];
     __syncthreads();               // the appended row is read back below: workgroup-scope visibility of the global stores
-    attend<DH>(qkv, cache, cache + d, 2 * d, step + 1, smask, 0x7fffffff, d, p.H, sc, LkP, part, os, tid);
+    attend<DH>(qkv, cache, cache + d, 2 * d, step + 1, smask, 0x7fffffff, d, p.H, sc, LkP, part, os, tid,
+               aw ? aw + (size_t)(2 * l) * aw_blk : nullptr, aw_hs, p.Le);
     dense(w.o, os, ys, 0, part, tid);
     add_ln(xs, ys, w.ln1_g, w.ln1_b, o1, d, red, tid);
     dense(w.q2, o1, qkv, 0, part, tid);
     const float* kv2 = w.kv2 + (size_t)b * p.Le * 2 * d;
-    attend<DH>(qkv, kv2, kv2 + d, 2 * d, p.Le, nullptr, limit, d, p.H, sc, LkP, part, os, tid);
+    attend<DH>(qkv, kv2, kv2 + d, 2 * d, p.Le, nullptr, limit, d, p.H, sc, LkP, part, os, tid,
+               aw ? aw + (size_t)(2 * l + 1) * aw_blk : nullptr, aw_hs, p.Le);
     dense(w.o2, os, ys, 0, part, tid);
     add_ln(o1, ys, w.ln2_g, w.ln2_b, o2, d, red, tid);
     dense(w.f1, o2, hs, 1, part, tid);
@@ -317,13 +330,17 @@ int skf_decode_fused_launch(const SkfDecodeFused& p, hipStream_t st) {
   const int dh = p.d / p.H;
   const size_t smem = skf_decode_fused_lds_bytes(p);
   SkfProfScope ps(st, "decode_position", 0.0, 0.0);
-#define SKF_DF(DHV)                                                                                                  \
+#define SKF_DF(DHV, AWV)                                                                                             \
   {                                                                                                                  \
-    SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_position_kernel<DHV>),                           \
+    SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_position_kernel<DHV, AWV>),                      \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024)); /* per launch: per-device attribute */ \
-    hipLaunchKernelGGL((decode_position_kernel<DHV>), dim3(p.B), dim3(NT), smem, st, p);                             \
+    hipLaunchKernelGGL((decode_position_kernel<DHV, AWV>), dim3(p.B), dim3(NT), smem, st, p);                        \
   }
-  if (dh == 16) SKF_DF(16) else if (dh == 32) SKF_DF(32) else SKF_DF(64)
+  if (p.attn) {
+    if (dh == 16) SKF_DF(16, true) else if (dh == 32) SKF_DF(32, true) else SKF_DF(64, true)
+  } else {
+    if (dh == 16) SKF_DF(16, false) else if (dh == 32) SKF_DF(32, false) else SKF_DF(64, false)
+  }
 #undef SKF_DF
   SKF_LAUNCH_CHECK();
   return SKF_OK;

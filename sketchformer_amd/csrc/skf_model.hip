@@ -1614,8 +1614,9 @@ int run_backward(SkfModel* M, hipStream_t s) {
 //   target padding mask (look-ahead is implicit: later keys do not exist yet) ; LN ; cross attention over the
 //   cached K/V of pre_decoder ; LN ; FFN ; LN                               (transformer.py:245-262)
 //   logits of position i -> argmax / stroke-5 row -> appended                (sketchformer.py:285-301)
+// attn (optional): the softmax rows of every position, (2N, B, H, max_steps, Le) - see skf_model_greedy_decode_attn.
 int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
-                      long long eos, int max_steps, void* out, int* out_len_host, hipStream_t s) {
+                      long long eos, int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s) {
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
   const Plan& P = M->plan;
@@ -1669,6 +1670,7 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
   float* kvnew = M->at<float>(P.dc_kvnew);
   // One decode step.  Every argument is the same for every step and every call (the step index, n_valid and eos are
   // read from device memory), so the ~50 small launches are captured once into a hipGraph and replayed.
+  const size_t aw_blk = (size_t)B * H * max_steps * Le;   // one (B, H, max_steps, Le) block of the attention weights
   auto issue_step = [&]() -> int {
     float* x = M->at<float>(P.dc_x[0]);
     float* xn = M->at<float>(P.dc_x[1]);
@@ -1683,15 +1685,17 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
       SKF_TRY(dense_fwd_ld(M, wq, x, d, B, q, d, 0, s));
       SKF_TRY(dense_fwd_ld(M, wkv, x, d, B, kvnew, 2 * d, 0, s));
       // keys 0..step: the cache plus the row just projected (which the kernel also appends to the cache)
-      SKF_TRY(skf_attention_decode(q, d, cache, cache + d, 2 * d, (long long)Le * 2 * d, selfmask, Le + 1, nullptr, 0, B, H,
-                                   Le, dh, o, d, step_dev, kvnew, kvnew + d, 2 * d, 0, s));
+      SKF_TRY(skf_attention_decode_w(q, d, cache, cache + d, 2 * d, (long long)Le * 2 * d, selfmask, Le + 1, nullptr, 0, B, H,
+                                     Le, dh, o, d, step_dev, kvnew, kvnew + d, 2 * d, 0, attn ? attn + (size_t)(2 * l) * aw_blk : nullptr,
+                                     max_steps, Le, s));
       SKF_TRY(dense_fwd(M, w.mha1.o, o, B, z, 0, s));
       SKF_TRY(skf_layernorm_residual_fwd(x, z, M->P(w.ln1.g), M->P(w.ln1.b), out1, stats, B, d, 0.f, 0, M->state, s));
       const float* kv2 = M->at<float>(P.dec[l].kv2);
       SKF_TRY(dense_fwd(M, w.mha2.q, out1, B, q, 0, s));
       // cross mask (models/sketchformer.py:172,279-283): none when blind, else keys >= nattn (expected length or step+1)
-      SKF_TRY(skf_attention_decode(q, d, kv2, kv2 + d, 2 * d, (long long)Le * 2 * d, nullptr, 0, limit, 0, B, H, Le, dh, o, d,
-                                   step_dev, nullptr, nullptr, 0, c.blind_decoder_mask ? 0 : 1, s));
+      SKF_TRY(skf_attention_decode_w(q, d, kv2, kv2 + d, 2 * d, (long long)Le * 2 * d, nullptr, 0, limit, 0, B, H, Le, dh, o, d,
+                                     step_dev, nullptr, nullptr, 0, c.blind_decoder_mask ? 0 : 1,
+                                     attn ? attn + (size_t)(2 * l + 1) * aw_blk : nullptr, max_steps, Le, s));
       SKF_TRY(dense_fwd(M, w.mha2.o, o, B, z, 0, s));
       SKF_TRY(skf_layernorm_residual_fwd(out1, z, M->P(w.ln2.g), M->P(w.ln2.b), out2, stats, B, d, 0.f, 0, M->state, s));
       SKF_TRY(dense_fwd(M, w.f1, out2, B, hbuf, 1, s));
@@ -1730,10 +1734,13 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
     fp.embd_w = c.continuous ? M->P(L.dec_embd.w) : nullptr; fp.embd_b = c.continuous ? M->P(L.dec_embd.b) : nullptr;
     fp.pos = M->pos; fp.tokens = tokens; fp.cont = cont; fp.Ti = Ti; fp.selfmask = selfmask; fp.mask_ld = Le + 1;
     fp.eos_seen = eos_seen; fp.done_step = done_step; fp.step_dev = step_dev; fp.ticket = done_step + 1;
-    fp.dyn = dyn; fp.limit = limit;
+    fp.dyn = dyn; fp.limit = limit; fp.attn = attn; fp.attn_rows = max_steps;
     SKF_HIP(hipMemsetAsync(fp.ticket, 0, sizeof(int), s));
   }
-  static const bool use_graph = !(skf_knob("SKF_DECODE_GRAPH") && skf_knob("SKF_DECODE_GRAPH")[0] == '0');
+  // the captured step has constant arguments and no weight output: with weights requested, the steps are issued eagerly
+  // (g_dec stays as it is)
+  static const bool use_graph_knob = !(skf_knob("SKF_DECODE_GRAPH") && skf_knob("SKF_DECODE_GRAPH")[0] == '0');
+  const bool use_graph = use_graph_knob && !attn;
   if (fused) {
     for (int i = 0; i < max_steps; ++i) {
       SKF_TRY(skf_decode_fused_launch(fp, s));
@@ -2101,17 +2108,29 @@ extern "C" int skf_model_encode(SkfModel* m, const void* inp, skf_stream_t strea
   return run_forward(m, false, false, s, true);
 }
 
-extern "C" int skf_model_greedy_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
-                                       long long sos, long long eos, int max_steps, void* out, int* out_len_host,
-                                       skf_stream_t stream) {
+extern "C" int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
+                                            long long sos, long long eos, int max_steps, void* out, int* out_len_host,
+                                            float* attn_weights, skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
   SKF_CHECK_ARG(out, "null output");
   SKF_CHECK_ARG(n_valid > 0 && n_valid <= m->cfg.batch, "n_valid must be in [1, batch]");
   SKF_CHECK_ARG(max_steps > 0 && max_steps <= m->cfg.seq_len, "max_steps must be in [1, seq_len]");
   SKF_CHECK_ARG(m->cfg.do_reconstruction, "the model was built without a decoder (do_reconstruction = 0)");
-  if (m->bf16) return run_greedy_decode16(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, (hipStream_t)stream);
-  return run_greedy_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host,
+  SKF_CHECK_ARG(!attn_weights || m->cfg.blind_decoder_mask || expected_len_host,
+                "attention weights of a non-blind decoder need expected_len (with nattn = i + 1 the cached rows differ from the "
+                "reference's last pass)");
+  if (m->bf16)
+    return run_greedy_decode16(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights,
+                               (hipStream_t)stream);
+  return run_greedy_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights,
                            (hipStream_t)stream);
+}
+
+extern "C" int skf_model_greedy_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
+                                       long long sos, long long eos, int max_steps, void* out, int* out_len_host,
+                                       skf_stream_t stream) {
+  return skf_model_greedy_decode_attn(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, nullptr,
+                                      stream);
 }
 
 // The embedding gradients' counting sorts depend on the staged tokens only.  Eager path with a decoder: side stream, under

@@ -485,7 +485,7 @@ int issue_embed_sorts16(SkfModel* M, hipStream_t s) {
 // weights through the one-launch-per-position kernel of the fp32 path (skf_decode_fused.hip); only the embedding it starts
 // from comes from the bf16 encoder.  Token mode (the bf16 path has no continuous mode).
 int run_greedy_decode16(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos, long long eos,
-                        int max_steps, void* out, int* out_len_host, hipStream_t s) {
+                        int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s) {
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
   const Plan16& P = M->p16;
@@ -536,6 +536,7 @@ int run_greedy_decode16(SkfModel* M, const float* embedding, const int* expected
   fp.out = dn(L.out);
   fp.emb_table = M->P(L.dec_emb); fp.pos = M->pos; fp.tokens = tokens; fp.cont = nullptr; fp.Ti = Ti; fp.selfmask = selfmask; fp.mask_ld = Le + 1;
   fp.eos_seen = eos_seen; fp.done_step = done_step; fp.step_dev = step_dev; fp.ticket = done_step + 1; fp.dyn = dyn; fp.limit = limit;
+  fp.attn = attn; fp.attn_rows = max_steps;
   SKF_HIP(hipMemsetAsync(fp.ticket, 0, sizeof(int), s));
   for (int i = 0; i < max_steps; ++i) {
     SKF_TRY(skf_decode_fused_launch(fp, s));

@@ -311,13 +311,21 @@ class TrainEngine:
         finally:
             self._leave()
 
-    def greedy_decode(self, embedding=None, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None):
+    def greedy_decode(self, embedding=None, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None,
+                      with_attn_weights=False):
         """predict_from_embedding (models/sketchformer.py:255-311) with a K/V cache.  embedding: (B,d) array / tensor
         or None (= the model's own 'embedding' buffer, i.e. right after ``encode``).  Returns the reconstruction as a
-        host array: (n_valid, T) int32 tokens incl. the SOS column, or (n_valid, T, 5) float32 stroke-5 rows."""
+        host array: (n_valid, T) int32 tokens incl. the SOS column, or (n_valid, T, 5) float32 stroke-5 rows.
+        with_attn_weights: return ``(recon, weights)`` instead, weights = the reference's res['attn_weights']
+        (builders/layers/transformer.py:328-344): {'decoder_layer{i}_block1': (n_valid, H, T-1, T-1),
+        'decoder_layer{i}_block2': (n_valid, H, T-1, seq_len)} float32, the last decoder pass over recon[:, :T-1]
+        (skf_model_greedy_decode_attn).  A non-blind decoder needs expected_len for it (ValueError otherwise)."""
         B, L = self.cfg.batch, self.cfg.seq_len
         n_valid = B if n_valid is None else int(n_valid)
         max_steps = L if max_steps is None else int(max_steps)
+        if with_attn_weights and not self.cfg.blind_decoder_mask and expected_len is None:
+            raise ValueError("attention weights of a non-blind decoder need expected_len: with nattn = i + 1 the rows decoded "
+                             "earlier were masked differently from the reference's last pass")
         emb_ptr = None
         if embedding is not None:
             e = torch.as_tensor(np.asarray(embedding, dtype=np.float32) if not torch.is_tensor(embedding) else embedding)
@@ -341,15 +349,31 @@ class TrainEngine:
         else:
             out = torch.zeros(B, max_steps + 1, dtype=torch.int64, device=self.device)
         n_out = C.c_int(0)
+        aw = None
+        if with_attn_weights:       # every row of a decoded position is written by the kernels: no memset
+            aw = torch.empty(2 * self.cfg.num_layers, B, self.cfg.num_heads, max_steps, L, dtype=torch.float32,
+                             device=self.device)
         self._enter()
         try:
-            _lib.call("skf_model_greedy_decode", self.handle, emb_ptr, lim, n_valid, int(sos), int(eos), max_steps, self._p(out),
-                      C.byref(n_out), self._stream())
+            if aw is None:
+                _lib.call("skf_model_greedy_decode", self.handle, emb_ptr, lim, n_valid, int(sos), int(eos), max_steps,
+                          self._p(out), C.byref(n_out), self._stream())
+            else:
+                _lib.call("skf_model_greedy_decode_attn", self.handle, emb_ptr, lim, n_valid, int(sos), int(eos), max_steps,
+                          self._p(out), C.byref(n_out), self._p(aw), self._stream())
         finally:
             self._leave()
         self.synchronize()
         res = out[:n_valid, :n_out.value].cpu().numpy()
-        return res if self.cfg.continuous else res.astype(np.int32)
+        res = res if self.cfg.continuous else res.astype(np.int32)
+        if aw is None:
+            return res
+        T = n_out.value - 1
+        weights = {}
+        for i in range(self.cfg.num_layers):
+            weights['decoder_layer%d_block1' % (i + 1)] = aw[2 * i, :n_valid, :, :T, :T].cpu().numpy()
+            weights['decoder_layer%d_block2' % (i + 1)] = aw[2 * i + 1, :n_valid, :, :T, :].cpu().numpy()
+        return res, weights
 
     def _stage(self, inp, tar, labels):
         """caller-side arguments -> device tensors (enqueued on the CALLER's stream: must precede _enter).  Device tensors of the

@@ -187,10 +187,12 @@ class Transformer(BaseModel, TransformerMetricsMixin):
                 d[b, :int(n)] = 1.0
         return d
 
-    def predict_from_embedding(self, emb, expected_len=None):
+    def predict_from_embedding(self, emb, expected_len=None, with_attn_weights=False):
         """Greedy reconstruction from the bottleneck (models/sketchformer.py:255-311), KV-cached on the device.
-        Returns {'recon', 'class', 'attn_weights'}; attention weights are never materialised here (no consumer in the
-        reference reads them: evaluation_mixin.py:25-35, experiments/*.py) -> None."""
+        Returns {'recon', 'class', 'attn_weights'}.  attn_weights is None unless with_attn_weights: then the reference's
+        dict of the last decoder pass, {'decoder_layer{i}_block1': (n, H, T, T), 'decoder_layer{i}_block2': (n, H, T, seq_len)}
+        float32 with T = recon length - 1 (models/sketchformer.py:306).  Opt-in: the evaluation code calls predict on
+        whole splits and reads no weights.  A non-blind model needs expected_len for them (ValueError otherwise)."""
         if not self.hps['do_reconstruction']:
             raise ValueError("do_reconstruction is off")
         emb = np.asarray(emb, dtype=np.float32)
@@ -204,16 +206,22 @@ class Transformer(BaseModel, TransformerMetricsMixin):
         tok = self.dataset.tokenizer
         if self.hps['blind_decoder_mask']:
             expected_len = None                     # "will be ignored if blind_decoder_mask=True"
-        recon = self.engine.greedy_decode(pad, expected_len=expected_len, n_valid=n,
-                                          sos=getattr(tok, 'SOS', 0) if tok is not None else 0,
-                                          eos=getattr(tok, 'EOS', 0) if tok is not None else 0)
-        out = {'recon': recon, 'attn_weights': None}
+        if with_attn_weights and expected_len is None and not self.hps['blind_decoder_mask']:
+            raise ValueError("attn_weights of a non-blind decoder need expected_len (with nattn = i + 1 the decoded rows "
+                             "were masked differently from the reference's last pass)")
+        res = self.engine.greedy_decode(pad, expected_len=expected_len, n_valid=n,
+                                        sos=getattr(tok, 'SOS', 0) if tok is not None else 0,
+                                        eos=getattr(tok, 'EOS', 0) if tok is not None else 0,
+                                        with_attn_weights=with_attn_weights)
+        recon, weights = res if with_attn_weights else (res, None)
+        out = {'recon': recon, 'attn_weights': weights}
         if self._has_cls:
             out['class'] = self.engine.buffer('class_probs')[:n].cpu().numpy().argmax(-1).astype(np.int32)
         return out
 
-    def predict(self, inp_seq):
-        """models/sketchformer.py:201-221."""
+    def predict(self, inp_seq, with_attn_weights=False):
+        """models/sketchformer.py:201-221.  with_attn_weights: out['attn_weights'] = the decoder's attention weights
+        (see predict_from_embedding), else None."""
         out = self.encode_from_seq(inp_seq)
         if self._has_cls:
             out['class'] = out['class'].argmax(-1).astype(np.int32)
@@ -225,7 +233,7 @@ class Transformer(BaseModel, TransformerMetricsMixin):
                 tlen = np.sum(x[..., -1] != 1, axis=-1).reshape(-1)
             else:
                 tlen = np.sum(x > 0, axis=-1).reshape(-1)
-            dec = self.predict_from_embedding(out['embedding'], tlen)
+            dec = self.predict_from_embedding(out['embedding'], tlen, with_attn_weights=with_attn_weights)
             out['recon'] = dec['recon']
             out['attn_weights'] = dec['attn_weights']
         return out
