@@ -670,7 +670,7 @@ extern "C" int skf_attention_fwd_ordered(const float* Q, int ldq, const float* K
   p.order = (B & 7) == 0 ? sample_order : nullptr;      // (the deal needs whole rounds of the 8 XCDs; results never depend on it)
   p.Q = Q; p.K = K; p.V = V; p.O = O; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.key_mask = key_mask; p.key_mask_ld = key_mask_ld; p.causal = causal; p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.stats = stats;
-  { const char* e = skf_knob("SKF_ATTN_XCD"); p.xcd_remap = !(e && e[0] == '0'); }
+  p.xcd_remap = !skf_knob_is("SKF_ATTN_XCD", '0');
 #if SKF_MEASURE
   { const char* db = skf_knob("SKF_ATTN_DBG"); p.dbg = db ? (long long*)strtoull(db, nullptr, 0) : nullptr; }
 #endif
@@ -684,7 +684,7 @@ extern "C" int skf_attention_fwd_ordered(const float* Q, int ldq, const float* K
   // rows it removed 26 % of the MFMA cycles and changed nothing (the forward is wait-bound: 45 % of the wave cycles parked,
   // and the planes cost the fourth resident workgroup per CU); with unpadded rows (four workgroups per CU again, 2-way bank
   // conflicts) it is 4-11 % faster than the fp32-MFMA tiles: 36.4 / 29.0 / 42.1 vs 39.2 / 30.2 / 47.2 us.
-  static const bool split_off = skf_knob("SKF_ATTN_SPLIT") && skf_knob("SKF_ATTN_SPLIT")[0] == '0';
+  static const bool split_off = skf_knob_is("SKF_ATTN_SPLIT", '0');
   const bool split = dh == 16 && !split_off && precision != SKF_PREC_F32;
   const size_t smem = fwd_smem(dh, Lk, split);
   SKF_CHECK_ARG(smem <= 160 * 1024, "K/V of one head do not fit in LDS");
@@ -742,7 +742,7 @@ extern "C" int skf_attention_bwd_ordered(const float* Q, int ldq, const float* K
   p.key_mask = key_mask; p.key_mask_ld = key_mask_ld; p.causal = causal; p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk;
   p.stats = const_cast<float*>(stats);
   { const char* ab = skf_knob("SKF_ATTN_ABLATE"); p.ablate = ab ? atoi(ab) : 0; }
-  { const char* e = skf_knob("SKF_ATTN_XCD"); p.xcd_remap = !(e && e[0] == '0'); }
+  p.xcd_remap = !skf_knob_is("SKF_ATTN_XCD", '0');
 #if SKF_MEASURE
   { const char* db = skf_knob("SKF_ATTN_DBG"); p.dbg = db ? (long long*)strtoull(db, nullptr, 0) : nullptr; }
 #endif

@@ -758,7 +758,7 @@ int set_smem(K kfn, size_t bytes) {
 
 // rows per output tile the launcher will use for this problem (a live-row block list must be built for that height)
 extern "C" int skf_gemm_bf16_tile_rows(int M, int N, int K, int act) {
-  static const bool dma_off = skf_knob("SKF_BF16_GEMM_DMA") && skf_knob("SKF_BF16_GEMM_DMA")[0] == '0';
+  static const bool dma_off = skf_knob_is("SKF_BF16_GEMM_DMA", '0');
   static const int tile_env = skf_knob("SKF_BF16_GEMM_TILE") ? atoi(skf_knob("SKF_BF16_GEMM_TILE")) : 0;
   const bool dma = (K & 63) == 0 && !dma_off;
   // the 256 x 256 tile: one workgroup per CU, so only where there are enough tiles to fill the chip
@@ -808,7 +808,7 @@ extern "C" int skf_gemm_bf16_bits(int M, int N, int K, const void* A, int lda, c
   p.bits_out = (unsigned char*)relu_bits_out; p.bits_in = (const unsigned char*)relu_bits_in; p.ld_bits = ld_bits;
   const bool extra = relu_src || accumulate || C_f32 || relu_bits_in;
   // SKF_BF16_GEMM_DMA=0: register-staged tiles everywhere; SKF_BF16_GEMM_TILE=128: no 256 x 256 tiles (measurement knobs)
-  static const bool dma_off = skf_knob("SKF_BF16_GEMM_DMA") && skf_knob("SKF_BF16_GEMM_DMA")[0] == '0';
+  static const bool dma_off = skf_knob_is("SKF_BF16_GEMM_DMA", '0');
   const bool dma = (K & 63) == 0 && !dma_off;
   const bool big = skf_gemm_bf16_tile_rows(M, N, K, act) == 256;
   const int tile = big ? 256 : 128;
@@ -827,7 +827,7 @@ extern "C" int skf_gemm_bf16_bits(int M, int N, int K, const void* A, int lda, c
     hipLaunchKernelGGL((gemm_bf16_nt_kernel<EX, DM, 64, BG, TH>), dim3(p.tiles_m * p.tiles_n), dim3(BG ? 512 : 256), smem, st, p); \
   }
   // the phased K loop (PH8) for the 256 x 256 tile with at least two 64-deep steps; SKF_BF16_GEMM_PH8=0 (measurement builds): the two-buffer loop
-  static const bool ph8_off = skf_knob("SKF_BF16_GEMM_PH8") && skf_knob("SKF_BF16_GEMM_PH8")[0] == '0';
+  static const bool ph8_off = skf_knob_is("SKF_BF16_GEMM_PH8", '0');
   const bool ph8 = big && K >= 128 && !ph8_off;
 #define SKF_NT_GO8(EX)                                                                                                       \
   {                                                                                                                          \

@@ -23,6 +23,8 @@ static inline const char* skf_knob(const char* name) { return getenv(name); }
 #else
 static inline const char* skf_knob(const char*) { return nullptr; }
 #endif
+// the knob is set and its value starts with `c`
+static inline bool skf_knob_is(const char* name, char c) { const char* v = skf_knob(name); return v && v[0] == c; }
 
 void skf_set_error(const char* fmt, ...);
 

@@ -955,7 +955,7 @@ int launch_ffn(const FfnFusedParams& p, hipStream_t st) {
   SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_fused_kernel<P, MODE, LNB, POST, PRE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   // one profiler line for the family (the kernel template's forward / backward / LayerNorm-prologue / chained-projection variants,
   // like the epilogue kinds of gemm_wsx); SKF_PROF_FINE=1 (measurement builds): one line per variant
-  static const bool fine = skf_knob("SKF_PROF_FINE") && skf_knob("SKF_PROF_FINE")[0] == '1';
+  static const bool fine = skf_knob_is("SKF_PROF_FINE", '1');
   static const std::string tag = std::string("ffn_fused") + (!fine ? "" : MODE == 0 ? (PRE ? (POST ? "_fwd_pre_proj" : "_fwd_pre") : POST ? "_fwd_proj" : "_fwd") : LNB ? "_bwd_ln" : "_bwd") +
                                  "<d128,dff512,bf16x" + std::to_string(P * (P + 1) / 2) + ">";
   const double live = skf_prof_list_fraction(p.row_blocks);

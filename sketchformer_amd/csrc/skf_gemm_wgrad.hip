@@ -458,8 +458,6 @@ __global__ __launch_bounds__(64 * NW, SKF_WGRAD_OCC) void wgrad_x_group_kernel(W
 // (the caller runs the slab reduction).  p.k_chunk must already be set (multiple of 64).
 int skf_gemm_wgrad_dispatch(const GemmParams& p, int a_kcontig, int b_kcontig, int splits, hipStream_t st, int* handled) {
   *handled = 0;
-  const char* off = skf_knob("SKF_GEMM_NO_WGRAD");
-  if (off && off[0] == '1') return SKF_OK;
   if (a_kcontig || b_kcontig) return SKF_OK;
   if ((p.M & 3) || (p.N & 3) || (p.lda & 3) || (p.ldb & 3) || ((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15)) return SKF_OK;
   if (((uintptr_t)p.slab & 15) || (p.k_chunk & 63)) return SKF_OK;
@@ -502,9 +500,7 @@ int skf_gemm_wgrad_dispatch(const GemmParams& p, int a_kcontig, int b_kcontig, i
 // (split arithmetic, aligned, 32-bit offsets); *handled = 0 when any is not (the caller then issues them one by one).
 int skf_gemm_wgrad_group_dispatch(const GemmParams* ps, const int* splits, int n, hipStream_t st, int* handled) {
   *handled = 0;
-  const char* off = skf_knob("SKF_GEMM_NO_WGRAD");
-  static const bool group_off = skf_knob("SKF_NO_WGRAD_GROUP") && skf_knob("SKF_NO_WGRAD_GROUP")[0] == '1';
-  if ((off && off[0] == '1') || group_off || n < 2 || n > kWgradGroupMax) return SKF_OK;
+  if (n < 2 || n > kWgradGroupMax) return SKF_OK;
   WgradGroup grp{};
   grp.n = n;
   int cursor = 0;

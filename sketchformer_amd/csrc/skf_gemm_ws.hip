@@ -338,8 +338,6 @@ static int ws_launch_one(const GemmParams& p, int b_kcontig, hipStream_t st) {
 
 int skf_gemm_ws_dispatch(const GemmParams& p, int a_kcontig, int b_kcontig, hipStream_t st, int* handled) {
   *handled = 0;
-  const char* off = skf_knob("SKF_GEMM_NO_WS");
-  if (off && off[0] == '1') return SKF_OK;
   if (!a_kcontig || p.M < 1024) return SKF_OK;
   // K in {128,256,384,512} = one launch; longer K (a multiple of 128 up to 2048: dff = 1024 / 2048, the 3d-wide qkv dgrad
   // at d = 256) = a chain of <= 512-deep launches over column slices of A / row slices of B, every launch after the first
@@ -347,12 +345,11 @@ int skf_gemm_ws_dispatch(const GemmParams& p, int a_kcontig, int b_kcontig, hipS
   const bool single = p.K == 128 || p.K == 256 || p.K == 384 || p.K == 512;
   const bool chain = !single && p.K > 512 && p.K <= 2048 && (p.K & 127) == 0 && p.act == 0 && !p.relu_src;
   // Input-gradient form with any K % 4 == 0 (the logits layer: K = vocabulary = 1004 / 10004), split arithmetic only: 512-deep
-  // slices, the last one masked (GemmParams::k_valid).  SKF_NO_MASKED_CHAIN=1 keeps such shapes on the generic kernel.
-  static const bool masked_off = skf_knob("SKF_NO_MASKED_CHAIN") && skf_knob("SKF_NO_MASKED_CHAIN")[0] == '1';
+  // slices, the last one masked (GemmParams::k_valid).
   const bool fits32m = (double)p.M * p.lda * 4 < 2147483648.0 && (double)p.M * p.ldc * 4 < 2147483648.0;
   // (round 6: up to 16384 - the grid tokenizer's vocabulary of 10004 is twenty 512-deep launches, ~0.45 ms instead of ONE 0.85-ms launch of
   //  the generic fp32-MFMA kernel; every launch after the first re-reads and rewrites the 13 MB of C)
-  const bool chain_masked = !single && !chain && !masked_off && b_kcontig && p.precision != SKF_PREC_F32 && fits32m && p.K > 512 &&
+  const bool chain_masked = !single && !chain && b_kcontig && p.precision != SKF_PREC_F32 && fits32m && p.K > 512 &&
                             p.K <= 16384 && (p.K & 3) == 0 && p.act == 0 && !p.relu_src && !p.relu_bits_in && !p.relu_bits_out && !p.bias;
   if (!single && !chain && !chain_masked) return SKF_OK;
   if ((p.N & 3) || (p.lda & 3) || (p.ldc & 3) || ((uintptr_t)p.A & 15) || ((uintptr_t)p.C & 15)) return SKF_OK;

@@ -594,7 +594,7 @@ int launch_wsx(const GemmParams& p, int b_kc, hipStream_t st) {
   const double a_c = (double)p.M * p.K + (double)p.M * p.N * ((p.accumulate ? 1 : 0) + (p.relu_src && !p.relu_bits_in ? 1 : 0));
   const double ln_c = p.ln_out ? 2.0 * p.M * p.N : 0.0;
   // SKF_PROF_FINE=1 (analysis only): one table line per output width and epilogue
-  static const bool fine = skf_knob("SKF_PROF_FINE") && skf_knob("SKF_PROF_FINE")[0] == '1';
+  static const bool fine = skf_knob_is("SKF_PROF_FINE", '1');
   static std::set<std::string> fine_tags;           // the profiler keeps the pointer: interned
   const char* ftag = nullptr;
   if (fine) ftag = fine_tags.insert(tag + "[N" + std::to_string(p.N) + (b_kc ? ",dgrad" : "") + (p.relu_bits_in ? ",bits" : "") + (p.relu_src ? ",relu_src" : "") +
@@ -668,18 +668,18 @@ int launch_wsx_k(const GemmParams& p, int b_kc, hipStream_t st) {
       // K = 256: only for N <= 128 (one or two column groups, 256 workgroups either way); with more column groups the 512-thread form
       // was 4 % slower at cfg 3 (N = 256 ... 1024).  SKF_WSX_KSPLIT256=1 forces it for every N, =0 turns it off (measurement)
       static const char* ks2 = skf_knob("SKF_WSX_KSPLIT256");
-      const bool ks_on2 = ks2 ? ks2[0] == '1' : (p.N <= 128 && !(skf_knob("SKF_WSX_KSPLIT") && skf_knob("SKF_WSX_KSPLIT")[0] == '0'));
+      const bool ks_on2 = ks2 ? ks2[0] == '1' : (p.N <= 128 && !skf_knob_is("SKF_WSX_KSPLIT", '0'));
       if (ks_on2 && p.act == 0) return launch_wsx<256, 1, P, 2>(p, b_kc, st);
       return launch_wsx<256, 1, P>(p, b_kc, st);
     }
     case 384: {
-      static const bool ks_off3 = (skf_knob("SKF_WSX_KSPLIT") && skf_knob("SKF_WSX_KSPLIT")[0] == '0') || (skf_knob("SKF_WSX_KSPLIT384") && skf_knob("SKF_WSX_KSPLIT384")[0] == '0');
+      static const bool ks_off3 = skf_knob_is("SKF_WSX_KSPLIT", '0') || skf_knob_is("SKF_WSX_KSPLIT384", '0');
       if (!ks_off3 && p.act == 0) return launch_wsx<384, 1, P, 2>(p, b_kc, st);
       return launch_wsx<384, 1, P>(p, b_kc, st);
     }
     default: {
       // K = 512 without an activation: the contraction split between wave pairs (two waves per SIMD); SKF_WSX_KSPLIT=0: A/B knob
-      static const bool ks_off = skf_knob("SKF_WSX_KSPLIT") && skf_knob("SKF_WSX_KSPLIT")[0] == '0';
+      static const bool ks_off = skf_knob_is("SKF_WSX_KSPLIT", '0');
       if (!ks_off && p.act == 0) return launch_wsx<512, 1, P, 2>(p, b_kc, st);
       return launch_wsx<512, 1, P>(p, b_kc, st);
     }

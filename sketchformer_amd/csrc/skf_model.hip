@@ -14,23 +14,6 @@
 #include "skf_decode_fused.h"
 
 // ------------------------------------------------------------------ error plumbing
-#if SKF_MEASURE
-// measurement builds: SKF_EVLOG=1 lists every event record / stream wait of the THIRD train step with its source line and stream
-// (tools: which packets still sit on the main stream between two kernels)
-static hipStream_t g_evlog_main = nullptr;
-static int g_evlog_step = 0;
-static inline bool evlog_on() { static const bool on = skf_knob("SKF_EVLOG") != nullptr; return on && g_evlog_step == 3; }
-static inline hipError_t skf_logged_record(hipEvent_t e, hipStream_t st, int line) {
-  if (evlog_on()) fprintf(stderr, "EVLOG record line %d on %s\n", line, st == g_evlog_main ? "MAIN" : "side");
-  return hipEventRecord(e, st);
-}
-static inline hipError_t skf_logged_wait(hipStream_t st, hipEvent_t e, unsigned f, int line) {
-  if (evlog_on()) fprintf(stderr, "EVLOG wait   line %d on %s\n", line, st == g_evlog_main ? "MAIN" : "side");
-  return hipStreamWaitEvent(st, e, f);
-}
-#define hipEventRecord(e, st) skf_logged_record(e, st, __LINE__)
-#define hipStreamWaitEvent(st, e, f) skf_logged_wait(st, e, f, __LINE__)
-#endif
 static thread_local char g_err[512] = "";
 thread_local hipEvent_t skf_tls_stop_event = nullptr;      // skf_common.h: an event for the next SKF_LAUNCH_TAIL launch of this thread
 void skf_set_error(const char* fmt, ...) {
@@ -417,9 +400,8 @@ Plan build_plan(const SkfConfig& c) {
   // is written twice in a step and those waits are gone (cfg 2: 8 x 170 MB); above 8 GB the sets fall back to two.
   {
     const size_t per_set = (3 * Me * d + Me * F + Md * d + Me * 2 * d + Me * 3 * d) * f;
-    static const bool two_sets = skf_knob("SKF_TWO_GRAD_SETS") && skf_knob("SKF_TWO_GRAD_SETS")[0] == '1';      // (measurement builds)
     const size_t layers = (size_t)c.num_layers * (do_recon(c) ? 2 : 1);
-    P.n_gs = (two_sets || per_set * layers > ((size_t)8 << 30) || layers < 2) ? 2 : (int)layers;
+    P.n_gs = (per_set * layers > ((size_t)8 << 30) || layers < 2) ? 2 : (int)layers;
     P.gs.resize(P.n_gs);
   }
   for (int k = 0; k < P.n_gs; ++k) {
@@ -452,7 +434,7 @@ Plan build_plan(const SkfConfig& c) {
   if (2 * B * L * f > s) s = 2 * B * L * f;
   if (c.continuous && skf_embed_continuous_bwd_workspace_bytes((int)Me, (int)d) > s) s = skf_embed_continuous_bwd_workspace_bytes((int)Me, (int)d);
   P.small_ws_bytes = s; P.small_ws = b.take(s);
-  if (!c.continuous && c.vocab_size <= 12288 && c.d_model <= 512 && !skf_knob("SKF_NO_EMBED_SORT")) {   // (the sorted kernel's partial slab is sized for rows of <= 512 floats)
+  if (!c.continuous && c.vocab_size <= 12288 && c.d_model <= 512) {   // (the sorted kernel's partial slab is sized for rows of <= 512 floats)
     P.emb_sort_bytes = (skf_embed_sort_workspace_bytes((int)B, (int)L, c.vocab_size) + 255) & ~(size_t)255;
     P.emb_sort[0] = b.take(P.emb_sort_bytes); P.emb_sort[1] = b.take(P.emb_sort_bytes);
   }
@@ -506,7 +488,6 @@ struct SkfModel {
   // buffers share one `done` event: one barrier packet on the main stream instead of seven, ~5 us each)
   struct SideEvent { hipEvent_t e; long seq; };
   long side_seq = 0, side_waited = 0;
-  bool no_wait_dedupe = skf_knob("SKF_NO_WAIT_DEDUPE") && skf_knob("SKF_NO_WAIT_DEDUPE")[0] == '1';     // A/B knob
   std::map<const void*, SideEvent> pending_readers;    // buffer -> completion event of its last side-stream reader
   // kind 0: dW = X^T dY (+ bias grad); kind 1: an input gradient nobody on the main stream needs soon (dx (+)= dY W^T)
   struct QueuedWgrad { DenseP w; const float* x; int ldx; const float* dy; int lddy; int rows; int kind = 0; float* dx = nullptr; int lddx = 0; int accumulate = 0; const int* blocks32 = nullptr; };
@@ -535,10 +516,9 @@ struct SkfModel {
     if (next_event == events.size()) {
       hipEvent_t e = nullptr;
       // Events that only order the library's own two streams on ONE device: a device-scope release is all the waiter needs
-      // (the default system-scope fence of hipEventRecord writes caches back for host / peer visibility).  SKF_EVENT_SCOPE=system
-      // restores the default for A/B measurements.  (The gradient-bucket events handed to the caller keep the default.)
-      static const bool sys_scope = skf_knob("SKF_EVENT_SCOPE") && skf_knob("SKF_EVENT_SCOPE")[0] == 's';
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming | (sys_scope ? 0u : hipEventReleaseToDevice)) != hipSuccess) return nullptr;
+      // (the default system-scope fence of hipEventRecord writes caches back for host / peer visibility).  (The gradient-bucket
+      // events handed to the caller keep the default.)
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return nullptr;
       events.push_back(e);
     }
     return events[next_event++];
@@ -563,11 +543,10 @@ int dense_fwd(SkfModel* M, const DenseP& w, const float* x, int rows, float* y, 
                       nullptr, 0, nullptr, 0, M->cfg.gemm_precision, s);
 }
 // y = Dense(a); z = x + dropout(y); out = LayerNorm(z): one launch where the fused kernel exists (the attention output projection
-// at d_model = 128 in the split-arithmetic modes), else the Dense launch followed by the LayerNorm launch.  SKF_NO_LN_FUSE=1: A/B knob.
+// at d_model = 128 in the split-arithmetic modes), else the Dense launch followed by the LayerNorm launch.
 int dense_ln_fwd(SkfModel* M, const DenseP& w, const float* a, int rows, const float* x, float* z, const LnP& ln, float* out,
                  float* stats, float rate, unsigned site, hipStream_t s) {
-  static const bool fuse_off = skf_knob("SKF_NO_LN_FUSE") && skf_knob("SKF_NO_LN_FUSE")[0] == '1';
-  if (!fuse_off && !M->no_ln_fuse && skf_gemm_ln_residual_supported(rows, w.out, w.in, M->cfg.gemm_precision)) {
+  if (!M->no_ln_fuse && skf_gemm_ln_residual_supported(rows, w.out, w.in, M->cfg.gemm_precision)) {
     const int rc = skf_gemm_ln_residual_f32(rows, w.out, w.in, a, w.in, M->P(w.w), w.ld, M->P(w.b), x, M->P(ln.g), M->P(ln.b), z, out, stats,
                                             rate, site, M->state, M->cfg.gemm_precision, s);
     // the shape test above does not see pitches / alignment: a launch the fused entry declines takes the general pair (from now on)
@@ -577,11 +556,10 @@ int dense_ln_fwd(SkfModel* M, const DenseP& w, const float* a, int rows, const f
   SKF_TRY(dense_fwd(M, w, a, rows, z, 0, s));
   return skf_layernorm_residual_fwd(x, z, M->P(ln.g), M->P(ln.b), out, stats, rows, w.out, rate, site, M->state, s);
 }
-// sign-bit buffer of an ffn hidden tensor (rows x dff from d inputs), or null when the shape has no such path / SKF_NO_RELU_BITS=1
+// sign-bit buffer of an ffn hidden tensor (rows x dff from d inputs), or null when the shape has no such path
 void* hbits_of(SkfModel* M, size_t off, int rows) {
-  static const bool bits_off = skf_knob("SKF_NO_RELU_BITS") && skf_knob("SKF_NO_RELU_BITS")[0] == '1';
   if (M->ffn_fused) return M->at<char>(off);      // (the fused block always writes / reads its own sign-bit words)
-  if (bits_off || M->no_relu_bits || !skf_gemm_relu_bits_bytes(rows, M->cfg.dff, M->cfg.d_model, M->cfg.gemm_precision)) return nullptr;
+  if (M->no_relu_bits || !skf_gemm_relu_bits_bytes(rows, M->cfg.dff, M->cfg.d_model, M->cfg.gemm_precision)) return nullptr;
   return M->at<char>(off);
 }
 // ffn dense1 (relu): also leaves the sign bits of the hidden tensor for the backward when the shape has that path (bits != null)
@@ -610,26 +588,43 @@ int issue_held_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded = nu
 // The "main stream has reached this point" event of a held weight-gradient group as the COMPLETION SIGNAL of the launch in front of it
 // (skf_common.h: SKF_LAUNCH_TAIL) instead of a packet of its own: park_ready() before the launcher, take_ready() behind it - the
 // event when the launcher attached it, null when it did not (or nothing is held / the step is being captured).
-hipEvent_t park_ready(SkfModel* M);
+// park_fresh(): the same for a group that is issued right behind ONE call's last launch (no held group needed).
+hipEvent_t park_fresh(SkfModel* M) {
+  if (!M->side || g_capturing) return nullptr;
+  hipEvent_t e = M->new_event();
+  skf_tls_stop_event = e;
+  return e;
+}
+hipEvent_t park_ready(SkfModel* M) { return M->wq_held.empty() ? nullptr : park_fresh(M); }
 hipEvent_t take_ready(hipEvent_t parked) {
   const bool attached = parked && skf_tls_stop_event == nullptr;
   skf_tls_stop_event = nullptr;
   return attached ? parked : nullptr;
 }
+// The main stream waits for the side-stream event `pending` holds for `buf` (unless it already waited for a later one); a queued or
+// held group that `touches` the buffer is issued first.
+template <typename Touches>
+int wait_side(SkfModel* M, std::map<const void*, SkfModel::SideEvent>& pending, const void* buf, hipStream_t s, Touches touches) {
+  for (const auto* qs : {&M->wq_held, &M->wq})
+    for (const auto& q : *qs)
+      if (touches(q)) { SKF_TRY(issue_wgrads(M, s)); break; }
+  auto it = pending.find(buf);
+  if (it == pending.end()) return SKF_OK;
+  if (it->second.seq > M->side_waited) {
+    SKF_HIP(hipStreamWaitEvent(s, it->second.e, 0));
+    M->side_waited = it->second.seq;
+  }
+  pending.erase(it);
+  return SKF_OK;
+}
 // Main-stream kernels that overwrite `buf` must first wait for the side-stream wgrad that still reads it
 // (a wgrad that is still queued is issued first; with the alternating gradient-buffer sets this is the rare case).
 int before_write(SkfModel* M, const void* buf, hipStream_t s) {
-  for (const auto* qs : {&M->wq_held, &M->wq})
-    for (const auto& q : *qs)
-      if (q.dy == buf || q.x == buf) { SKF_TRY(issue_wgrads(M, s)); break; }
-  auto it = M->pending_readers.find(buf);
-  if (it == M->pending_readers.end()) return SKF_OK;
-  if (it->second.seq > M->side_waited || M->no_wait_dedupe) {
-    SKF_HIP(hipStreamWaitEvent(s, it->second.e, 0));
-    M->side_waited = std::max(M->side_waited, it->second.seq);
-  }
-  M->pending_readers.erase(it);
-  return SKF_OK;
+  return wait_side(M, M->pending_readers, buf, s, [buf](const SkfModel::QueuedWgrad& q) { return q.dy == buf || q.x == buf; });
+}
+// Main-stream kernels that read `buf` first wait for the side-stream dgrad that writes it.
+int before_read(SkfModel* M, const void* buf, hipStream_t s) {
+  return wait_side(M, M->pending_writers, buf, s, [buf](const SkfModel::QueuedWgrad& q) { return q.kind == 1 && q.dx == buf; });
 }
 // dW = X^T dY (+ bias grad).  Eager path: queued, and issued per layer on the side stream by issue_wgrads().
 int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const float* dy, int lddy, int rows, hipStream_t s) {
@@ -639,20 +634,12 @@ int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const flo
   M->wq.push_back(q);
   return SKF_OK;
 }
-// Main-stream kernels that read `buf` first wait for the side-stream dgrad that writes it.
-int before_read(SkfModel* M, const void* buf, hipStream_t s) {
-  for (const auto* qs : {&M->wq_held, &M->wq})
-    for (const auto& q : *qs)
-      if (q.kind == 1 && q.dx == buf) { SKF_TRY(issue_wgrads(M, s)); break; }
-  auto it = M->pending_writers.find(buf);
-  if (it == M->pending_writers.end()) return SKF_OK;
-  if (it->second.seq > M->side_waited || M->no_wait_dedupe) {
-    SKF_HIP(hipStreamWaitEvent(s, it->second.e, 0));
-    M->side_waited = std::max(M->side_waited, it->second.seq);
-  }
-  M->pending_writers.erase(it);
-  return SKF_OK;
-}
+// side-stream launches must never pick up an event that is parked for the main stream's next launch
+struct ParkedEventGuard {
+  hipEvent_t saved;
+  ParkedEventGuard() : saved(skf_tls_stop_event) { skf_tls_stop_event = nullptr; }
+  ~ParkedEventGuard() { skf_tls_stop_event = saved; }
+};
 // Issue the queued wgrads on the side stream: ONE ready event (everything queued on `s` so far is complete before they
 // start) and ONE done event for the whole group; they are serialized among themselves and joined before the optimizer.
 // The fused feed-forward backward is the FIRST kernel of a layer's backward, and its workgroups (147 KB of LDS, two waves per SIMD)
@@ -660,27 +647,6 @@ int before_read(SkfModel* M, const void* buf, hipStream_t s) {
 // stream, the block on the main stream - they ran one after the other (134 + 136 us where 45 + 100 were expected, per layer).  So a
 // layer's group is HELD at the end of the layer and goes out right behind the next layer's first launch: it then runs beside the
 // LayerNorm / projection / attention kernels of that layer, which share CUs with it well.
-hipEvent_t park_ready(SkfModel* M) {
-  static const bool off = skf_knob("SKF_NO_STOP_EVENTS") && skf_knob("SKF_NO_STOP_EVENTS")[0] == '1';   // (measurement builds only)
-  if (off || M->wq_held.empty() || !M->side || g_capturing) return nullptr;
-  hipEvent_t e = M->new_event();
-  skf_tls_stop_event = e;
-  return e;
-}
-// the same for a group that is issued right behind ONE call's last launch (no held group needed): a fresh event, or null
-hipEvent_t park_fresh(SkfModel* M) {
-  static const bool off = skf_knob("SKF_NO_STOP_EVENTS") && skf_knob("SKF_NO_STOP_EVENTS")[0] == '1';   // (measurement builds only)
-  if (off || !M->side || g_capturing) return nullptr;
-  hipEvent_t e = M->new_event();
-  skf_tls_stop_event = e;
-  return e;
-}
-// side-stream launches must never pick up an event that is parked for the main stream's next launch
-struct ParkedEventGuard {
-  hipEvent_t saved;
-  ParkedEventGuard() : saved(skf_tls_stop_event) { skf_tls_stop_event = nullptr; }
-  ~ParkedEventGuard() { skf_tls_stop_event = saved; }
-};
 int issue_held_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded) {
   if (M->wq_held.empty()) return SKF_OK;
   std::vector<SkfModel::QueuedWgrad> cur;
@@ -699,14 +665,7 @@ int hold_wgrads(SkfModel* M, hipStream_t s) {
 // the backward that the side stream would finish last (see run_backward)
 int issue_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool on_main) {
   ParkedEventGuard guard;                                      // (this function may run INSIDE a parked call: before_write)
-  if (!M->wq_held.empty()) {                                   // the held group first, as a group of its own
-    std::vector<SkfModel::QueuedWgrad> cur;
-    cur.swap(M->wq);
-    M->wq.swap(M->wq_held);
-    const int rc = issue_wgrads(M, s);
-    M->wq.swap(cur);
-    if (rc != SKF_OK) return rc;
-  }
+  SKF_TRY(issue_held_wgrads(M, s));                            // the held group first, as a group of its own
   if (M->wq.empty()) return SKF_OK;
   std::vector<SkfModel::QueuedWgrad> group;
   group.swap(M->wq);
@@ -799,8 +758,7 @@ int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_
     }
     // LayerNorm partials and the embedding gradients of this bucket were written by the main stream: the batched
     // reduction (wgrad slabs + LayerNorm partials) and the bucket-ready event are ordered after both streams
-    static const bool tail_on_main = !(skf_knob("SKF_TAIL_REDUCE_SIDE") && skf_knob("SKF_TAIL_REDUCE_SIDE")[0] == '1');
-    if (final && tail_on_main) {
+    if (final) {
       // end of the backward: the optimizer waits for this reduction anyway, so it runs on the MAIN stream behind ONE hop
       // (side -> main after the last weight gradient) instead of two (main -> side for the partials, side -> main for the result)
       hipEvent_t e = M->new_event();
@@ -814,21 +772,13 @@ int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_
       bucket_recorded = br && skf_tls_stop_event == nullptr;
       skf_tls_stop_event = nullptr;
       SKF_TRY(rc);
-      ready_on = s;
     } else {
-    hipEvent_t em = main_here ? main_here : M->new_event();      // (main_here: already the completion signal of the main stream's last launch)
-    SKF_CHECK_ARG(em, "event allocation failed");
-    if (!main_here) SKF_HIP(hipEventRecord(em, s));
-    SKF_HIP(hipStreamWaitEvent(M->side, em, 0));
-    SKF_TRY(skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->reduce_blocks, M->side));
-    ready_on = M->side;
-    if (final) {
-      hipEvent_t e = M->new_event();
-      SKF_CHECK_ARG(e, "event allocation failed");
-      SKF_HIP(hipEventRecord(e, M->side));
-      SKF_HIP(hipStreamWaitEvent(s, e, 0));
-      ready_on = s;
-    }
+      hipEvent_t em = main_here ? main_here : M->new_event();      // (main_here: already the completion signal of the main stream's last launch)
+      SKF_CHECK_ARG(em, "event allocation failed");
+      if (!main_here) SKF_HIP(hipEventRecord(em, s));
+      SKF_HIP(hipStreamWaitEvent(M->side, em, 0));
+      SKF_TRY(skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->reduce_blocks, M->side));
+      ready_on = M->side;
     }
   }
   if (bucket >= 0 && M->bucket_ready[bucket] && !bucket_recorded) SKF_HIP(hipEventRecord(M->bucket_ready[bucket], ready_on));   // bucket < 0: an intermediate reduction
@@ -858,8 +808,7 @@ int dense_dgrad(SkfModel* M, const DenseP& w, const float* dy, int lddy, int row
 // before_read(dx).  Successive deferred writers of one dx stay in order (one side stream).
 int dense_dgrad_deferred(SkfModel* M, const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate,
                          hipStream_t s) {
-  static const bool off = skf_knob("SKF_NO_DEFERRED_DGRAD") != nullptr;
-  if (!M->side || off) return dense_dgrad(M, w, dy, lddy, rows, dx, lddx, accumulate, nullptr, 0, s);
+  if (!M->side) return dense_dgrad(M, w, dy, lddy, rows, dx, lddx, accumulate, nullptr, 0, s);
   SkfModel::QueuedWgrad q{w, nullptr, 0, dy, lddy, rows};
   q.kind = 1; q.dx = dx; q.lddx = lddx; q.accumulate = accumulate;
   M->wq.push_back(q);
@@ -897,8 +846,7 @@ int classify_fwd(SkfModel* M, bool training, hipStream_t s) {
 // checkpoint restore, a test - did not have to tell the library).
 bool ffn_fused_on(const SkfModel* M) {
   const SkfConfig& c = M->cfg;
-  static const bool off = skf_knob("SKF_NO_FFN_FUSE") && skf_knob("SKF_NO_FFN_FUSE")[0] == '1';   // (measurement builds only)
-  return !off && !(M->flags & SKF_MODEL_FFN_LAUNCHES) && skf_ffn_fused_supported(c.batch * c.seq_len, c.d_model, c.dff, c.gemm_precision) &&
+  return !(M->flags & SKF_MODEL_FFN_LAUNCHES) && skf_ffn_fused_supported(c.batch * c.seq_len, c.d_model, c.dff, c.gemm_precision) &&
          skf_ffn_image_bytes(c.d_model, c.dff, c.gemm_precision) > 0;
 }
 int build_ffn_images(SkfModel* M, bool with_backward, bool encoder_only, hipStream_t s) {
@@ -940,9 +888,8 @@ int ffn_ln_fwd(SkfModel* M, const DenseP& f1, const DenseP& f2, const LnP& ln, c
                const void* image, float* z, float* out, float* stats, float rate, unsigned site, hipStream_t s,
                const DenseP* next = nullptr, const void* next_image = nullptr, float* next_out = nullptr, bool* next_done = nullptr) {
   const int d = M->cfg.d_model;
-  static const bool chain_off = skf_knob("SKF_NO_FFN_CHAIN") && skf_knob("SKF_NO_FFN_CHAIN")[0] == '1';   // (measurement builds only)
   if (next_done) *next_done = false;
-  if (M->ffn_fused && next && !chain_off && next->in == d && (next->out == 128 || next->out == 256 || next->out == 384) && next->ld == next->out) {
+  if (M->ffn_fused && next && next->in == d && (next->out == 128 || next->out == 256 || next->out == 384) && next->ld == next->out) {
     if (next_done) *next_done = true;
     return skf_ffn_fused_fwd_proj_f32(rows, d, M->cfg.dff, x, image, M->P(f1.b), M->P(f2.b), h, bits, M->P(ln.g), M->P(ln.b), z, out, stats,
                                       rate, site, M->state, next_image, M->P(next->b), next->out, next_out, M->cfg.gemm_precision, s);
@@ -963,9 +910,7 @@ int attn_tail_ffn_fwd(SkfModel* M, const DenseP& o, const LnP& ln_a, const float
                       const void* image, float* z, float* out, float* stats, unsigned site, int rows, float rate, hipStream_t s,
                       const DenseP* next, const void* next_image, float* next_out, bool* next_done) {
   const int d = M->cfg.d_model;
-  static const bool pre_off = skf_knob("SKF_NO_FFN_PRE") && skf_knob("SKF_NO_FFN_PRE")[0] == '1';   // (measurement builds only)
-  static const bool chain_off = skf_knob("SKF_NO_FFN_CHAIN") && skf_knob("SKF_NO_FFN_CHAIN")[0] == '1';
-  if (!M->ffn_fused || pre_off || o.in != d || o.out != d || ln_a.b != ln_a.g + (size_t)d) {
+  if (!M->ffn_fused || o.in != d || o.out != d || ln_a.b != ln_a.g + (size_t)d) {
     SKF_TRY(dense_ln_fwd(M, o, a, rows, x, z1, ln_a, x1, st1, rate, site_a, s));
     return ffn_ln_fwd(M, f1, f2, ln, x1, rows, h, bits, image, z, out, stats, rate, site, s, next, next_image, next_out, next_done);
   }
@@ -975,7 +920,7 @@ int attn_tail_ffn_fwd(SkfModel* M, const DenseP& o, const LnP& ln_a, const float
   b.gamma = M->P(ln.g); b.beta = M->P(ln.b); b.z = z; b.out = out; b.stats = stats; b.rate = rate; b.site = site; b.step_state = M->state;
   b.pre_image = o_image; b.pre_bias = M->P(o.b); b.pre_residual = x; b.pre_gamma = M->P(ln_a.g); b.pre_beta = M->P(ln_a.b);
   b.pre_z = z1; b.pre_out = x1; b.pre_stats = st1; b.pre_site = site_a;
-  const bool chain = next && !chain_off && next->in == d && (next->out == 128 || next->out == 256 || next->out == 384) && next->ld == next->out;
+  const bool chain = next && next->in == d && (next->out == 128 || next->out == 256 || next->out == 384) && next->ld == next->out;
   if (chain) { b.proj_image = next_image; b.proj_bias = M->P(next->b); b.proj_out = next_out; b.proj_n = next->out; }
   if (next_done) *next_done = chain;
   return skf_ffn_block_fwd_f32(&b, s);
@@ -999,9 +944,8 @@ int forward_preamble(SkfModel* M, bool with_backward, bool encoder_only, hipStre
     SKF_TRY(skf_padding_mask(M->at<long long>(P.inp), Le, B, Le, emask, s));
     SKF_TRY(skf_padding_mask(M->at<long long>(P.tar), Le, B, Ld, dmask, s));
   }
-  static const bool order_off = skf_knob("SKF_ATTN_ORDER") && skf_knob("SKF_ATTN_ORDER")[0] == '0';      // (measurement builds)
   M->order = nullptr;
-  if (!order_off && B <= 4096) {
+  if (B <= 4096) {
     SKF_TRY(skf_sample_order(emask, Le, Le, encoder_only ? nullptr : dmask, Ld, Ld, B, M->at<int>(P.order), s));
     M->order = M->at<int>(P.order);
   }
@@ -1110,8 +1054,7 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
   hipEvent_t kv_done = nullptr, kv_first = nullptr;
   if (M->side) {
     kv_done = M->new_event();
-    static const bool wait_all = skf_knob("SKF_KV_WAIT_ALL") && skf_knob("SKF_KV_WAIT_ALL")[0] == '1';      // (measurement builds)
-    kv_first = N > 1 && !wait_all ? M->new_event() : kv_done;
+    kv_first = N > 1 ? M->new_event() : kv_done;
     SKF_CHECK_ARG(dec_in_ready && kv_done && kv_first, "event allocation failed");
     if (!dec_in_recorded) SKF_HIP(hipEventRecord(dec_in_ready, s));
     SKF_HIP(hipStreamWaitEvent(M->side, dec_in_ready, 0));
@@ -1132,8 +1075,7 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
                                       M->at<float>(a.o1), d, M->at<float>(a.astats1), M->cfg.gemm_precision, order, s));
     // out1 = LayerNorm(x + dropout(o1 . Wo + bo)) and q2 = out1 . Wq + bq: one row-owner launch where that kernel runs
     // (skf_ffn_block_fwd_f32 without a feed-forward image), else the fused Dense + LayerNorm launch and the projection launch
-    static const bool tail_off = skf_knob("SKF_NO_TAIL_PROJ") && skf_knob("SKF_NO_TAIL_PROJ")[0] == '1';   // (measurement builds only)
-    const bool tail_proj = M->ffn_fused && !tail_off && w.mha1.o.in == d && w.mha1.o.out == d && w.mha2.q.in == d && w.mha2.q.out == d &&
+    const bool tail_proj = M->ffn_fused && w.mha1.o.in == d && w.mha1.o.out == d && w.mha2.q.in == d && w.mha2.q.out == d &&
                            w.mha2.q.ld == d && w.ln1.b == w.ln1.g + (size_t)d;
     if (tail_proj) {
       SkfFfnBlockFwd tb{};
@@ -1283,9 +1225,8 @@ int ffn_ln_bwd(SkfModel* M, const LnP& ln, const DenseP& f1, const DenseP& f2, c
   const Plan& P = M->plan;
   const int d = M->cfg.d_model;
   M->last_ready = nullptr;
-  static const bool ln_off = skf_knob("SKF_NO_FFN_LN_BWD") && skf_knob("SKF_NO_FFN_LN_BWD")[0] == '1';   // (measurement builds only)
   const size_t pbytes = (size_t)skf_ffn_fused_ln_partials(rows) * 2 * d * sizeof(float);
-  if (ln_off || !M->ffn_fused || !M->side || ln.b != ln.g + (size_t)d || pbytes > P.ln_part_stride) {
+  if (!M->ffn_fused || !M->side || ln.b != ln.g + (size_t)d || pbytes > P.ln_part_stride) {
     SKF_TRY(ln_bwd(M, ln, dout, z, st, dx, dy, rows, rate, site, s));
     return ffn_bwd(M, f1, f2, x_in, h, dy, dh, dx, rows, s, hbits, image_t);
   }
@@ -1314,9 +1255,8 @@ int ffn_ln_bwd(SkfModel* M, const LnP& ln, const DenseP& f1, const DenseP& f2, c
 bool ln_oproj_bwd_takes_lead(SkfModel* M, const LnP& ln, const DenseP& o, const DenseP& lead_w, int rows) {
   const Plan& P = M->plan;
   const int d = M->cfg.d_model;
-  static const bool off = (skf_knob("SKF_NO_LN_DGRAD") && skf_knob("SKF_NO_LN_DGRAD")[0] == '1') || (skf_knob("SKF_NO_LN_LEAD") && skf_knob("SKF_NO_LN_LEAD")[0] == '1');
   const size_t pbytes = (size_t)skf_layernorm_bwd_dgrad_partials(rows) * 2 * d * sizeof(float);
-  return !off && M->ffn_fused && M->side && ln.b == ln.g + (size_t)d && pbytes <= P.ln_part_stride && o.in == d && o.out == d &&
+  return M->ffn_fused && M->side && ln.b == ln.g + (size_t)d && pbytes <= P.ln_part_stride && o.in == d && o.out == d &&
          lead_w.in == d && lead_w.out == d && skf_layernorm_bwd_dgrad_supported(rows, d, M->cfg.gemm_precision);
 }
 int ln_oproj_bwd(SkfModel* M, const LnP& ln, const DenseP& o, const float* dout, const float* z, const float* st, const float* a_in,
@@ -1324,9 +1264,8 @@ int ln_oproj_bwd(SkfModel* M, const LnP& ln, const DenseP& o, const float* dout,
                  const float* lead_a = nullptr, const void* lead_image_t = nullptr) {
   const Plan& P = M->plan;
   const int d = M->cfg.d_model;
-  static const bool off = skf_knob("SKF_NO_LN_DGRAD") && skf_knob("SKF_NO_LN_DGRAD")[0] == '1';   // (measurement builds only)
   const size_t pbytes = (size_t)skf_layernorm_bwd_dgrad_partials(rows) * 2 * d * sizeof(float);
-  if (off || !M->ffn_fused || !M->side || ln.b != ln.g + (size_t)d || pbytes > P.ln_part_stride || o.in != d || o.out != d ||
+  if (!M->ffn_fused || !M->side || ln.b != ln.g + (size_t)d || pbytes > P.ln_part_stride || o.in != d || o.out != d ||
       !skf_layernorm_bwd_dgrad_supported(rows, d, M->cfg.gemm_precision)) {
     SKF_TRY(ln_bwd(M, ln, dout, z, st, dz, dy, rows, rate, site, s));
     SKF_TRY(dense_wgrad(M, o, a_in, d, dy, d, rows, s));
@@ -1348,9 +1287,8 @@ int ln_oproj_bwd(SkfModel* M, const LnP& ln, const DenseP& o, const float* dout,
 int build_row_lists(SkfModel* M, hipStream_t s) {
   const SkfConfig& c = M->cfg;
   const Plan& P = M->plan;
-  static const bool rows_off = skf_knob("SKF_NO_ROW_BLOCKS") && skf_knob("SKF_NO_ROW_BLOCKS")[0] == '1';
   M->lists_built = false;
-  if (c.continuous || rows_off || !do_recon(c) || c.gemm_precision == SKF_PREC_F32) return SKF_OK;
+  if (c.continuous || !do_recon(c) || c.gemm_precision == SKF_PREC_F32) return SKF_OK;
   const int B = c.batch, Le = c.seq_len, Ld = c.seq_len - 1;
   SKF_TRY(skf_target_live_len(M->at<long long>(P.tar), Le, B, Ld, M->at<int>(P.live_len), s));
   SKF_TRY(skf_row_blocks_build(M->at<int>(P.live_len), B, Ld, 16, M->at<int>(P.live16), s));
@@ -1444,8 +1382,7 @@ int run_backward(SkfModel* M, hipStream_t s) {
                                       dqkv + 2 * d, 3 * d, M->cfg.gemm_precision, qlive, M->order, s));
     SKF_TRY(dense_wgrad(M, w.mha1.qkv, M->at<float>(a.x_in), d, dqkv, 3 * d, Md, s));
     // the 8 weight gradients of this layer: one event pair - held until the next layer's fused feed-forward launch is queued
-    static const bool hold_off = skf_knob("SKF_NO_WGRAD_HOLD") && skf_knob("SKF_NO_WGRAD_HOLD")[0] == '1';   // (measurement builds only)
-    const bool hold = M->ffn_fused && i > 0 && !hold_off;
+    const bool hold = M->ffn_fused && i > 0;
     hipEvent_t parked = hold ? nullptr : park_fresh(M);         // not held: the group's event rides on this layer's last launch
     const int rc_dg = dense_dgrad(M, w.mha1.qkv, dqkv, 3 * d, Md, G2, d, 1, nullptr, 0, s);
     const hipEvent_t ready = take_ready(parked);
@@ -1480,8 +1417,7 @@ int run_backward(SkfModel* M, hipStream_t s) {
   hipEvent_t bott_ready = nullptr;
   if (bott) {
     // expander, classifier
-    static const bool part_off = skf_knob("SKF_NO_BOTT_PARTIALS") && skf_knob("SKF_NO_BOTT_PARTIALS")[0] == '1';   // (measurement builds only)
-    const bool defer_sums = !part_off && M->side && Ua <= 4096;      // (wherever the batched reduction runs: the eager step and its two-stream capture)
+    const bool defer_sums = M->side && Ua <= 4096;      // (wherever the batched reduction runs: the eager step and its two-stream capture)
     float* xp1 = M->at<float>(P.bott_part);
     float* xp2 = xp1 + (size_t)B * Le;
     float* pvp = xp2 + (size_t)B * Le;
@@ -1554,17 +1490,16 @@ int run_backward(SkfModel* M, hipStream_t s) {
                        M->at<float>(gs.dh), G2, Me, rate, site_enc(i, 1), s, hbits_of(M, a.hbits, Me), M->at<char>(a.img[1])));
     // last layer of the backward: nothing is left on the main stream to hide a whole layer's weight gradients behind
     // (only the embedding gradient follows), so they go out per sublayer - the step's tail before Adam is one wgrad, not four
-    static const bool early_tail = !skf_knob("SKF_NO_EARLY_TAIL");
     // (the fused launch's completion signal already served the held group as its "main stream is here" event: this group shares it)
-    if (i == 0 && early_tail) SKF_TRY(issue_wgrads(M, s, M->last_ready));
+    if (i == 0) SKF_TRY(issue_wgrads(M, s, M->last_ready));
     M->last_ready = nullptr;
     {
-      hipEvent_t parked = (i == 0 && early_tail) ? park_fresh(M) : nullptr;
+      hipEvent_t parked = i == 0 ? park_fresh(M) : nullptr;
       const int rc_ln = ln_oproj_bwd(M, w.ln1, w.mha.o, G2, M->at<float>(a.z1), M->at<float>(a.st1), M->at<float>(a.o), G, dy1, dO, Me, rate,
                                      site_enc(i, 0), s, M->at<char>(a.img_o));
       const hipEvent_t ready = take_ready(parked);
       SKF_TRY(rc_ln);
-      if (i == 0 && early_tail) SKF_TRY(issue_wgrads(M, s, ready));
+      if (i == 0) SKF_TRY(issue_wgrads(M, s, ready));
     }
     const float* qkv = M->at<float>(a.qkv);
     SKF_TRY(before_write(M, dqkv, s));
@@ -1578,19 +1513,16 @@ int run_backward(SkfModel* M, hipStream_t s) {
     // queued behind the held group of the layer above and finished ~20 us AFTER the main stream's last kernel
     // (profiles/r06h_timeline.txt: 34 us of idle main stream in front of the final reduction); with the 18-us q|k|v gradient in line
     // here both streams end together and the final reduction starts without waiting for a hop.
-    static const bool tail_main = !(skf_knob("SKF_TAIL_WGRAD_SIDE") && skf_knob("SKF_TAIL_WGRAD_SIDE")[0] == '1');   // (measurement builds only)
-    if (i == 0 && early_tail) SKF_TRY(issue_wgrads(M, s, nullptr, tail_main && M->wq_held.empty()));
+    if (i == 0) SKF_TRY(issue_wgrads(M, s, nullptr, M->wq_held.empty()));
     SKF_TRY(dense_dgrad(M, w.mha.qkv, dqkv, 3 * d, Me, G, d, 1, nullptr, 0, s));
-    static const bool hold_off_e = skf_knob("SKF_NO_WGRAD_HOLD") && skf_knob("SKF_NO_WGRAD_HOLD")[0] == '1';
-    if (M->ffn_fused && i > 0 && !hold_off_e) SKF_TRY(hold_wgrads(M, s));
+    if (M->ffn_fused && i > 0) SKF_TRY(hold_wgrads(M, s));
     else SKF_TRY(issue_wgrads(M, s));
     // half-way through the encoder: the slabs and LayerNorm partials finished so far are reduced on the side stream now, under the
     // remaining layers - the final reduction, which the optimizer waits for on the main stream, shrinks to the last layers' share
     // (with a held group: only what is already on the side stream - issuing the held group here would put it beside the next layer's
     //  fused feed-forward launch again)
-    static const bool mid_flush = !(skf_knob("SKF_MID_FLUSH") && skf_knob("SKF_MID_FLUSH")[0] == '0');
     // (not with the fused feed-forward blocks: the reduction launch lands beside a fused launch it cannot share CUs with - A/B 3.95 vs 3.99 ms)
-    if (mid_flush && !M->ffn_fused && M->side && N >= 2 && i == N / 2) SKF_TRY(flush_wgrads(M, s, -1, false, M->wq_held.empty()));
+    if (!M->ffn_fused && M->side && N >= 2 && i == N / 2) SKF_TRY(flush_wgrads(M, s, -1, false, M->wq_held.empty()));
   }
   if (c.continuous) {
     SKF_TRY(skf_embed_continuous_bwd(M->at<float>(P.inp), Le, B, Le, G, d, M->G(L.enc_embd.w), M->G(L.enc_embd.b), rate,
@@ -1739,8 +1671,7 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
   }
   // the captured step has constant arguments and no weight output: with weights requested, the steps are issued eagerly
   // (g_dec stays as it is)
-  static const bool use_graph_knob = !(skf_knob("SKF_DECODE_GRAPH") && skf_knob("SKF_DECODE_GRAPH")[0] == '0');
-  const bool use_graph = use_graph_knob && !attn;
+  const bool use_graph = !attn;
   if (fused) {
     for (int i = 0; i < max_steps; ++i) {
       SKF_TRY(skf_decode_fused_launch(fp, s));
@@ -1812,17 +1743,13 @@ int stage_inputs(SkfModel* M, const void* inp, const void* tar, int tar_ld, cons
   const size_t row = c.continuous ? (size_t)c.seq_len * 5 * sizeof(float) : (size_t)c.seq_len * 8;     // bytes per sample
   const size_t src_row = c.continuous ? (size_t)tar_ld * 5 * sizeof(float) : (size_t)tar_ld * 8;
   // one launch for the three copies (skf_rowops.hip); operands that are not 4-byte aligned take the copy engine below
-  static const bool stage_off = skf_knob("SKF_NO_STAGE_KERNEL") && skf_knob("SKF_NO_STAGE_KERNEL")[0] == '1';   // (measurement builds only)
-  if (!stage_off) {
-    // token mode: the two padding masks are written by the same launch (forward_preamble then skips its mask launches)
-    static const bool mask_off = skf_knob("SKF_NO_STAGED_MASKS") && skf_knob("SKF_NO_STAGED_MASKS")[0] == '1';   // (measurement builds only)
-    const bool masks = !c.continuous && !mask_off && tar_ld >= c.seq_len;
-    const int rc = skf_stage_inputs_launch(inp, M->at<char>(P.inp), tar, M->at<char>(P.tar), row, src_row, row < src_row ? row : src_row, c.batch,
-                                           labels, M->at<char>(P.labels), s, masks ? M->at<unsigned char>(P.enc_mask) : nullptr,
-                                           masks ? M->at<unsigned char>(P.dec_mask) : nullptr, masks ? c.seq_len : 0);
-    if (rc == SKF_OK) M->masks_staged = masks;
-    if (rc != SKF_EUNSUPPORTED) return rc;
-  }
+  // token mode: the two padding masks are written by the same launch (forward_preamble then skips its mask launches)
+  const bool masks = !c.continuous && tar_ld >= c.seq_len;
+  const int rc = skf_stage_inputs_launch(inp, M->at<char>(P.inp), tar, M->at<char>(P.tar), row, src_row, row < src_row ? row : src_row, c.batch,
+                                         labels, M->at<char>(P.labels), s, masks ? M->at<unsigned char>(P.enc_mask) : nullptr,
+                                         masks ? M->at<unsigned char>(P.dec_mask) : nullptr, masks ? c.seq_len : 0);
+  if (rc == SKF_OK) M->masks_staged = masks;
+  if (rc != SKF_EUNSUPPORTED) return rc;
   SKF_HIP(hipMemcpyAsync(M->at<char>(P.inp), inp, row * c.batch, hipMemcpyDeviceToDevice, s));
   if (tar_ld == c.seq_len) {
     SKF_HIP(hipMemcpyAsync(M->at<char>(P.tar), tar, row * c.batch, hipMemcpyDeviceToDevice, s));
@@ -2040,7 +1967,7 @@ extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
   // measured on MI355X: eager launches + a wgrad side stream beat hipGraph replay (graph nodes of different
   // streams do not overlap, 7.50 vs 7.72 ms/step), so the side stream is only used on the eager path
   // (round 5: use_graph = 2 captures the two-stream step - capture_or_run)
-  if (cfg->use_graph != 1 && !(skf_knob("SKF_NO_SIDE_STREAM") && skf_knob("SKF_NO_SIDE_STREAM")[0] == '1'))
+  if (cfg->use_graph != 1)
     SKF_HIP(hipStreamCreateWithFlags(&M->side, hipStreamNonBlocking));
   if (cfg->use_graph == 2 && M->side) {
     SKF_HIP(hipEventCreateWithFlags(&M->fork_event, hipEventDisableTiming));
@@ -2156,14 +2083,11 @@ int issue_embed_sorts(SkfModel* M, hipStream_t s) {
     ss = M->side;
     // first on the side stream: what the forward does not need before its first attention (forward_preamble) - the main stream goes
     // straight to the embedding and the first q|k|v projection (30 us of one-workgroup and short launches off the critical path)
-    static const bool pre_off = skf_knob("SKF_NO_SIDE_PREAMBLE") && skf_knob("SKF_NO_SIDE_PREAMBLE")[0] == '1';   // (measurement builds)
-    if (!pre_off) {
-      hipEvent_t masks = M->new_event(), ready = M->new_event();
-      SKF_CHECK_ARG(masks && ready, "event allocation failed");
-      SKF_TRY(forward_preamble(M, true, false, ss, masks));
-      SKF_HIP(hipEventRecord(ready, ss));
-      M->masks_ready = masks; M->pre_ready = ready;
-    }
+    hipEvent_t masks = M->new_event(), ready = M->new_event();
+    SKF_CHECK_ARG(masks && ready, "event allocation failed");
+    SKF_TRY(forward_preamble(M, true, false, ss, masks));
+    SKF_HIP(hipEventRecord(ready, ss));
+    M->masks_ready = masks; M->pre_ready = ready;
   }
   SKF_TRY(skf_embed_sort(M->at<long long>(P.inp), Le, B, Le, c.vocab_size, M->G(L.enc_emb), d, M->at<char>(P.emb_sort[0]),
                          P.emb_sort_bytes, ss));
@@ -2178,9 +2102,6 @@ extern "C" int skf_model_forward_backward(SkfModel* m, const void* inp, const vo
   SKF_CHECK_ARG(m && m->ws, "model not bound");
   SKF_CHECK_ARG(labels, "null labels");
   hipStream_t s = (hipStream_t)stream;
-#if SKF_MEASURE
-  g_evlog_main = s; ++g_evlog_step;
-#endif
   if (m->bf16) {
     SKF_TRY(stage_with_event(m, s, [&]() { return stage_inputs16(m, inp, tar, tar_ld, labels, s); }));
     return capture_or_run(m, &m->g_fb, s, [&]() -> int {

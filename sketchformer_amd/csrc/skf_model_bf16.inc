@@ -222,10 +222,9 @@ int d16_fwd(SkfModel* M, const DenseP& w, const void* x, int ldx, int rows, void
   const Img16& im = M->p16.img.at(w.w);
   return skf_gemm_bf16(rows, w.out, w.in, x, ldx, w16(M, im.wt), im.ldt, y, ldy, M->P(w.b), act, nullptr, 0, 0, nullptr, 0, s);
 }
-// sign-bit buffer of an ffn hidden tensor, or null (dff % 8 != 0, or SKF_NO_RELU_BITS=1)
+// sign-bit buffer of an ffn hidden tensor, or null (dff % 8 != 0)
 void* hbits16(SkfModel* M, size_t off) {
-  static const bool bits_off = skf_knob("SKF_NO_RELU_BITS") && skf_knob("SKF_NO_RELU_BITS")[0] == '1';
-  return (bits_off || (M->cfg.dff & 7)) ? nullptr : M->ws + off;
+  return (M->cfg.dff & 7) ? nullptr : M->ws + off;
 }
 // ffn dense1: relu forward that also leaves the sign bits of the hidden tensor
 int d16_fwd_relu_bits(SkfModel* M, const DenseP& w, const void* x, int ldx, int rows, void* y, int ldy, void* bits, hipStream_t s) {
@@ -293,9 +292,8 @@ int run_forward16(SkfModel* M, bool training, bool with_loss, hipStream_t s, boo
   SKF_TRY(skf_padding_mask(inp, Le, B, Le, emask, s));
   SKF_TRY(skf_padding_mask(tar, Le, B, Ld, dmask, s));
   // samples by length, longest first: the attention launches deal their workgroups over XCDs and shader engines from it
-  static const bool order_off = skf_knob("SKF_ATTN_ORDER") && skf_knob("SKF_ATTN_ORDER")[0] == '0';      // (measurement builds)
   M->order = nullptr;
-  if (!order_off && B <= 4096) {
+  if (B <= 4096) {
     SKF_TRY(skf_sample_order(emask, Le, Le, encoder_only ? nullptr : dmask, Ld, Ld, B, M->at<int>(P.order), s));
     M->order = M->at<int>(P.order);
   }
@@ -389,14 +387,11 @@ int run_backward16(SkfModel* M, hipStream_t s) {
   void* aws = W + P.attn_ws;
   M->p16.ln_cursor = 0;
   // ---------------- decoder side: every (B * Ld)-row gradient is zero behind a sample's last trained position (skf_row_blocks.hip)
-  static const bool rows_off = skf_knob("SKF_NO_ROW_BLOCKS") && skf_knob("SKF_NO_ROW_BLOCKS")[0] == '1';
-  if (!rows_off) {
-    int* ll = M->at<int>(P.live_len);
-    SKF_TRY(skf_target_live_len(M->at<long long>(P.tar), Le, B, Ld, ll, s));
-    SKF_TRY(skf_row_blocks_build(ll, B, Ld, 1, M->at<int>(P.live1), s));
-    SKF_TRY(skf_row_blocks_build(ll, B, Ld, 64, M->at<int>(P.live64), s));
-    M->live16 = M->at<int>(P.live1); M->live_rows = Md;        // (live16 only serves as the "lists are set" flag on this path)
-  }
+  int* ll = M->at<int>(P.live_len);
+  SKF_TRY(skf_target_live_len(M->at<long long>(P.tar), Le, B, Ld, ll, s));
+  SKF_TRY(skf_row_blocks_build(ll, B, Ld, 1, M->at<int>(P.live1), s));
+  SKF_TRY(skf_row_blocks_build(ll, B, Ld, 64, M->at<int>(P.live64), s));
+  M->live16 = M->at<int>(P.live1); M->live_rows = Md;        // (live16 only serves as the "lists are set" flag on this path)
   // ---------------- output layer (the logits buffer holds dlogits, pad columns zero)
   SKF_TRY(d16_wgrad(M, L.out, W + P.dec[N - 1].out3, d, W + P.logits, P.ld_logits, Md, s));
   SKF_TRY(d16_dgrad(M, L.out, W + P.logits, P.ld_logits, Md, G, d, 0, nullptr, 0, s));

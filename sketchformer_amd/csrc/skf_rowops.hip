@@ -1299,9 +1299,8 @@ extern "C" int skf_layernorm_residual_fwd(const float* x, float* y_inout_z, cons
   dim3 grid(grid_for_rows(rows)), block(256);
   hipStream_t s = (hipStream_t)stream;
   SkfProfScope ps(s, "ln_fwd", 0.0, 16.0 * rows * d);
-  static const bool v4 = !(skf_knob("SKF_LN_V4") && skf_knob("SKF_LN_V4")[0] == '0');
   const bool al = ((((uintptr_t)x | (uintptr_t)y_inout_z | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0);
-  if (v4 && al && (d == 64 || d == 128 || d == 256)) {
+  if (al && (d == 64 || d == 128 || d == 256)) {
     const int rpi = (64 / (d / 4)) * SKF_LN_UR * 4;               // rows per workgroup iteration
     int g = skf_cdiv(rows, rpi); if (g > kMaxGrid) g = kMaxGrid;
     if (d == 64) hipLaunchKernelGGL(ln_fwd_v4_kernel<16>, dim3(g), block, 0, s, x, y_inout_z, gamma, beta, out, stats, rows, rate, site, st);
@@ -1350,13 +1349,12 @@ extern "C" int skf_layernorm_residual_bwd_rows(const float* dout, const float* z
   float* part = (float*)workspace;
   float* dyp = (dy && (rate > 0.f || dy != dz)) ? dy : nullptr;   // rate 0 with a separate dy buffer: dy = dz
   SkfProfScope ps(s, "ln_bwd", 0.0, (rate > 0.f ? 16.0 : 12.0) * rows * d);
-  static const bool v4 = !(skf_knob("SKF_LN_V4") && skf_knob("SKF_LN_V4")[0] == '0');
   const bool al = ((((uintptr_t)dout | (uintptr_t)z | (uintptr_t)dz | (uintptr_t)dyp | (uintptr_t)gamma) & 15) == 0) &&
                   (double)rows * d * 4 < 2147483648.0;             // (the v4 kernel stores through 32-bit buffer offsets)
   const dim3 block4(SKF_LN_BWD_THREADS);
-  if (v4 && al && d == 64) hipLaunchKernelGGL(ln_bwd_v4_kernel<16>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
-  else if (v4 && al && d == 128) hipLaunchKernelGGL(ln_bwd_v4_kernel<32>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
-  else if (v4 && al && d == 256) hipLaunchKernelGGL(ln_bwd_v4_kernel<64>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
+  if (al && d == 64) hipLaunchKernelGGL(ln_bwd_v4_kernel<16>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
+  else if (al && d == 128) hipLaunchKernelGGL(ln_bwd_v4_kernel<32>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
+  else if (al && d == 256) hipLaunchKernelGGL(ln_bwd_v4_kernel<64>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
   else
   switch (d) {
     case 128: hipLaunchKernelGGL(ln_bwd_kernel<2>, grid, block, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st); break;

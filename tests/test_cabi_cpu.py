@@ -130,6 +130,32 @@ def test_shipped_library_reads_no_environment():
     assert not re.search(r"\bU (secure_)?getenv\b", syms), "libskf.so imports getenv"
 
 
+_RETIRED_KNOBS = (
+    "SKF_EVLOG", "SKF_TWO_GRAD_SETS", "SKF_NO_EMBED_SORT", "SKF_NO_WAIT_DEDUPE", "SKF_EVENT_SCOPE", "SKF_NO_LN_FUSE",
+    "SKF_NO_RELU_BITS", "SKF_NO_STOP_EVENTS", "SKF_TAIL_REDUCE_SIDE", "SKF_NO_DEFERRED_DGRAD", "SKF_NO_FFN_FUSE",
+    "SKF_NO_FFN_CHAIN", "SKF_NO_FFN_PRE", "SKF_ATTN_ORDER", "SKF_KV_WAIT_ALL", "SKF_NO_TAIL_PROJ", "SKF_NO_FFN_LN_BWD",
+    "SKF_NO_LN_DGRAD", "SKF_NO_LN_LEAD", "SKF_NO_ROW_BLOCKS", "SKF_NO_WGRAD_HOLD", "SKF_NO_BOTT_PARTIALS", "SKF_NO_EARLY_TAIL",
+    "SKF_TAIL_WGRAD_SIDE", "SKF_MID_FLUSH", "SKF_DECODE_GRAPH", "SKF_NO_STAGE_KERNEL", "SKF_NO_STAGED_MASKS",
+    "SKF_NO_SIDE_STREAM", "SKF_NO_SIDE_PREAMBLE",
+    "SKF_GEMM_NO_SMALL", "SKF_GEMM_NO_WGRAD", "SKF_NO_WGRAD_GROUP", "SKF_GEMM_NO_WS", "SKF_NO_MASKED_CHAIN", "SKF_LN_V4",
+)
+
+
+def test_train_step_schedule_has_no_knobs():
+    """The train step's stream / event schedule and the Dense / LayerNorm routing are fixed: the A/B knobs that once switched
+    them (even in measurement builds) are gone, the step's orchestrator reads no knob at all, and the integration guide and the
+    knob table of tools/ do not name the retired ones."""
+    import glob
+    csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
+    for name in ("skf_model.hip", "skf_model_bf16.inc"):
+        assert "skf_knob(" not in open(os.path.join(csrc, name)).read(), name
+    pattern = re.compile(r"\b(%s)\b" % "|".join(_RETIRED_KNOBS))
+    docs = [os.path.join(ROOT, "INTEGRATION.md"), os.path.join(ROOT, "tools", "README.md")]
+    for path in glob.glob(os.path.join(csrc, "*")) + docs:
+        m = pattern.search(open(path, encoding="utf-8").read())
+        assert m is None, "%s names the retired knob %s" % (path, m.group(1))
+
+
 def test_gemm_wsx_isa_has_no_crossed_select_packed_fp32():
     """Round 4 bisected the run-to-run wrong results of round 3's 'accumulate only' epilogue kind to a compiler-formed
     v_pk_add_f32 with crossed operand selects in gemm_wsx_kernel's exit block (skf_gemm_wsx.hip: launch_wsx).  The kind is gone; this
