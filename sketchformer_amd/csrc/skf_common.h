@@ -79,14 +79,43 @@ static inline int skf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // An event that means "everything this stream was given so far is complete" costs the stream ~5 us as a packet of its own
 // (hipEventRecord) and ~1.3 us attached to the kernel launch in front of it as that command's completion signal (hipExtLaunchKernelGGL's
 // stop event; tools/micro/event_cost.hip, profiles/r06c_event_cost.txt: 25.4 vs 21.7 us per iteration against 20.4 without any event).
-// A caller that is about to record such an event behind a launcher's LAST kernel parks it in skf_tls_stop_event first; a launcher built
-// with SKF_LAUNCH_TAIL attaches it and clears the slot (a launcher that is not leaves it: the caller then records the event as before).
-extern thread_local hipEvent_t skf_tls_stop_event;
+//
+// The attach protocol, all of it:
+//  - PARK.  A caller that wants event E behind the LAST launch of the calls it is about to make opens an SkfTailScope(E) around them
+//    and asks scope.attached() afterwards: true = E is that launch's completion signal, false = nothing carries E and the caller
+//    records it (hipEventRecord) as before.  The scope restores what the slot held before on every way out, so an early return or an
+//    error can neither leak E into a later launch nor lose an outer scope's event.  SkfTailScope(nullptr) only shields the calls
+//    inside it: launches on ANOTHER stream (the side stream's weight gradients) must never pick up an event parked for this one.
+//  - ATTACH.  Only SKF_LAUNCH_TAIL attaches, and it says so (slot.attached); nobody infers it from an empty slot.  A launch site may
+//    use SKF_LAUNCH_TAIL only where it is the last launch of every entry point that reaches it with an event parked (each site
+//    carries a comment that names its parkers); a site that is not simply launches with hipLaunchKernelGGL and the event is recorded.
+//  - CHAIN.  A launcher that issues several SKF_LAUNCH_TAIL launches takes the event out at entry (skf_tail_defer) and puts it back
+//    in front of its final launch (skf_tail_resume).  A chain that fails midway never puts it back: the event stays un-attached.
+// Nothing is parked while a step is captured into a hipGraph (the orchestrator's with_tail_event checks); the slot is per host thread.
+struct SkfTailSlot {
+  hipEvent_t event = nullptr;      // parked for this thread's next SKF_LAUNCH_TAIL launch
+  bool attached = false;           // that launch has taken it
+};
+extern thread_local SkfTailSlot skf_tls_tail;      // (defined in skf_model.hip; named in this header only)
+struct SkfTailScope {
+  explicit SkfTailScope(hipEvent_t e) : saved_(skf_tls_tail) { skf_tls_tail = SkfTailSlot{e, false}; }
+  ~SkfTailScope() { skf_tls_tail = saved_; }
+  SkfTailScope(const SkfTailScope&) = delete;
+  SkfTailScope& operator=(const SkfTailScope&) = delete;
+  bool attached() const { return skf_tls_tail.attached; }
+ private:
+  SkfTailSlot saved_;
+};
+inline hipEvent_t skf_tail_defer() { hipEvent_t e = skf_tls_tail.event; skf_tls_tail.event = nullptr; return e; }
+inline void skf_tail_resume(hipEvent_t e) { skf_tls_tail.event = e; }
+inline hipEvent_t skf_tail_attach() {      // SKF_LAUNCH_TAIL only
+  hipEvent_t e = skf_tls_tail.event;
+  if (e) skf_tls_tail = SkfTailSlot{nullptr, true};
+  return e;
+}
 #define SKF_LAUNCH_TAIL(kernel, grid, block, smem, stream, ...)                                        \
   do {                                                                                                 \
-    hipEvent_t ev__ = skf_tls_stop_event;                                                              \
-    if (ev__) {                                                                                        \
-      skf_tls_stop_event = nullptr;                                                                    \
+    if (hipEvent_t ev__ = skf_tail_attach()) {                                                         \
       hipExtLaunchKernelGGL(kernel, grid, block, smem, stream, nullptr, ev__, 0, __VA_ARGS__);         \
     } else {                                                                                           \
       hipLaunchKernelGGL(kernel, grid, block, smem, stream, __VA_ARGS__);                              \

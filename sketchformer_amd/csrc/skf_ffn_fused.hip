@@ -963,6 +963,7 @@ int launch_ffn(const FfnFusedParams& p, hipStream_t st) {
   const double bytes = 4.0 * ((double)p.M * FD * (MODE == 0 ? 4 : 3) + (double)p.M * FF + (POST ? (double)p.M * p.n2 : 0.0) + (PRE ? 4.0 * p.M * FD : 0.0)) + 2.0 * image_bytes(P) / 2;
   SkfProfScope ps(st, tag.c_str(), flops, bytes);
   ps.done(flops * live, bytes * live);
+  // tail audit: parked by ffn_bwd / ffn_ln_bwd (skf_model.hip) around skf_ffn_fused_bwd[_ln]_f32; every entry point of this file is ONE launch
   SKF_LAUNCH_TAIL((ffn_fused_kernel<P, MODE, LNB, POST, PRE>), dim3(grid), dim3(512), smem, st, p);
   SKF_LAUNCH_CHECK();
   return SKF_OK;
@@ -1159,6 +1160,7 @@ extern "C" int skf_layernorm_bwd_dgrad_lead_f32(int M, int d, const float* dout,
   const double nprod = lead ? 2.0 : 1.0, nrows = lead ? 6.0 : 5.0;
   SkfProfScope ps(st, (P == 2 ? tag2 : tag3).c_str(), nprod * 2.0 * M * FD * FD, 4.0 * nrows * M * FD);
   ps.done(nprod * 2.0 * M * FD * FD * live, 4.0 * nrows * M * FD * live);
+  // tail audit: parked by run_backward around ln_oproj_bwd (first encoder layer), whose fused branch makes this ONE launch and then only queues
 #define SKF_LN_DGRAD_GO(PV, LV)                                                                                                                  \
   {                                                                                                                                              \
     SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_bwd_dgrad_kernel<PV, LV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \

@@ -609,6 +609,9 @@ int launch_wsx(const GemmParams& p, int b_kc, hipStream_t st) {
   // different XCDs, i.e. every A tile is fetched into `groups` L2s (PMC, round 1: 1.55x the algorithmic bytes)
   static const char* xcd_env = skf_knob("SKF_WS_XCD");     // "0" / "1" force it (measurement)
   q.xcd_remap = xcd_env ? xcd_env[0] == '1' : (groups > 1 && (K >= 384 || groups >= 3));
+  // tail audit (all four sites of launch_wsx): parked by run_backward around dense_dgrad / ln_oproj_bwd, whose last call is one skf_gemm_f32*.
+  // launch_wsx is ONE launch and the last thing its entry points do (skf_gemm_ws_dispatch: single launch, or a chain that defers the event to its
+  // last slice; skf_gemm_ln_residual_f32: single launch, nobody parks)
 #define SKF_WSX_LAUNCH(BKC, EX)                                                                                    \
   do {                                                                                                             \
     static SkfOncePerDevice attr_done;                                                                             \
@@ -628,6 +631,7 @@ int launch_wsx(const GemmParams& p, int b_kc, hipStream_t st) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wsx_kernel<K, NB, P, false, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_ln) == hipSuccess)
           attr_ln.mark();
       }
+      // tail audit: skf_gemm_ln_residual_f32 only (forward), nobody parks; one launch
       SKF_LAUNCH_TAIL((gemm_wsx_kernel<K, NB, P, false, 0, false, true>), grid, block, smem_ln, st, q, groups, workers);
       SKF_LAUNCH_CHECK();
       return SKF_OK;
@@ -641,6 +645,7 @@ int launch_wsx(const GemmParams& p, int b_kc, hipStream_t st) {
                                     : hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wsx_kernel<K, NB, P, true, 0, true, false, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (ea == hipSuccess) attr_m[extra ? 1 : 0].mark();
       }
+      // tail audit (both): the masked slice is the LAST of skf_gemm_ws_dispatch's chain (output-layer dgrad, parked by run_backward), event resumed for it
       if (extra) SKF_LAUNCH_TAIL((gemm_wsx_kernel<K, NB, P, true, 3, true, false, KS>), grid, block, smem, st, q, groups, workers);
       else SKF_LAUNCH_TAIL((gemm_wsx_kernel<K, NB, P, true, 0, true, false, KS>), grid, block, smem, st, q, groups, workers);
       SKF_LAUNCH_CHECK();

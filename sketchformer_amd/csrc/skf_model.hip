@@ -15,7 +15,7 @@
 
 // ------------------------------------------------------------------ error plumbing
 static thread_local char g_err[512] = "";
-thread_local hipEvent_t skf_tls_stop_event = nullptr;      // skf_common.h: an event for the next SKF_LAUNCH_TAIL launch of this thread
+thread_local SkfTailSlot skf_tls_tail;      // skf_common.h: the event parked for this thread's next SKF_LAUNCH_TAIL launch
 void skf_set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -585,21 +585,27 @@ int dense_wgrad_on(SkfModel* M, const DenseP& w, const float* x, int ldx, const 
 }
 int issue_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded = nullptr, bool on_main = false);
 int issue_held_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded = nullptr);
-// The "main stream has reached this point" event of a held weight-gradient group as the COMPLETION SIGNAL of the launch in front of it
-// (skf_common.h: SKF_LAUNCH_TAIL) instead of a packet of its own: park_ready() before the launcher, take_ready() behind it - the
-// event when the launcher attached it, null when it did not (or nothing is held / the step is being captured).
-// park_fresh(): the same for a group that is issued right behind ONE call's last launch (no held group needed).
-hipEvent_t park_fresh(SkfModel* M) {
-  if (!M->side || g_capturing) return nullptr;
-  hipEvent_t e = M->new_event();
-  skf_tls_stop_event = e;
-  return e;
+// Run `call` with event `e` riding on its LAST launch as that launch's completion signal instead of a packet of its own (skf_common.h:
+// the attach protocol).  *rode = the launch carries it; false = the caller records `e` where it needs it.  Nothing is parked for a null
+// `e`, while the step is being captured, or - the events that hand work to the side stream - without a side stream (`needs_side`).
+inline bool may_park(const SkfModel* M, bool needs_side = true) { return !g_capturing && (M->side || !needs_side); }
+template <typename F>
+int with_tail_event(SkfModel* M, hipEvent_t e, bool* rode, F call, bool needs_side = true) {
+  SkfTailScope scope(may_park(M, needs_side) ? e : nullptr);
+  const int rc = call();
+  *rode = scope.attached();
+  return rc;
 }
-hipEvent_t park_ready(SkfModel* M) { return M->wq_held.empty() ? nullptr : park_fresh(M); }
-hipEvent_t take_ready(hipEvent_t parked) {
-  const bool attached = parked && skf_tls_stop_event == nullptr;
-  skf_tls_stop_event = nullptr;
-  return attached ? parked : nullptr;
+// The same with a fresh event of the step's pool, for the "main stream has reached this point" event of the weight-gradient group that
+// is issued right behind `call`: *ready = the event when it rode, null when it did not (or was not wanted) - the group then records
+// one of its own (issue_wgrads).
+template <typename F>
+int with_ready_event(SkfModel* M, bool want, hipEvent_t* ready, F call) {
+  hipEvent_t e = (want && may_park(M)) ? M->new_event() : nullptr;
+  bool rode = false;
+  const int rc = with_tail_event(M, e, &rode, call);
+  *ready = rode ? e : nullptr;
+  return rc;
 }
 // The main stream waits for the side-stream event `pending` holds for `buf` (unless it already waited for a later one); a queued or
 // held group that `touches` the buffer is issued first.
@@ -634,12 +640,6 @@ int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const flo
   M->wq.push_back(q);
   return SKF_OK;
 }
-// side-stream launches must never pick up an event that is parked for the main stream's next launch
-struct ParkedEventGuard {
-  hipEvent_t saved;
-  ParkedEventGuard() : saved(skf_tls_stop_event) { skf_tls_stop_event = nullptr; }
-  ~ParkedEventGuard() { skf_tls_stop_event = saved; }
-};
 // Issue the queued wgrads on the side stream: ONE ready event (everything queued on `s` so far is complete before they
 // start) and ONE done event for the whole group; they are serialized among themselves and joined before the optimizer.
 // The fused feed-forward backward is the FIRST kernel of a layer's backward, and its workgroups (147 KB of LDS, two waves per SIMD)
@@ -664,7 +664,7 @@ int hold_wgrads(SkfModel* M, hipStream_t s) {
 // on_main: the queued group runs on the MAIN stream, in place (no events, no hop) - for the one weight gradient at the very end of
 // the backward that the side stream would finish last (see run_backward)
 int issue_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool on_main) {
-  ParkedEventGuard guard;                                      // (this function may run INSIDE a parked call: before_write)
+  SkfTailScope shield(nullptr);      // this function may run INSIDE a parked call (before_write): its side-stream launches must not take that event
   SKF_TRY(issue_held_wgrads(M, s));                            // the held group first, as a group of its own
   if (M->wq.empty()) return SKF_OK;
   std::vector<SkfModel::QueuedWgrad> group;
@@ -766,12 +766,9 @@ int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_
       SKF_HIP(hipEventRecord(e, M->side));
       SKF_HIP(hipStreamWaitEvent(s, e, 0));
       // the bucket-ready event rides on the reduction launch as its completion signal (skf_common.h: SKF_LAUNCH_TAIL)
-      hipEvent_t br = (bucket >= 0 && !g_capturing) ? M->bucket_ready[bucket] : nullptr;
-      skf_tls_stop_event = br;
-      const int rc = skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->reduce_blocks, s);
-      bucket_recorded = br && skf_tls_stop_event == nullptr;
-      skf_tls_stop_event = nullptr;
-      SKF_TRY(rc);
+      SKF_TRY(with_tail_event(M, bucket >= 0 ? M->bucket_ready[bucket] : nullptr, &bucket_recorded, [&] {
+        return skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->reduce_blocks, s);
+      }));
     } else {
       hipEvent_t em = main_here ? main_here : M->new_event();      // (main_here: already the completion signal of the main stream's last launch)
       SKF_CHECK_ARG(em, "event allocation failed");
@@ -1031,11 +1028,8 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
     SKF_CHECK_ARG(dec_in_ready, "event allocation failed");
   }
   if (recon && bott) {
-    if (dec_in_ready && !g_capturing) skf_tls_stop_event = dec_in_ready;
-    const int rc_ex = skf_expander_fwd(M->at<float>(P.emb), M->P(L.exp_w), M->P(L.exp_b), B, Le, E, pre, s);
-    dec_in_recorded = dec_in_ready && !g_capturing && skf_tls_stop_event == nullptr;
-    skf_tls_stop_event = nullptr;
-    SKF_TRY(rc_ex);
+    SKF_TRY(with_tail_event(M, dec_in_ready, &dec_in_recorded,
+                            [&] { return skf_expander_fwd(M->at<float>(P.emb), M->P(L.exp_w), M->P(L.exp_b), B, Le, E, pre, s); }));
   }
 
   // ---------------- decoder (builders/layers/transformer.py:325-344)
@@ -1144,11 +1138,11 @@ int ffn_bwd(SkfModel* M, const DenseP& f1, const DenseP& f2, const float* x_in, 
     SKF_TRY(before_write(M, dh, s));
     SKF_TRY(before_write(M, dx_acc, s));
     const int* blocks = (M->live16 && rows == M->live_rows) ? M->live16 : nullptr;
-    hipEvent_t parked = park_ready(M);
-    const int rc = skf_ffn_fused_bwd_f32(rows, M->cfg.d_model, M->cfg.dff, dy, image_t, hbits, dh, dx_acc, 1, blocks, blocks ? 16 : 0,
-                                         M->cfg.gemm_precision, s);
-    const hipEvent_t ready = take_ready(parked);
-    SKF_TRY(rc);
+    hipEvent_t ready = nullptr;      // the held group's "main stream is here" event rides on this launch
+    SKF_TRY(with_ready_event(M, !M->wq_held.empty(), &ready, [&] {
+      return skf_ffn_fused_bwd_f32(rows, M->cfg.d_model, M->cfg.dff, dy, image_t, hbits, dh, dx_acc, 1, blocks, blocks ? 16 : 0,
+                                   M->cfg.gemm_precision, s);
+    }));
     SKF_TRY(issue_held_wgrads(M, s, ready));
     return dense_wgrad(M, f1, x_in, f1.in, dh, f1.out, rows, s);
   }
@@ -1236,11 +1230,11 @@ int ffn_ln_bwd(SkfModel* M, const LnP& ln, const DenseP& f1, const DenseP& f2, c
   SKF_TRY(before_write(M, dh, s));
   SKF_TRY(before_write(M, dx, s));
   const int* blocks = (M->live16 && rows == M->live_rows) ? M->live16 : nullptr;
-  hipEvent_t parked = park_ready(M);
-  const int rc = skf_ffn_fused_bwd_ln_f32(rows, d, M->cfg.dff, dout, z, st, M->P(ln.g), rate, site, M->state, image_t, hbits, dy, dh, dx, part,
-                                          pbytes, blocks, blocks ? 16 : 0, M->cfg.gemm_precision, s);
-  const hipEvent_t ready = take_ready(parked);
-  SKF_TRY(rc);
+  hipEvent_t ready = nullptr;      // the held group's "main stream is here" event rides on this launch
+  SKF_TRY(with_ready_event(M, !M->wq_held.empty(), &ready, [&] {
+    return skf_ffn_fused_bwd_ln_f32(rows, d, M->cfg.dff, dout, z, st, M->P(ln.g), rate, site, M->state, image_t, hbits, dy, dh, dx, part,
+                                    pbytes, blocks, blocks ? 16 : 0, M->cfg.gemm_precision, s);
+  }));
   SKF_TRY(ln_partials_desc(M, ln, part, skf_ffn_fused_ln_partials(rows)));
   M->last_ready = ready;                        // (nothing else reaches the main stream before this function returns: the caller may reuse it)
   SKF_TRY(issue_held_wgrads(M, s, ready));      // the previous layer's weight gradients: behind this launch (see hold_wgrads)
@@ -1336,10 +1330,8 @@ int run_backward(SkfModel* M, hipStream_t s) {
   const float* dlog = M->at<float>(P.logits);
   SKF_TRY(dense_wgrad(M, L.out, M->at<float>(P.dec[N - 1].out3), d, dlog, L.out.out, Md, s));
   {
-    hipEvent_t parked = park_fresh(M);       // the group's "main stream is here" event rides on the input-gradient launch (the last of its chain)
-    const int rc = dense_dgrad(M, L.out, dlog, L.out.out, Md, G, d, 0, nullptr, 0, s);
-    const hipEvent_t ready = take_ready(parked);
-    SKF_TRY(rc);
+    hipEvent_t ready = nullptr;      // the group's "main stream is here" event rides on the input-gradient launch (the last of its chain)
+    SKF_TRY(with_ready_event(M, true, &ready, [&] { return dense_dgrad(M, L.out, dlog, L.out.out, Md, G, d, 0, nullptr, 0, s); }));
     SKF_TRY(issue_wgrads(M, s, ready));
   }
   const unsigned char* cross_mask = c.blind_decoder_mask ? nullptr : emask;
@@ -1383,10 +1375,8 @@ int run_backward(SkfModel* M, hipStream_t s) {
     SKF_TRY(dense_wgrad(M, w.mha1.qkv, M->at<float>(a.x_in), d, dqkv, 3 * d, Md, s));
     // the 8 weight gradients of this layer: one event pair - held until the next layer's fused feed-forward launch is queued
     const bool hold = M->ffn_fused && i > 0;
-    hipEvent_t parked = hold ? nullptr : park_fresh(M);         // not held: the group's event rides on this layer's last launch
-    const int rc_dg = dense_dgrad(M, w.mha1.qkv, dqkv, 3 * d, Md, G2, d, 1, nullptr, 0, s);
-    const hipEvent_t ready = take_ready(parked);
-    SKF_TRY(rc_dg);
+    hipEvent_t ready = nullptr;      // not held: the group's event rides on this layer's last launch
+    SKF_TRY(with_ready_event(M, !hold, &ready, [&] { return dense_dgrad(M, w.mha1.qkv, dqkv, 3 * d, Md, G2, d, 1, nullptr, 0, s); }));
     float* t = G; G = G2; G2 = t;
     if (hold) SKF_TRY(hold_wgrads(M, s));
     else SKF_TRY(issue_wgrads(M, s, ready));
@@ -1399,11 +1389,10 @@ int run_backward(SkfModel* M, hipStream_t s) {
                                      site_dec_embed(N), M->state, M->at<char>(P.small_ws), P.small_ws_bytes, s));
   } else {
     if (P.emb_sort_bytes) {
-      hipEvent_t parked = M->n_buckets == 2 ? park_fresh(M) : nullptr;      // the bucket's reduction (side stream) waits for this launch's own signal
-      const int rc_e = skf_embed_bwd_sorted(M->at<char>(P.emb_sort[1]), B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N),
-                                            M->state, s);
-      dec_emb_done = take_ready(parked);
-      SKF_TRY(rc_e);
+      // the bucket's reduction (side stream) waits for this launch's own signal
+      SKF_TRY(with_ready_event(M, M->n_buckets == 2, &dec_emb_done, [&] {
+        return skf_embed_bwd_sorted(M->at<char>(P.emb_sort[1]), B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N), M->state, s);
+      }));
     } else {
       SKF_HIP(hipMemsetAsync(M->G(L.dec_emb), 0, (size_t)c.vocab_size * d * sizeof(float), s));
       SKF_TRY(skf_embed_bwd(tar, Le, B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N), M->state, s));
@@ -1470,10 +1459,7 @@ int run_backward(SkfModel* M, hipStream_t s) {
     SKF_TRY(skf_pool_bwd(M->at<float>(P.u), M->P(L.bott_v), enc_out, M->at<float>(P.pool_a), dpool, B, Le, Ua, d,
                          G, M->G(L.bott_v), M->at<char>(P.small_ws), P.small_ws_bytes, s));
     SKF_TRY(dense_wgrad(M, L.bott_w, enc_out, d, M->at<float>(P.u), Ua, Me, s));
-    hipEvent_t parked = park_fresh(M);
-    const int rc_dg = dense_dgrad(M, L.bott_w, M->at<float>(P.u), Ua, Me, G, d, 1, nullptr, 0, s);
-    bott_ready = take_ready(parked);
-    SKF_TRY(rc_dg);
+    SKF_TRY(with_ready_event(M, true, &bott_ready, [&] { return dense_dgrad(M, L.bott_w, M->at<float>(P.u), Ua, Me, G, d, 1, nullptr, 0, s); }));
   } else {
     // no bottleneck: d(enc_output) is what the cross-attention K/V projections of all decoder layers sent back
     float* spare = (G == M->at<float>(P.gA)) ? M->at<float>(P.gB) : M->at<float>(P.gA);
@@ -1494,11 +1480,11 @@ int run_backward(SkfModel* M, hipStream_t s) {
     if (i == 0) SKF_TRY(issue_wgrads(M, s, M->last_ready));
     M->last_ready = nullptr;
     {
-      hipEvent_t parked = i == 0 ? park_fresh(M) : nullptr;
-      const int rc_ln = ln_oproj_bwd(M, w.ln1, w.mha.o, G2, M->at<float>(a.z1), M->at<float>(a.st1), M->at<float>(a.o), G, dy1, dO, Me, rate,
-                                     site_enc(i, 0), s, M->at<char>(a.img_o));
-      const hipEvent_t ready = take_ready(parked);
-      SKF_TRY(rc_ln);
+      hipEvent_t ready = nullptr;
+      SKF_TRY(with_ready_event(M, i == 0, &ready, [&] {
+        return ln_oproj_bwd(M, w.ln1, w.mha.o, G2, M->at<float>(a.z1), M->at<float>(a.st1), M->at<float>(a.o), G, dy1, dO, Me, rate,
+                            site_enc(i, 0), s, M->at<char>(a.img_o));
+      }));
       if (i == 0) SKF_TRY(issue_wgrads(M, s, ready));
     }
     const float* qkv = M->at<float>(a.qkv);
@@ -1769,11 +1755,10 @@ int stage_inputs(SkfModel* M, const void* inp, const void* tar, int tar_ld, cons
 template <typename F>
 int stage_with_event(SkfModel* M, hipStream_t s, F stage) {
   if (!M->inputs_staged) SKF_HIP(hipEventCreateWithFlags(&M->inputs_staged, hipEventDisableTiming));
-  skf_tls_stop_event = M->inputs_staged;
-  const int rc = stage();
-  const bool attached = skf_tls_stop_event == nullptr;
-  skf_tls_stop_event = nullptr;
-  SKF_TRY(rc);
+  // (runs in front of capture_or_run, never inside the library's own capture.  A caller whose stream is under a capture of ITS OWN
+  //  would be detected here - hipStreamIsCapturing(s), then no parking - at the price of one more HIP call per step: not done)
+  bool attached = false;
+  SKF_TRY(with_tail_event(M, M->inputs_staged, &attached, stage, /*needs_side=*/false));
   if (!attached) SKF_HIP(hipEventRecord(M->inputs_staged, s));
   M->inputs_staged_valid = true;
   return SKF_OK;

@@ -1196,6 +1196,7 @@ int skf_stage_inputs_launch(const void* inp, void* dinp, const void* tar, void* 
   if (mask_L > 0 && (!emask || !dmask || (size_t)mask_L * 8 > row || (size_t)(mask_L - 1) * 8 > src_row)) mask_L = 0;
   const int total = (int)((row + copy) / 4) * batch + 2 * batch + (mask_L > 0 ? (2 * mask_L - 1) * batch : 0);
   int grid = skf_cdiv(total, 256); if (grid > 512) grid = 512;
+  // tail audit: parked by stage_with_event (skf_model.hip) around stage_inputs / stage_inputs16, which launch nothing behind a successful return
   SKF_LAUNCH_TAIL(stage_inputs_kernel, dim3(grid), dim3(256), 0, st, (const unsigned*)inp, (unsigned*)dinp, (const unsigned*)tar,
                      (unsigned*)dtar, (int)(row / 4), (int)(src_row / 4), (int)(copy / 4), batch, (const unsigned*)labels, (unsigned*)dlabels,
                      emask, dmask, mask_L);
@@ -1272,6 +1273,7 @@ static int embed_bwd_sorted_launch(const void* ws, int B, int L, const void* dx,
   const int* order = w.order;
   SkfProfScope ps((hipStream_t)stream, dx_bf16 ? "embed_bwd_sorted_bf16" : "embed_bwd_sorted", 0.0,
                   (dx_bf16 ? 2.0 : 4.0) * rows * d + 4.0 * (double)vocab * d);
+  // tail audit (both): parked by run_backward around skf_embed_bwd_sorted (two buckets); the bf16 entry point has no parker; one launch each
   if (dx_bf16)
     SKF_LAUNCH_TAIL(embed_bwd_sorted_kernel<skf_bf16>, dim3((unsigned)maxc), dim3(256), (size_t)3 * d * sizeof(float), (hipStream_t)stream,
                        hdr, chunks, order, (const skf_bf16*)dx, d, dtable, rate, site, (const SkfStepState*)step_state, w.partial, w.done);
@@ -1463,6 +1465,7 @@ extern "C" int skf_expander_fwd(const float* emb, const float* w, const float* b
   const size_t total = (size_t)B * L * d;
   int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
   SkfProfScope ps((hipStream_t)stream, "expander_fwd", 0.0, 4.0 * total);
+  // tail audit: parked by run_forward (decoder-input event); the only launch of this entry point
   SKF_LAUNCH_TAIL(expander_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, emb, w, bias, B, L, d, pre);
   SKF_LAUNCH_CHECK();
   return SKF_OK;

@@ -156,6 +156,8 @@ class TrainEngine:
         self.stream = torch.cuda.Stream(device=dev)
         self._depth = 0
         self._dirty = False
+        # A/B knob of the Python layer, read once: "1" = a train step clones the caller's device inputs like round 5 (see _stage)
+        self._step_clones = os.environ.get("SKF_CLONE_INPUTS") == "1"
         self._comm = None                # communication stream of the data-parallel gradient buckets
         self.pg = process_group
         self.world_size = torch.distributed.get_world_size(process_group) if process_group is not None else 1
@@ -239,8 +241,8 @@ class TrainEngine:
             self.set(k, v, which)
 
     # ---- steps
-    def _dev_tokens(self, x, limit=None, what="token id"):
-        """int64 device copy.  Host inputs (the loader's numpy batches) are range-checked against ``limit`` here - a
+    def _dev_tokens(self, x, clone, limit=None, what="token id"):
+        """int64 device copy (``clone``: see _own).  Host inputs (the loader's numpy batches) are range-checked against ``limit`` here - a
         tokenizer / vocab_size (or class count) mismatch must fail loudly instead of training on wrong rows; tensors
         that already live on the device are trusted (checking them would cost a host sync per step)."""
         t = torch.as_tensor(x)
@@ -251,28 +253,27 @@ class TrainEngine:
                                  "does not match the model (vocab_size / n_classes)" % (what, lo, hi, limit))
         if t.dtype != torch.int64:
             t = t.to(torch.int64)
-        return self._own(t, t.to(self.device, non_blocking=True).contiguous())
+        return self._own(t, t.to(self.device, non_blocking=True).contiguous(), clone)
 
-    _clone_inputs = True
-
-    def _own(self, given, staged):
+    def _own(self, given, staged, clone):
         """The step reads its inputs asynchronously on the engine's stream and no longer makes the caller's stream wait for it
         (_publish): a device tensor the caller passes in - and may refill IN PLACE for the next batch - is therefore copied here,
         on the caller's stream (the hand-over of _enter orders the step behind the copy).  Host inputs already became fresh device
-        copies.  ~2 us of copy kernels on the caller's stream, nothing on the engine's."""
-        if self._clone_inputs and torch.is_tensor(given) and given.is_cuda and staged.data_ptr() == given.data_ptr():
+        copies.  ~2 us of copy kernels on the caller's stream, nothing on the engine's.  ``clone=False`` is for _stage alone: there the
+        caller's stream waits for the library's staging copy instead."""
+        if clone and torch.is_tensor(given) and given.is_cuda and staged.data_ptr() == given.data_ptr():
             return staged.clone()
         return staged
 
-    def _dev_input(self, x):
+    def _dev_input(self, x, clone):
         """(B,L) int64 tokens, or (B,L,5) float32 stroke-5 rows in continuous mode (the reference casts the
         loader's float64 to float32 at the tf.function boundary, models/sketchformer.py:317-319)."""
         if not self.cfg.continuous:
-            return self._dev_tokens(x, self.cfg.vocab_size)
+            return self._dev_tokens(x, clone, self.cfg.vocab_size)
         t = torch.as_tensor(x)
         if t.dim() != 3 or t.shape[-1] != 5:
             raise ValueError("continuous mode expects (B, L, 5) stroke-5 input")
-        return self._own(t, t.to(self.device, dtype=torch.float32, non_blocking=True).contiguous())
+        return self._own(t, t.to(self.device, dtype=torch.float32, non_blocking=True).contiguous(), clone)
 
     def _hold(self, *tensors):
         """The engine's stream reads these caller-owned tensors asynchronously: tell the caching allocator, so that a tensor the
@@ -287,8 +288,8 @@ class TrainEngine:
 
     def forward(self, inp, tar=None, training=False):
         """Transformer.call: fills the internal buffers (see ``buffer``)."""
-        inp = self._dev_input(inp)
-        tar = inp if tar is None else self._dev_input(tar)
+        inp = self._dev_input(inp, clone=True)
+        tar = inp if tar is None else self._dev_input(tar, clone=True)
         self._enter()
         try:
             self._hold(inp, tar)
@@ -303,7 +304,7 @@ class TrainEngine:
     def encode(self, inp):
         """encode_from_seq (models/sketchformer.py:162-168): encoder + bottleneck + classifier, dropout off.
         Results in the buffers 'embedding', 'class_probs', 'enc_output'."""
-        inp = self._dev_input(inp)
+        inp = self._dev_input(inp, clone=True)
         self._enter()
         try:
             self._hold(inp)
@@ -375,24 +376,27 @@ class TrainEngine:
             weights['decoder_layer%d_block2' % (i + 1)] = aw[2 * i + 1, :n_valid, :, :T, :].cpu().numpy()
         return res, weights
 
+    class _Staged:
+        """What _stage hands to _forward_backward_staged, and to nothing else: device tensors that may still be the CALLER's own."""
+        __slots__ = ("inp", "tar", "labels")
+
     def _stage(self, inp, tar, labels):
         """caller-side arguments -> device tensors (enqueued on the CALLER's stream: must precede _enter).  Device tensors of the
         caller are NOT cloned here (round 6): the library copies them into its workspace first thing on the engine's stream and
-        _forward_backward_staged makes the caller's stream wait for exactly that copy (skf_model_wait_inputs_staged) - the two
-        clone kernels per step sat on the caller's stream in front of the hand-over, ~19 us of idle GPU at the head of every step."""
-        self._clone_inputs = os.environ.get("SKF_CLONE_INPUTS") == "1"      # (A/B knob of the Python layer: the round-5 behaviour)
-        try:
-            inp = self._dev_input(inp)
-            tar = inp if tar is None else self._dev_input(tar)
-            labels = self._dev_tokens(labels, self.cfg.n_classes if self.cfg.do_classification and self.cfg.lowerdim else None,
-                                      "class label")
-        finally:
-            self._clone_inputs = True
-        return inp, tar, labels
+        _forward_backward_staged - the only consumer of the result - makes the caller's stream wait for exactly that copy
+        (skf_model_wait_inputs_staged); the two clone kernels per step sat on the caller's stream in front of the hand-over,
+        ~19 us of idle GPU at the head of every step."""
+        clone = self._step_clones
+        st = self._Staged()
+        st.inp = self._dev_input(inp, clone)
+        st.tar = st.inp if tar is None else self._dev_input(tar, clone)
+        st.labels = self._dev_tokens(labels, clone, self.cfg.n_classes if self.cfg.do_classification and self.cfg.lowerdim else None,
+                                     "class label")
+        return st
 
-    def _forward_backward_staged(self, inp, tar, labels):
-        self._hold(inp, tar, labels)
-        _lib.call("skf_model_forward_backward", self.handle, self._p(inp), self._p(tar), self._ld(tar), self._p(labels),
+    def _forward_backward_staged(self, st):
+        self._hold(st.inp, st.tar, st.labels)
+        _lib.call("skf_model_forward_backward", self.handle, self._p(st.inp), self._p(st.tar), self._ld(st.tar), self._p(st.labels),
                   self._stream())
         # the caller may refill its device tensors as soon as the staging copy has read them: its stream waits for that copy only
         _lib.call("skf_model_wait_inputs_staged", self.handle, torch.cuda.current_stream(self.device).cuda_stream)
@@ -401,7 +405,7 @@ class TrainEngine:
         staged = self._stage(inp, tar, labels)
         self._enter()
         try:
-            self._forward_backward_staged(*staged)
+            self._forward_backward_staged(staged)
         finally:
             self._leave()
 
@@ -458,7 +462,7 @@ class TrainEngine:
         staged = self._stage(inp, tar, labels)       # host-to-device copies of the batch go to the caller's stream FIRST:
         self._enter()                                # the hand-over below is what orders the step behind them
         try:
-            self._forward_backward_staged(*staged)
+            self._forward_backward_staged(staged)
             self.apply_gradients()
         finally:
             self._leave()

@@ -156,6 +156,31 @@ def test_train_step_schedule_has_no_knobs():
         assert m is None, "%s names the retired knob %s" % (path, m.group(1))
 
 
+def test_launch_attached_events_and_input_handover_have_one_owner():
+    """The thread-local slot that carries an event to a launcher's last launch (skf_tls_tail) is named in skf_common.h - the attach
+    protocol: scope, chain helper, SKF_LAUNCH_TAIL - and at its single definition, nowhere else; the open-coded forms of the protocol
+    are gone; and the Python layer reads its clone knob once instead of flipping an attribute around every step."""
+    import glob
+    pkg = os.path.join(ROOT, "sketchformer_amd")
+    sources = [p for p in glob.glob(os.path.join(pkg, "**", "*"), recursive=True)
+               if os.path.splitext(p)[1] in (".py", ".hip", ".h", ".inc")]
+    assert len(sources) > 40, sources
+    slot_lines = []
+    for path in sources:
+        text = open(path, encoding="utf-8").read()
+        for gone in ("skf_tls_stop_event", "ParkedEventGuard", "take_ready", "_clone_inputs"):
+            assert gone not in text, "%s still names %s" % (path, gone)
+        if os.path.basename(path) != "skf_common.h":
+            slot_lines += [(os.path.basename(path), ln.strip()) for ln in text.splitlines() if re.search(r"\bskf_tls_tail\b", ln)]
+    assert len(slot_lines) == 1 and slot_lines[0][0] == "skf_model.hip", slot_lines
+    assert slot_lines[0][1].startswith("thread_local SkfTailSlot skf_tls_tail;"), slot_lines
+    header = open(os.path.join(pkg, "csrc", "skf_common.h")).read()
+    assert header.count("extern thread_local") == 1 and "extern thread_local SkfTailSlot skf_tls_tail;" in header
+    assert re.search(r"struct SkfTailSlot \{[^}]*hipEvent_t event[^}]*bool attached[^}]*\}", header)      # the event AND an explicit flag
+    assert open(os.path.join(pkg, "engine.py")).read().count("SKF_CLONE_INPUTS") == 1
+    assert "`SKF_CLONE_INPUTS=1`" in open(os.path.join(ROOT, "tools", "README.md")).read()
+
+
 def test_gemm_wsx_isa_has_no_crossed_select_packed_fp32():
     """Round 4 bisected the run-to-run wrong results of round 3's 'accumulate only' epilogue kind to a compiler-formed
     v_pk_add_f32 with crossed operand selects in gemm_wsx_kernel's exit block (skf_gemm_wsx.hip: launch_wsx).  The kind is gone; this
