@@ -689,6 +689,27 @@ int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int*
 int skf_model_buffer_info(SkfModel* m, const char* name, void** ptr, int* rows, int* cols, int* ld, int* is_bf16);
 int skf_model_buffer(SkfModel* m, const char* name, float** ptr, int* rows, int* cols);
 
+/* ------------------------------------------------------------------ Retrieval
+ * The third task the reference's README names for the learned embedding (classification, reconstruction / interpolation,
+ * image retrieval); the reference ships no code for it.  Serves the (N, d) embeddings that models/sketchformer.py:162-168
+ * (predict_class) returns and experiments/extract_embeddings.py writes.
+ * skf_knn_topk_f32: for each of Q query rows the k gallery rows with the smallest squared Euclidean distance
+ *   |q|^2 + |g|^2 - 2 q.g, ascending: out_idx (Q, k) int32 gallery rows, out_dist (Q, k) fp32.  Exact search: the Q x G scores
+ *   are formed tile by tile on the fp32 matrix cores and never stored.  Equal distances come out in gallery-row order; the
+ *   distance of a (query, gallery row) pair does not depend on where either row sits, nor on how the search was cut up, so two
+ *   calls over the same rows agree bit for bit.  exclude (NULL, or Q int32, -1 = none): one gallery row per query that is left
+ *   out of its ranking (leave-one-out over a single split: exclude[i] = i).
+ *   Limits (SKF_EINVAL): d % 4 == 0, 4 <= d <= 1024, 1 <= k <= 128, k <= G (G - 1 with exclude), Q >= 1, rows 16-byte aligned
+ *   (base pointers and ldq, ldg % 4 == 0).  Inputs must be finite.  workspace: skf_knn_workspace_bytes(Q, G, k) bytes
+ *   (0 = bad sizes), 16-byte aligned.
+ * skf_row_normalize_f32: y = x / max(|x|, 1e-12) per row, out of place.  The cosine ranking is the same search on normalised
+ *   rows; the distance reported is then 2 - 2 cos. */
+size_t skf_knn_workspace_bytes(int Q, int G, int k);
+int skf_knn_topk_f32(const float* queries, int ldq, int Q, const float* gallery, int ldg, int G, int d, int k,
+                     const int* exclude, int* out_idx, float* out_dist, void* workspace, size_t workspace_bytes,
+                     skf_stream_t stream);
+int skf_row_normalize_f32(const float* x, int ldx, int rows, int d, float* y, int ldy, skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,9 @@ SIGNATURES = {
     "skf_model_apply_gradients": (_I, [_P, _F, _P]),
     "skf_model_buffer": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]),
     "skf_model_buffer_info": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "skf_knn_workspace_bytes": (_Z, [_I, _I, _I]),
+    "skf_knn_topk_f32": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "skf_row_normalize_f32": (_I, [_P, _I, _I, _I, _P, _I, _P]),
 }
 
 _lib = None

@@ -537,3 +537,42 @@ def dropout_keep_mask(drop_key, site, rate, n):
     out = np.empty(n, dtype=np.uint8)
     _lib.call("skf_dropout_keep_mask", drop_key, site, rate, n, out.ctypes.data_as(C.c_void_p))
     return out.astype(bool)
+
+
+def row_normalize(x):
+    """(N, d) float32 -> rows divided by max(norm, 1e-12), out of place (skf_row_normalize_f32)."""
+    _f32(x, "x")
+    assert x.dim() == 2
+    y = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
+    _lib.call("skf_row_normalize_f32", _p(x), x.stride(0), x.shape[0], x.shape[1], _p(y), y.stride(0), _stream())
+    return y
+
+
+def knn_topk(queries, gallery, k, exclude=None, metric='l2'):
+    """Exact k nearest gallery rows of every query row (skf_knn_topk_f32): queries (Q, d), gallery (G, d) float32 ->
+    (indices int32 (Q, k), distances float32 (Q, k)), ascending by squared Euclidean distance, ties to the lower gallery row.
+    exclude: int32 (Q,), one gallery row per query left out of its ranking (-1 = none).  metric 'cosine' ranks the row-normalised
+    inputs (the distance is then 2 - 2 cos)."""
+    if metric not in ('l2', 'cosine'):
+        raise ValueError("metric must be 'l2' or 'cosine' (got %r)" % (metric,))
+    _f32(queries, "queries"); _f32(gallery, "gallery")
+    if queries.dim() != 2 or gallery.dim() != 2 or queries.shape[1] != gallery.shape[1]:
+        raise ValueError("queries (Q, d) and gallery (G, d) must share d")
+    _p(queries); _p(gallery)                                     # CPU tensors: SkfError before anything is allocated
+    if gallery.device != queries.device:
+        raise ValueError("queries and gallery must be on one device")
+    if exclude is not None:
+        if exclude.dtype != torch.int32 or exclude.shape != (queries.shape[0],) or not exclude.is_contiguous():
+            raise TypeError("exclude must be a contiguous int32 tensor of shape (Q,)")
+    Q, d = queries.shape
+    G = gallery.shape[0]
+    k = int(k)
+    if metric == 'cosine':
+        queries, gallery = row_normalize(queries), row_normalize(gallery)
+    idx = torch.empty(Q, k, dtype=torch.int32, device=queries.device)
+    dist = torch.empty(Q, k, dtype=torch.float32, device=queries.device)
+    wsb = _lib.load().skf_knn_workspace_bytes(Q, G, k)
+    ws = _ws(wsb, queries.device)
+    _lib.call("skf_knn_topk_f32", _p(queries), queries.stride(0), Q, _p(gallery), gallery.stride(0), G, d, k, _p(exclude),
+              _p(idx), _p(dist), _p(ws), ws.numel(), _stream())
+    return idx, dist
