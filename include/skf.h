@@ -710,6 +710,41 @@ int skf_knn_topk_f32(const float* queries, int ldq, int Q, const float* gallery,
                      skf_stream_t stream);
 int skf_row_normalize_f32(const float* x, int ldx, int rows, int d, float* y, int ldy, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Token dictionary (k-means)
+ * The dictionary of the default tokenizer: prep_data/sketch_token/create_token_dict.py:104-109 fits sklearn KMeans(n_clusters=1000,
+ * n_init=10, max_iter=500, tol=1e-6) over 5 M normalised (dx, dy) offsets, and utils/tokenizer.py:43 maps every offset to its
+ * nearest centre (KMeans.predict).  Lloyd iterations for 2-D points:
+ * skf_kmeans_assign_f32: labels[i] (N int32) = the nearest of K centres for point i, and optionally dist[i] (N fp32, NULL = not
+ *   wanted) = its squared distance.  The distance of a pair is DEFINED as dx = x - cx; dy = y - cy; fmaf(dy, dy, dx * dx) in fp32,
+ *   so it depends on the two rows alone; among equal minima the lowest centre index wins (the first-minimum rule of argmin).
+ * skf_kmeans_step_f32: one Lloyd iteration, always the same three commands (clear accumulators, assign + accumulate, update):
+ *   labels as above against the centres going in; per centre the count (counts, K int32, NULL = not wanted) and the mean of its
+ *   points, written over `centers` in place - a centre that received no point keeps its coordinates; into *state the inertia (sum
+ *   of the minimum distances, fp64), the squared shift sum |c_new - c_old|^2 (fp64), the number of empty centres, and
+ *   iterations += 1.  Coordinates are accumulated as 64-bit integers of rint(x * 2^scale_exp) - the caller picks scale_exp once per
+ *   fit so that max|coordinate| * 2^scale_exp < 2^30 - and the mean is formed in fp64 and rounded once to fp32, the inertia is
+ *   summed in a fixed order: the result is bit-identical from run to run and does not depend on grid size or arrival order.
+ *   Stop flag: when shift <= tol_abs the update sets state->converged; every later step on that state returns at once and leaves
+ *   centres, labels, counts and state as that iteration wrote them (tol_abs < 0: never stops).  A fit zeroes the state block
+ *   once, enqueues steps in groups and reads the block once per group; nothing here synchronises with the host.
+ *   Limits: d == 2 (else SKF_EUNSUPPORTED); SKF_EINVAL: 1 <= K <= 4096, 1 <= N < 2^31, rows 8-byte aligned (base pointers, and ldp,
+ *   ldc even), scale_exp in [-126, 127].  Inputs must be finite.  workspace: skf_kmeans_workspace_bytes(N, K) bytes (0 = bad
+ *   sizes), 16-byte aligned; its contents carry nothing from one step to the next. */
+typedef struct SkfKmeansState {
+  int32_t iterations; /* Lloyd iterations performed on this state */
+  int32_t converged;  /* set by the iteration whose shift <= tol_abs */
+  int32_t n_empty;    /* centres that received no point in the last iteration */
+  int32_t pad;
+  double inertia;     /* of the last iteration's assignment */
+  double shift;       /* sum |c_new - c_old|^2 of the last iteration */
+} SkfKmeansState;
+size_t skf_kmeans_workspace_bytes(long long N, int K);
+int skf_kmeans_assign_f32(const float* points, int ldp, long long N, int d, const float* centers, int ldc, int K,
+                          int* labels, float* dist, skf_stream_t stream);
+int skf_kmeans_step_f32(const float* points, int ldp, long long N, int d, float* centers, int ldc, int K, int scale_exp,
+                        double tol_abs, int* labels, int* counts, SkfKmeansState* state, void* workspace,
+                        size_t workspace_bytes, skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,12 @@ class SkfFfnBlockFwd(C.Structure):
                 ("proj_image", C.c_void_p), ("proj_bias", C.c_void_p), ("proj_out", C.c_void_p)]
 
 
+class SkfKmeansState(C.Structure):
+    """include/skf.h: struct SkfKmeansState, field for field (skf_kmeans_step_f32)."""
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("n_empty", C.c_int32), ("pad", C.c_int32),
+                ("inertia", C.c_double), ("shift", C.c_double)]
+
+
 class SkfParamEntry(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32),
                 ("row_stride", C.c_int32)]
@@ -84,6 +90,8 @@ _I = C.c_int
 _F = C.c_float
 _Z = C.c_size_t
 _U = C.c_uint
+_L = C.c_longlong
+_D = C.c_double
 
 # name -> (restype, argtypes).  Mirrors include/skf.h one to one (tests check this).
 SIGNATURES = {
@@ -228,6 +236,9 @@ SIGNATURES = {
     "skf_knn_workspace_bytes": (_Z, [_I, _I, _I]),
     "skf_knn_topk_f32": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "skf_row_normalize_f32": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "skf_kmeans_workspace_bytes": (_Z, [_L, _I]),
+    "skf_kmeans_assign_f32": (_I, [_P, _I, _L, _I, _P, _I, _I, _P, _P, _P]),
+    "skf_kmeans_step_f32": (_I, [_P, _I, _L, _I, _P, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

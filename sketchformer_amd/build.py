@@ -6,12 +6,16 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libskf.so")
-SOURCES = ["skf_model.hip", "skf_gemm.hip", "skf_gemm_ws.hip", "skf_gemm_small.hip", "skf_gemm_wsx.hip", "skf_gemm_wgrad.hip", "skf_ffn_fused.hip", "skf_attention.hip", "skf_attention_bwd2.hip", "skf_attention_bwd3.hip", "skf_rowops.hip", "skf_continuous.hip", "skf_optimizer.hip", "skf_decode.hip", "skf_decode_fused.hip", "skf_row_blocks.hip", "skf_generic.hip", "skf_bf16_gemm.hip", "skf_bf16_attention.hip", "skf_bf16_rowops.hip", "skf_retrieval.hip"]
+SOURCES = ["skf_model.hip", "skf_gemm.hip", "skf_gemm_ws.hip", "skf_gemm_small.hip", "skf_gemm_wsx.hip", "skf_gemm_wgrad.hip", "skf_ffn_fused.hip", "skf_attention.hip", "skf_attention_bwd2.hip", "skf_attention_bwd3.hip", "skf_rowops.hip", "skf_continuous.hip", "skf_optimizer.hip", "skf_decode.hip", "skf_decode_fused.hip", "skf_row_blocks.hip", "skf_generic.hip", "skf_bf16_gemm.hip", "skf_bf16_attention.hip", "skf_bf16_rowops.hip", "skf_retrieval.hip", "skf_kmeans.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          # f32-input MFMA shares the VALU pipe on gfx950 (tools/micro/mfma_valu_overlap.hip): keep accumulators in VGPRs so
          # the epilogues need no v_accvgpr_read/write moves (they were ~30 % of the VALU instructions of the attention loops)
          "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Wall", "-Wno-unused-function", "-Wno-unused-value"]
 FLAGS += os.environ.get("SKF_EXTRA_HIPCC_FLAGS", "").split()   # e.g. -DSKF_WS_STAMPS=1 for tools/ws_timeline.py
+# per-source additions.  skf_kmeans.hip: its distance loop is scalar fp32 on purpose; left alone, -O3 pairs the
+# subtracts / multiplies / fmas of neighbouring points into v_pk_*_f32, which run at the scalar rate on gfx950 and cost extra
+# v_mov / s_nop around them
+SOURCE_FLAGS = {"skf_kmeans.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():
@@ -27,7 +31,7 @@ STAMP = LIB + ".stamp"
 def _source_digest():
     """sha256 over every file the library is built from + the compiler flags (file times do not survive a snapshot copy)."""
     import hashlib
-    h = hashlib.sha256(" ".join(FLAGS).encode())
+    h = hashlib.sha256((" ".join(FLAGS) + repr(sorted(SOURCE_FLAGS.items()))).encode())
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + [os.path.join(HERE, "..", "include", "skf.h")]
     for path in files:
         h.update(os.path.basename(path).encode())
@@ -52,7 +56,7 @@ def build_library(force=False, verbose=True):
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     for src in SOURCES:
         obj = os.path.join(HERE, "build", src.replace(".hip", ".o"))
-        cmd = [_hipcc()] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [_hipcc()] + FLAGS + SOURCE_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -576,3 +576,69 @@ def knn_topk(queries, gallery, k, exclude=None, metric='l2'):
     _lib.call("skf_knn_topk_f32", _p(queries), queries.stride(0), Q, _p(gallery), gallery.stride(0), G, d, k, _p(exclude),
               _p(idx), _p(dist), _p(ws), ws.numel(), _stream())
     return idx, dist
+
+
+def _kmeans_operands(points, centers):
+    _f32(points, "points"); _f32(centers, "centers")
+    if points.dim() != 2 or centers.dim() != 2 or points.shape[1] != centers.shape[1]:
+        raise ValueError("points (N, d) and centers (K, d) must share d")
+    _p(points); _p(centers)                                      # CPU tensors: SkfError before anything is allocated
+    if centers.device != points.device:
+        raise ValueError("points and centers must be on one device")
+
+
+def kmeans_assign(points, centers, return_dist=False):
+    """Nearest centre of every point (skf_kmeans_assign_f32): points (N, 2), centers (K, 2) float32 -> labels int32 (N,), and
+    with return_dist the squared distances float32 (N,).  The distance is fmaf(dy, dy, dx * dx) in fp32; among equal minima the
+    lowest centre index wins."""
+    _kmeans_operands(points, centers)
+    N, d = points.shape
+    labels = torch.empty(N, dtype=torch.int32, device=points.device)
+    dist = torch.empty(N, dtype=torch.float32, device=points.device) if return_dist else None
+    _lib.call("skf_kmeans_assign_f32", _p(points), points.stride(0), N, d, _p(centers), centers.stride(0), centers.shape[0],
+              _p(labels), _p(dist), _stream())
+    return (labels, dist) if return_dist else labels
+
+
+def new_kmeans_state(device):
+    """Device-resident SkfKmeansState {int32 iterations, converged, n_empty, pad; f64 inertia, shift}, zeroed: one per fit."""
+    return torch.zeros(C.sizeof(_lib.SkfKmeansState) // 8, dtype=torch.int64, device=device)
+
+
+def read_kmeans_state(state):
+    """-> dict(iterations, converged, n_empty, inertia, shift) (host sync)."""
+    s = _lib.SkfKmeansState.from_buffer_copy(state.cpu().numpy().tobytes())
+    return {"iterations": s.iterations, "converged": bool(s.converged), "n_empty": s.n_empty, "inertia": s.inertia, "shift": s.shift}
+
+
+def kmeans_scale_exp(max_abs):
+    """The largest e with max_abs * 2^e < 2^30 (the integer image of a coordinate that skf_kmeans_step_f32 accumulates)."""
+    import math
+    if not max_abs > 0.0:
+        return 0
+    return max(-126, min(127, 30 - math.frexp(float(max_abs))[1]))      # max_abs = m * 2^ex, m in [0.5, 1) -> max_abs < 2^ex
+
+
+def kmeans_step(points, centers, state, scale_exp, tol_abs=-1.0, labels=None, counts=None, workspace=None):
+    """One Lloyd iteration (skf_kmeans_step_f32), enqueued on the current stream: labels of `points` against `centers`, then
+    `centers` (K, 2) overwritten IN PLACE by the means of their points (a centre without points keeps its coordinates) and `state`
+    (new_kmeans_state) updated: iterations += 1, inertia, shift, n_empty, and converged once shift <= tol_abs (tol_abs < 0: never).
+    On a converged state the call changes nothing.  scale_exp: kmeans_scale_exp(max |coordinate|), chosen once per fit.
+    labels / counts / workspace are allocated when not passed (a fit passes the same ones every iteration).
+    -> (labels int32 (N,), counts int32 (K,))."""
+    _kmeans_operands(points, centers)
+    N, d = points.shape
+    K = centers.shape[0]
+    dev = points.device
+    if state.dtype != torch.int64 or state.numel() * 8 < C.sizeof(_lib.SkfKmeansState) or not state.is_contiguous():
+        raise TypeError("state must come from new_kmeans_state")
+    labels = torch.empty(N, dtype=torch.int32, device=dev) if labels is None else labels
+    counts = torch.empty(K, dtype=torch.int32, device=dev) if counts is None else counts
+    if labels.dtype != torch.int32 or labels.shape != (N,) or not labels.is_contiguous():
+        raise TypeError("labels must be a contiguous int32 tensor of shape (N,)")
+    if counts.dtype != torch.int32 or counts.shape != (K,) or not counts.is_contiguous():
+        raise TypeError("counts must be a contiguous int32 tensor of shape (K,)")
+    ws = _ws(_lib.load().skf_kmeans_workspace_bytes(N, K), dev) if workspace is None else workspace
+    _lib.call("skf_kmeans_step_f32", _p(points), points.stride(0), N, d, _p(centers), centers.stride(0), K, int(scale_exp),
+              float(tol_abs), _p(labels), _p(counts), _p(state), _p(ws), ws.numel(), _stream())
+    return labels, counts
