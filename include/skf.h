@@ -745,6 +745,24 @@ int skf_kmeans_step_f32(const float* points, int ldp, long long N, int d, float*
                         double tol_abs, int* labels, int* counts, SkfKmeansState* state, void* workspace,
                         size_t workspace_bytes, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Latent interpolation
+ * The step between encode and greedy decode of experiments/interpolations_for_mturk.py:98-108: utils/skt_tools.py:18-25 (slerp) and
+ * :28-30 (lerp), for P pairs and T steps in one launch.
+ * skf_interpolate_f32: a, b (P, d) fp32 rows, t T fp32 steps, all on the device; out (P * T, d): row p * T + j is the
+ *   interpolation of (a[p], b[p]) at t[j].  mode 0 = slerp, 1 = lerp.
+ *   slerp: per pair aa = sum a_i^2, bb = sum b_i^2, ab = sum a_i b_i in fp64 (the products are exact; the three sums run over the
+ *   same elements in the same order), c = ab / sqrt(aa * bb) CLAMPED to [-1, 1], omega = acos(c), so = sin(omega), all fp64.  The
+ *   reference takes arccos of the unclamped dot product and returns NaN once rounding pushes |c| past 1; here those pairs take the
+ *   next branch.  so < 1e-6 (same or opposite direction, the reference's `return p0`): every row of the pair is a copy of a[p].
+ *   Otherwise w0 = (float)(sin((1 - (double)t_j) * omega) / so), w1 = (float)(sin((double)t_j * omega) / so).
+ *   lerp: w0 = 1.0f - t_j, w1 = t_j.  Elements, both modes, fp32: out_i = fmaf(w1, b_i, w0 * a_i).  So t = 0 gives the row a[p] and
+ *   t = 1 the row b[p], exactly; b = s a with s a power of two gives c = 1 exactly; two calls on the same inputs agree bit for bit.
+ *   Limits (SKF_EINVAL): d % 4 == 0, 4 <= d <= 4096, 1 <= T <= 256, P >= 1, P * T < 2^31, rows 16-byte aligned (base pointers of
+ *   a, b, out and lda, ldb, ldo % 4 == 0, each >= d), mode in {0, 1}.  Columns >= d of out are left alone.  out must not alias a
+ *   or b (not checked).  Inputs must be finite with non-zero norm. */
+int skf_interpolate_f32(const float* a, int lda, const float* b, int ldb, int P, int d, const float* t, int T, int mode,
+                        float* out, int ldo, skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,7 @@ SIGNATURES = {
     "skf_kmeans_workspace_bytes": (_Z, [_L, _I]),
     "skf_kmeans_assign_f32": (_I, [_P, _I, _L, _I, _P, _I, _I, _P, _P, _P]),
     "skf_kmeans_step_f32": (_I, [_P, _I, _L, _I, _P, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
+    "skf_interpolate_f32": (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
 }
 
 _lib = None

@@ -243,6 +243,42 @@ class DistributedStroke3DataLoader(BaseDataLoader):
             conv[-1:, 4] = 1
         return conv
 
+    def preprocess_extra_sets_from_interp_experiment(self, data):
+        """dataloaders/distributed_stroke3.py:164-179: the sketch lists the interpolation experiment brings along, which are
+        normalised already - no clamp, no normalisation, no squeeze: (N, L, 1) int tokens or (N, L, 5) stroke-5 rows."""
+        out = []
+        for sketch in data:
+            if self.hps["use_absolute_strokes"]:
+                sketch = convert_to_absolute(sketch)
+            if not self.hps["use_continuous_data"]:
+                sketch = self.tokenizer.encode(sketch)
+            if len(sketch) > self.hps["max_seq_len"]:
+                sketch = sketch[:self.hps["max_seq_len"]]
+            out.append(self._cap_pad_and_convert_sketch(sketch))
+        return np.array(out)
+
+    def get_class_exclusive_random_batch(self, split_name, n, class_list):
+        """dataloaders/distributed_stroke3.py:181-204: n // len(class_list) sketches of every class of class_list, in the order of
+        the seed-14 permutation of the split's current megabatch (the reference reads it through a get_split_data its loader
+        base class does not define)."""
+        self._ready(split_name)
+        data = self.splits[split_name].current
+        x, y = data["x"], data["y"]
+        np.random.seed(14)
+        idx = np.random.permutation(len(x))
+        np.random.seed()
+        n_per_class = n // len(class_list)
+        sel = []
+        for chosen in class_list:
+            n_from_class = 0
+            for i in idx:
+                if y[i] == chosen:
+                    sel.append(x[i])
+                    n_from_class += 1
+                    if n_from_class >= n_per_class:
+                        break
+        return np.array(sel)
+
     def _augment_sketch(self, sketch):
         """dataloaders/distributed_stroke3.py:155-160: random_scale (:127-137) then utils.sketch.augment_strokes; the
         random stream is consumed exactly like there: two draws for the scale factors, then one per point."""

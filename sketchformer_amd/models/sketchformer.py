@@ -238,6 +238,70 @@ class Transformer(BaseModel, TransformerMetricsMixin):
             out['attn_weights'] = dec['attn_weights']
         return out
 
+    def _embed_on_device(self, x):
+        """Bottleneck embeddings of any number of model-ready sequences as ONE device (P, E) float32 tensor: encoded in chunks of
+        batch_size, every chunk's rows copied out of the 'embedding' buffer device to device."""
+        import torch
+        x = np.asarray(x)
+        B = self.engine.cfg.batch
+        z = None
+        for i in range(0, len(x), B):
+            pad, n = self._pad_batch(x[i:i + B])
+            self.engine.encode(pad)
+            buf = self.engine.buffer('embedding')          # orders the current stream behind the encode
+            if z is None:
+                z = torch.empty(len(x), buf.shape[1], dtype=torch.float32, device=buf.device)
+            z[i:i + n].copy_(buf[:n])                      # the next encode's hand-over orders it behind this copy
+        return z
+
+    def interpolate(self, x_a, x_b, n_steps=10, mode='slerp', decode=True):
+        """n_steps embeddings on the way from every sketch of x_a to its partner in x_b (the slerp of
+        experiments/interpolations_for_mturk.py:98-108), and their greedy reconstructions.  x_a, x_b: P model-ready sequences
+        each (P is not limited by batch_size).  The embeddings stay on the device from the encoder to the decoder
+        (ops.interpolate at t = linspace(0, 1, n_steps) in float32).  decode: the P * n_steps rows, pair-major, go through the
+        decoder in consecutive chunks of batch_size rows (expected_len=None, like the reference's experiment; the last chunk is
+        zero-padded) and every chunk's reconstruction is zero-padded to seq_len + 1 columns - what a row holds after its own
+        EOS depends on when its chunk stops, so the chunking is part of the result.
+        Returns {'embedding': (P, T, E) float32, 'recon': (P, T, seq_len + 1[, 5]) or None, 'class': (P, T) int32 or None}."""
+        import torch
+        from .. import ops
+        if not self.hps['lowerdim']:
+            raise ValueError("interpolate needs lowerdim > 0: without a bottleneck the embedding is the (L, d) encoder output, "
+                             "and the reference's slerp of two matrices is not an interpolation")
+        if decode and not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        x_a, x_b = np.asarray(x_a), np.asarray(x_b)
+        if x_a.shape != x_b.shape or x_a.ndim != (3 if self.engine.cfg.continuous else 2) or len(x_a) == 0:
+            raise ValueError("x_a and x_b must hold the same number (>= 1) of model-ready sequences")
+        za, zb = self._embed_on_device(x_a), self._embed_on_device(x_b)
+        z = ops.interpolate(za, zb, torch.linspace(0, 1, int(n_steps), dtype=torch.float32), mode)
+        P, T, E = z.shape
+        out = {'embedding': z.cpu().numpy(), 'recon': None, 'class': None}
+        if not decode:
+            return out
+        B, L = self.engine.cfg.batch, self.seq_len + 1
+        tok = self.dataset.tokenizer
+        flat = z.view(P * T, E)
+        recon, cls = [], []
+        for i in range(0, P * T, B):
+            chunk = flat[i:i + B]
+            n = chunk.shape[0]
+            if n < B:
+                chunk = torch.cat([chunk, torch.zeros(B - n, E, dtype=torch.float32, device=z.device)], dim=0)
+            r = self.engine.greedy_decode(chunk, expected_len=None, n_valid=n,
+                                          sos=getattr(tok, 'SOS', 0) if tok is not None else 0,
+                                          eos=getattr(tok, 'EOS', 0) if tok is not None else 0)
+            pad = np.zeros((n, L) + r.shape[2:], dtype=r.dtype)
+            pad[:, :r.shape[1]] = r
+            recon.append(pad)
+            if self._has_cls:
+                cls.append(self.engine.buffer('class_probs')[:n].cpu().numpy().argmax(-1).astype(np.int32))
+        recon = np.concatenate(recon, axis=0)
+        out['recon'] = recon.reshape((P, T) + recon.shape[1:])
+        if self._has_cls:
+            out['class'] = np.concatenate(cls, axis=0).reshape(P, T)
+        return out
+
     def load_reference_checkpoint(self, prefix):
         """Weights (+ Adam slots, optimizer.iterations, current_step) from a checkpoint written by the reference's
         tf.train.Checkpoint(transformer=..., optimizer=...) (core/models.py:321-344), read without TensorFlow."""

@@ -578,6 +578,43 @@ def knn_topk(queries, gallery, k, exclude=None, metric='l2'):
     return idx, dist
 
 
+INTERP_MODES = {'slerp': 0, 'lerp': 1}
+
+
+def interpolate(a, b, t, mode='slerp', out=None):
+    """T interpolation steps between P pairs of rows (skf_interpolate_f32): a, b (P, d) float32, t a 1-D float32 tensor or a
+    sequence of T numbers (taken as float32) -> (P, T, d) float32, [p, j] = the interpolation of (a[p], b[p]) at t[j].
+    mode 'slerp': fp64 angle, fp32 weights sin((1 - t) w) / sin w and sin(t w) / sin w; a pair that points the same or the
+    opposite way (sin w < 1e-6) returns a[p] in every row.  mode 'lerp': weights 1 - t and t.  t = 0 / t = 1 give a[p] / b[p]
+    exactly.  out: a (P, T, d) view to write instead of a new tensor (its rows may sit in a wider buffer; it must not overlap a
+    or b)."""
+    if mode not in INTERP_MODES:
+        raise ValueError("mode must be 'slerp' or 'lerp' (got %r)" % (mode,))
+    _f32(a, "a"); _f32(b, "b")
+    if a.dim() != 2 or b.dim() != 2 or a.shape != b.shape:
+        raise ValueError("a and b must both be (P, d) (got %r and %r)" % (tuple(a.shape), tuple(b.shape)))
+    _p(a); _p(b)                                                 # CPU tensors: SkfError before anything is allocated
+    if b.device != a.device:
+        raise ValueError("a and b must be on one device")
+    if not torch.is_tensor(t):
+        t = torch.tensor([float(v) for v in t], dtype=torch.float32)
+    if t.dim() != 1:
+        raise ValueError("t must be one-dimensional")
+    t = t.to(device=a.device, dtype=torch.float32).contiguous()
+    P, d = a.shape
+    T = t.shape[0]
+    if out is None:
+        out = torch.empty(P, T, d, dtype=torch.float32, device=a.device)
+    else:
+        _f32(out, "out")
+        ldo = out.stride(1) if out.dim() == 3 else 0
+        if tuple(out.shape) != (P, T, d) or out.device != a.device or out.stride(0) != T * ldo:
+            raise ValueError("out must be a (P, T, d) device tensor whose rows p * T + j share one pitch")
+    _lib.call("skf_interpolate_f32", _p(a), a.stride(0), _p(b), b.stride(0), P, d, _p(t), T, INTERP_MODES[mode],
+              _p(out), out.stride(1), _stream())
+    return out
+
+
 def _kmeans_operands(points, centers):
     _f32(points, "points"); _f32(centers, "centers")
     if points.dim() != 2 or centers.dim() != 2 or points.shape[1] != centers.shape[1]:
