@@ -436,6 +436,41 @@ int skf_decode_select_continuous(const float* pred, int ld, int B, int n_valid, 
                                  unsigned char* selfmask, int mask_ld, int* done_step, int* step_dev,
                                  const long long* dyn, skf_stream_t stream);
 
+/* ---- sampled token selection: temperature, top-k and nucleus (top-p) decoding ----
+ * The selection rule, for one row of V fp32 logits, temperature > 0, top_k >= 0 (0 = off), 0 < top_p <= 1 (1 = off) and a
+ * uniform u in [0, 1):
+ *   1. z_j = logit_j / temperature in fp32; m = max z; e_j = exp(z_j - m).
+ *   2. top-k: keep j iff z_j >= the k-th largest z (ties at the threshold are all kept; top_k >= V keeps everything);
+ *      dropped entries get e_j = 0.
+ *   3. nucleus, over what top-k kept, S = the kept mass: keep j iff the mass of kept entries with z_i > z_j is < top_p * S
+ *      (ties share one fate, the maximum is always kept).
+ *   4. inverse CDF in INDEX order over the survivors, S' their mass: r = u * S'; the token is the smallest surviving j whose
+ *      inclusive prefix sum of e exceeds r.
+ *   Both cuts are thresholds on z, so the result does not depend on how equal values are ordered.  The kernels hold a mass as
+ *   the integer floor(e_j * 2^32): every sum and prefix sum is exact and order-free (no floating-point atomics), r is
+ *   floor(u * S') < S', so a token is always found, and the token is a pure function of (row, parameters, u).
+ * The random stream: skf_sample_uniform(seed, stream_id, step) = n * 2^-24, n the top 24 bits of three rounds of the 32-bit
+ *   hash the dropout masks use; stateless, the same on host and device.  stream_id is a per-row integer of the caller's
+ *   choosing: a row's draws depend neither on the batch slot it occupies nor on what else is in the batch.
+ * SkfSampling: struct_size = sizeof(SkfSampling) (checked like SkfConfig's); SKF_EINVAL for temperature <= 0, top_k < 0 or
+ *   top_p outside (0, 1].
+ * skf_decode_sample_tokens: skf_decode_select_tokens with the token of row b drawn by the rule above with
+ *   u = skf_sample_uniform(sampling->seed, stream_ids[b], step) instead of maximised; stream_ids: B device ints.  One workgroup
+ *   per row holds the row in LDS (V <= 40064, else SKF_EUNSUPPORTED), a second launch does the done_step / step_dev part.
+ *   Same padding mask, sticky EOS flags and step_dev / dyn device-side form as skf_decode_select_tokens. */
+typedef struct SkfSampling {
+  uint32_t struct_size; /* sizeof(SkfSampling) */
+  float temperature;    /* > 0; 1 = the model's distribution */
+  int32_t top_k;        /* 0 = off */
+  float top_p;          /* in (0, 1]; 1 = off */
+  uint32_t seed;
+} SkfSampling;
+float skf_sample_uniform(unsigned seed, unsigned stream_id, unsigned step);
+int skf_decode_sample_tokens(const float* logits, int ld, int B, int V, int n_valid, int step, long long eos,
+                             long long* tokens, int tok_ld, unsigned char* selfmask, int mask_ld, int* eos_seen,
+                             int* done_step, int* step_dev, const long long* dyn, const SkfSampling* sampling,
+                             const int* stream_ids, skf_stream_t stream);
+
 /* ------------------------------------------------------------------ bf16 path (BASELINE cfg 5)
  * bf16 storage + v_mfma_f32_32x32x16_bf16 with fp32 accumulation, fp32 master weights / optimizer state (SkfConfig.act_dtype
  * = SKF_ACT_BF16).  `void*` tensors below are bf16 (2 bytes per element, pitches in elements); parameters, statistics,
@@ -683,6 +718,15 @@ int skf_model_greedy_decode(SkfModel* m, const float* embedding, const int* expe
 int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
                                  long long sos, long long eos, int max_steps, void* out, int* out_len_host,
                                  float* attn_weights, skf_stream_t stream);
+/* skf_model_sample_decode: skf_model_greedy_decode with every token DRAWN by the selection rule above (skf_decode_sample_tokens)
+ *   instead of maximised: position i of row b uses u = skf_sample_uniform(sampling->seed, stream_id[b], i).
+ *   stream_ids_host: B host ints, NULL = 0 .. B-1.  Same outputs, stop rule and blocking behaviour as the greedy entry; one launch
+ *   per position (the sampling instantiation of the same kernel), or with SKF_MODEL_DECODE_LAYERWISE the layer-by-layer steps
+ *   issued eagerly.  Keeps no state: greedy decoding before and after is unchanged.
+ *   Continuous models are refused (SKF_EUNSUPPORTED): there is no categorical head to draw from. */
+int skf_model_sample_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
+                            long long sos, long long eos, int max_steps, void* out, int* out_len_host,
+                            const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream);
 /* look up an internal activation by name ("logits", "class_probs", "embedding", "enc_output", ...); skf_model_buffer serves
  * fp32 buffers, skf_model_buffer_info any buffer with its row pitch (elements) and element type (bf16 models keep their
  * activations in bf16) */

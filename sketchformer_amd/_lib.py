@@ -80,6 +80,17 @@ class SkfKmeansState(C.Structure):
                 ("inertia", C.c_double), ("shift", C.c_double)]
 
 
+class SkfSampling(C.Structure):
+    """include/skf.h: struct SkfSampling, field for field (skf_model_sample_decode, skf_decode_sample_tokens)."""
+    _fields_ = [("struct_size", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("seed", C.c_uint32)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(SkfSampling)
+
+
 class SkfParamEntry(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32),
                 ("row_stride", C.c_int32)]
@@ -179,6 +190,8 @@ SIGNATURES = {
     "skf_decode_init": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, C.c_longlong, _P, _P]),
     "skf_decode_embed": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "skf_decode_select_tokens": (_I, [_P, _I, _I, _I, _I, _I, C.c_longlong, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "skf_sample_uniform": (_F, [_U, _U, _U]),
+    "skf_decode_sample_tokens": (_I, [_P, _I, _I, _I, _I, _I, C.c_longlong, _P, _I, _P, _I, _P, _P, _P, _P, C.POINTER(SkfSampling), _P, _P]),
     "skf_decode_select_continuous": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P]),
     "skf_gemm_bf16": (_I, [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _I, _P]),
     "skf_gemm_bf16_tile_rows": (_I, [_I, _I, _I, _I]),
@@ -230,6 +243,8 @@ SIGNATURES = {
     "skf_model_encode": (_I, [_P, _P, _P]),
     "skf_model_greedy_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, C.POINTER(_I), _P]),
     "skf_model_greedy_decode_attn": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, C.POINTER(_I), _P, _P]),
+    "skf_model_sample_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, C.POINTER(_I), C.POINTER(SkfSampling),
+                                     C.POINTER(_I), _P]),
     "skf_model_apply_gradients": (_I, [_P, _F, _P]),
     "skf_model_buffer": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]),
     "skf_model_buffer_info": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),

@@ -223,6 +223,17 @@ __host__ __device__ __forceinline__ uint32_t skf_hash32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
   return x;
 }
+// Counter-based uniform of the sampled decode: draw `step` of the caller's stream `stream_id` under `seed`, three hash rounds,
+// as 24 bits n (the uniform is n * 2^-24, in [0, 1)).  Stateless; identical on host (skf_sample_uniform) and device.
+__host__ __device__ __forceinline__ uint32_t skf_sample_bits24(uint32_t seed, uint32_t stream_id, uint32_t step) {
+  uint32_t h = skf_hash32(seed + 0x243f6a88U);
+  h = skf_hash32(h ^ (stream_id * 0x9e3779b1U));
+  h = skf_hash32(h + step * 0x85ebca6bU);
+  return h >> 8;
+}
+__host__ __device__ __forceinline__ float skf_sample_uniform01(uint32_t seed, uint32_t stream_id, uint32_t step) {
+  return (float)skf_sample_bits24(seed, stream_id, step) * (1.0f / 16777216.0f);
+}
 __host__ __device__ __forceinline__ uint32_t skf_site_key(uint32_t key, uint32_t site) {
   return skf_hash32(key ^ (0x9e3779b9U * (site + 1)));
 }

@@ -5,6 +5,7 @@
 #include "skf_common.h"
 #include "../../include/skf.h"
 #include "skf_decode_fused.h"
+#include "skf_sample.h"
 
 namespace {
 
@@ -213,6 +214,50 @@ __global__ __launch_bounds__(1024) void decode_select_tokens_kernel(const float*
   }
 }
 
+// Sampled counterpart of decode_select_tokens_kernel, first half: one workgroup per row draws the row's token by the selection
+// rule (skf_sample.h, the device function decode_position_kernel uses) with u = uniform(seed, stream_ids[b], step), appends it and
+// maintains the padding mask and the sticky EOS flag.  Dynamic LDS: the row, then the scratch of skf_sample_row.
+__global__ __launch_bounds__(SKF_SAMPLE_NT) void decode_sample_tokens_kernel(const float* __restrict__ logits, int ld, int V, int step,
+                                                                             long long eos, float temperature, int top_k, float top_p,
+                                                                             unsigned seed, const int* __restrict__ stream_ids,
+                                                                             long long* __restrict__ tokens, int tok_ld,
+                                                                             unsigned char* __restrict__ selfmask, int mask_ld,
+                                                                             int* __restrict__ eos_seen, const int* __restrict__ step_dev,
+                                                                             const long long* __restrict__ dyn) {
+  extern __shared__ __attribute__((aligned(16))) float srow[];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  if (step_dev) { step = *step_dev; eos = dyn[1]; }
+  const float* x = logits + (size_t)b * ld;
+  for (int j = tid; j < V; j += SKF_SAMPLE_NT) srow[j] = x[j];
+  __syncthreads();
+  const int am = skf_sample_row(srow, V, temperature, top_k, top_p, skf_sample_bits24(seed, (uint32_t)stream_ids[b], (uint32_t)step),
+                                srow + V, tid);
+  if (tid == 0) {
+    tokens[(size_t)b * tok_ld + step + 1] = am;
+    selfmask[(size_t)b * mask_ld + step + 1] = am == 0 ? 1 : 0;
+    if ((long long)am == eos) eos_seen[b] = 1;
+  }
+}
+
+// Second half, one workgroup: done_step = first step after which every one of the n_valid samples has emitted an EOS; the
+// device-side step index advances.
+__global__ __launch_bounds__(256) void decode_sample_finish_kernel(int n_valid, int step, const int* __restrict__ eos_seen,
+                                                                   int* __restrict__ done_step, int* __restrict__ step_dev,
+                                                                   const long long* __restrict__ dyn) {
+  __shared__ int cnt[256];
+  if (step_dev) { step = *step_dev; n_valid = (int)dyn[0]; }
+  int seen = 0;
+  for (int b = threadIdx.x; b < n_valid; b += 256) seen += eos_seen[b] ? 1 : 0;
+  cnt[threadIdx.x] = seen;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+    for (int k = 0; k < 256; ++k) t += cnt[k];
+    if (t >= n_valid && *done_step < 0) *done_step = step;
+    if (step_dev) *step_dev = step + 1;
+  }
+}
+
 // Continuous mode: appended row = (x, y, softmax(pen logits)); self-mask byte = (row[4] == 1);
 // done_step = first step in which argmax(pen) == 2 for all n_valid samples at once (not sticky).
 __global__ __launch_bounds__(256) void decode_select_continuous_kernel(const float* __restrict__ pred, int ld, int B,
@@ -353,6 +398,52 @@ extern "C" int skf_decode_select_tokens(const float* logits, int ld, int B, int 
   SKF_CHECK_ARG(B > 0 && V > 0 && (step_dev || (n_valid > 0 && n_valid <= B && step >= 0 && step + 1 < tok_ld && step + 1 < mask_ld)), "bad shape");
   hipLaunchKernelGGL(decode_select_tokens_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, ld, B, V, n_valid,
                      step, eos, tokens, tok_ld, selfmask, mask_ld, eos_seen, done_step, step_dev, dyn);
+  SKF_LAUNCH_CHECK();
+  return SKF_OK;
+}
+
+int skf_sampling_check(const SkfSampling* sp) {
+  SKF_CHECK_ARG(sp, "null SkfSampling");
+  if (sp->struct_size != sizeof(SkfSampling)) {
+    skf_set_error("SkfSampling.struct_size is %u, this library's SkfSampling has %zu bytes (set struct_size = sizeof(SkfSampling))",
+                  sp->struct_size, sizeof(SkfSampling));
+    return SKF_EINVAL;
+  }
+  SKF_CHECK_ARG(sp->temperature > 0.f && sp->temperature <= 3.0e38f, "temperature must be a finite number > 0");
+  SKF_CHECK_ARG(sp->top_k >= 0, "top_k must be >= 0 (0 = off)");
+  SKF_CHECK_ARG(sp->top_p > 0.f && sp->top_p <= 1.f, "top_p must be in (0, 1] (1 = off)");
+  return SKF_OK;
+}
+
+extern "C" float skf_sample_uniform(unsigned seed, unsigned stream_id, unsigned step) {
+  return skf_sample_uniform01(seed, stream_id, step);
+}
+
+extern "C" int skf_decode_sample_tokens(const float* logits, int ld, int B, int V, int n_valid, int step, long long eos,
+                                        long long* tokens, int tok_ld, unsigned char* selfmask, int mask_ld,
+                                        int* eos_seen, int* done_step, int* step_dev, const long long* dyn,
+                                        const SkfSampling* sampling, const int* stream_ids, skf_stream_t stream) {
+  SKF_CHECK_ARG(logits && tokens && selfmask && eos_seen && done_step && stream_ids, "null operand");
+  SKF_CHECK_ARG((step_dev == nullptr) == (dyn == nullptr), "step_dev and dyn go together");
+  SKF_CHECK_ARG(B > 0 && V > 0 && ld >= V && (step_dev || (n_valid > 0 && n_valid <= B && step >= 0 && step + 1 < tok_ld && step + 1 < mask_ld)), "bad shape");
+  {
+    const int rc = skf_sampling_check(sampling);
+    if (rc != SKF_OK) return rc;
+  }
+  const size_t smem = ((size_t)V + SKF_SAMPLE_SCRATCH_FLOATS) * sizeof(float);
+  if (smem > 159 * 1024) {
+    skf_set_error("%s: a row of %d logits does not fit the workgroup's LDS (at most %d)", __func__, V,
+                  (int)(159 * 1024 / sizeof(float)) - SKF_SAMPLE_SCRATCH_FLOATS);
+    return SKF_EUNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_sample_tokens_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              159 * 1024));      /* per launch: per-device attribute */
+  hipLaunchKernelGGL(decode_sample_tokens_kernel, dim3(B), dim3(SKF_SAMPLE_NT), smem, st, logits, ld, V, step, eos,
+                     sampling->temperature, sampling->top_k, sampling->top_p, sampling->seed, stream_ids, tokens, tok_ld, selfmask,
+                     mask_ld, eos_seen, (const int*)step_dev, dyn);
+  SKF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(decode_sample_finish_kernel, dim3(1), dim3(256), 0, st, n_valid, step, (const int*)eos_seen, done_step, step_dev, dyn);
   SKF_LAUNCH_CHECK();
   return SKF_OK;
 }

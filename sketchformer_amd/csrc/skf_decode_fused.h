@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include "../../include/skf.h"
 
 constexpr int SKF_DEC_MAX_LAYERS = 8;
 
@@ -26,10 +27,16 @@ struct SkfDecodeFused {
   const long long* dyn;                           // [0] n_valid, [1] eos
   const int* limit;                               // per-sample cross-attention key limit (non-blind) or null
   float* attn; int attn_rows;                     // null, or (2N, B, H, attn_rows, Le) softmax rows: [2l] self, [2l+1] cross; row = step
+  // sample != 0 (token mode): the token is drawn by the selection rule of include/skf.h with u = uniform(seed, stream_ids[b], step)
+  int sample; float temperature; int top_k; float top_p; unsigned seed;
+  const int* stream_ids;                          // (B) device
 };
 
 bool skf_decode_fused_supported(int d, int H, int F, int Le, int N, int Vout);
 int skf_decode_fused_launch(const SkfDecodeFused& p, hipStream_t st);
+
+// SkfSampling as the public entries take it: struct_size, temperature > 0, top_k >= 0, 0 < top_p <= 1 (SKF_EINVAL otherwise)
+int skf_sampling_check(const SkfSampling* s);
 
 // skf_attention_decode plus an optional copy of the softmax rows: attn (B, H, attn_rows, attn_ld), row *step_dev of every
 // (sample, head) = the Lk probabilities, then zeros up to attn_ld (attn non-null needs step_dev).

@@ -5,7 +5,7 @@
 //   x = embed(token_i) * sqrt(d) + pos[i]
 //   per layer: [q|k|v] = x Wqkv ; k|v appended to the cache ; attention of q over keys 0..i (target padding mask) ;
 //              o-projection ; LN ; q2 = . Wq ; attention over the cached K|V of pre_decoder ; o-projection ; LN ; FFN ; LN
-//   logits -> argmax (first index on ties) / stroke-5 row -> appended ; EOS bookkeeping
+//   logits -> argmax (first index on ties), or a sampled token (skf_sample.h) / stroke-5 row -> appended ; EOS bookkeeping
 // The round-1 path issued this as 51 dependent launches of ~7 us each (0.35 ms per position, all latency); here the
 // activations of the position never leave LDS, and what the kernel waits for is the weight stream: every workgroup reads
 // the decoder's weights (0.9 MB per layer at d = 128) from the L2 once per position - 16-byte loads, 16 in flight per thread
@@ -17,10 +17,12 @@
 // an EOS" -> done_step, and advances the device-side step index, so a position is ONE launch (captured once, replayed).
 #include "skf_common.h"
 #include "skf_decode_fused.h"
+#include "skf_sample.h"
 
 namespace {
 
 constexpr int NT = 512;   // threads per workgroup (8 waves)
+static_assert(NT == SKF_SAMPLE_NT && 4 * NT >= SKF_SAMPLE_SCRATCH_FLOATS, "skf_sample_row runs on this workgroup, in the `part` area");
 #ifndef SKF_DEC_UNROLL
 #define SKF_DEC_UNROLL 16
 #endif
@@ -197,7 +199,8 @@ __device__ __forceinline__ void attend(const float* q_lds, const float* __restri
 }
 
 // AW: the instantiation that writes the attention weights; the other one is the decoder without that output.
-template <int DH, bool AW>
+// SAMPLE: the token is drawn (temperature / top-k / nucleus, skf_sample.h) instead of maximised; what follows the choice is shared.
+template <int DH, bool AW, bool SAMPLE>
 __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -267,21 +270,29 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   if (p.tokens) {
     // models/sketchformer.py:285-301: next = argmax (first index on ties, tf.argmax); PAD masks the key in later steps;
     // EOS flags are sticky
-    float mx = -INFINITY; int am = 0x7fffffff;
-    for (int j = tid; j < p.Vout; j += NT) {
-      const float v = hs[j];
-      if (v > mx) { mx = v; am = j; }
-    }
+    int am;
+    if constexpr (SAMPLE) {
+      am = skf_sample_row(hs, p.Vout, p.temperature, p.top_k, p.top_p,
+                          skf_sample_bits24(p.seed, (uint32_t)p.stream_ids[b], (uint32_t)step), part, tid);
+    } else {
+      float mx = -INFINITY; am = 0x7fffffff;
+      for (int j = tid; j < p.Vout; j += NT) {
+        const float v = hs[j];
+        if (v > mx) { mx = v; am = j; }
+      }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(mx, o, 64); const int oa = __shfl_xor(am, o, 64);
-      if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
+      for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(mx, o, 64); const int oa = __shfl_xor(am, o, 64);
+        if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
+      }
+      if ((tid & 63) == 0) { s_mx[tid >> 6] = mx; s_am[tid >> 6] = am; }
+      __syncthreads();
+      if (tid == 0) {
+        for (int wv = 1; wv < NT / 64; ++wv)
+          if (s_mx[wv] > mx || (s_mx[wv] == mx && s_am[wv] < am)) { mx = s_mx[wv]; am = s_am[wv]; }
+      }
     }
-    if ((tid & 63) == 0) { s_mx[tid >> 6] = mx; s_am[tid >> 6] = am; }
-    __syncthreads();
     if (tid == 0) {
-      for (int wv = 1; wv < NT / 64; ++wv)
-        if (s_mx[wv] > mx || (s_mx[wv] == mx && s_am[wv] < am)) { mx = s_mx[wv]; am = s_am[wv]; }
       p.tokens[(size_t)b * p.Ti + step + 1] = am;
       p.selfmask[(size_t)b * p.mask_ld + step + 1] = am == 0 ? 1 : 0;
       if ((long long)am == eos) p.eos_seen[b] = 1;
@@ -330,16 +341,19 @@ int skf_decode_fused_launch(const SkfDecodeFused& p, hipStream_t st) {
   const int dh = p.d / p.H;
   const size_t smem = skf_decode_fused_lds_bytes(p);
   SkfProfScope ps(st, "decode_position", 0.0, 0.0);
-#define SKF_DF(DHV, AWV)                                                                                             \
+#define SKF_DF(DHV, AWV, SMV)                                                                                        \
   {                                                                                                                  \
-    SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_position_kernel<DHV, AWV>),                      \
+    SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_position_kernel<DHV, AWV, SMV>),                 \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024)); /* per launch: per-device attribute */ \
-    hipLaunchKernelGGL((decode_position_kernel<DHV, AWV>), dim3(p.B), dim3(NT), smem, st, p);                        \
+    hipLaunchKernelGGL((decode_position_kernel<DHV, AWV, SMV>), dim3(p.B), dim3(NT), smem, st, p);                   \
   }
-  if (p.attn) {
-    if (dh == 16) SKF_DF(16, true) else if (dh == 32) SKF_DF(32, true) else SKF_DF(64, true)
+  if (p.sample) {                  // (no attention-weight output with sampling: nothing asks for it)
+    if (p.attn || !p.tokens || !p.stream_ids) { skf_set_error("%s: sampling needs token mode, stream ids and no attention output", __func__); return SKF_EINVAL; }
+    if (dh == 16) SKF_DF(16, false, true) else if (dh == 32) SKF_DF(32, false, true) else SKF_DF(64, false, true)
+  } else if (p.attn) {
+    if (dh == 16) SKF_DF(16, true, false) else if (dh == 32) SKF_DF(32, true, false) else SKF_DF(64, true, false)
   } else {
-    if (dh == 16) SKF_DF(16, false) else if (dh == 32) SKF_DF(32, false) else SKF_DF(64, false)
+    if (dh == 16) SKF_DF(16, false, false) else if (dh == 32) SKF_DF(32, false, false) else SKF_DF(64, false, false)
   }
 #undef SKF_DF
   SKF_LAUNCH_CHECK();

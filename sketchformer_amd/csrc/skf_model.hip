@@ -442,7 +442,7 @@ Plan build_plan(const SkfConfig& c) {
   P.dc_x[0] = b.take(B * d * f); P.dc_x[1] = b.take(B * d * f); P.dc_q = b.take(B * d * f); P.dc_o = b.take(B * d * f);
   P.dc_z = b.take(B * d * f); P.dc_out1 = b.take(B * d * f); P.dc_out2 = b.take(B * d * f); P.dc_h = b.take(B * F * f);
   P.dc_logits = b.take(B * Vout * f); P.dc_stats = b.take(B * 2 * f); P.dc_mask = b.take(B * (L + 1));
-  P.dc_flags = b.take((B + 16) * sizeof(int)); P.dc_limit = b.take(B * sizeof(int));
+  P.dc_flags = b.take((B + 16) * sizeof(int)); P.dc_limit = b.take(2 * B * sizeof(int));   // [B] key limits, [B] stream ids of a sampled decode
   P.dc_tok = b.take(B * (L + 1) * 8); P.dc_cont = b.take(B * (L + 1) * 5 * f); P.dc_kvnew = b.take(B * 2 * d * f);
   P.dc_dyn = b.take(64);
   P.live_len = b.take(B * sizeof(int));
@@ -475,6 +475,7 @@ struct SkfModel {
   void* state = nullptr;
   hipGraphExec_t g_fb = nullptr, g_opt = nullptr, g_dec = nullptr;   // g_dec: one greedy-decode step
   long long dec_dyn_host[2] = {0, 0};
+  std::vector<int> dec_stream_host;  // stream ids of a sampled decode on their way to the device
   float g_opt_scale = 0.f;
   // weight-gradient GEMMs run on a side stream, off the dgrad critical path
   hipStream_t side = nullptr;
@@ -1533,8 +1534,11 @@ int run_backward(SkfModel* M, hipStream_t s) {
 //   cached K/V of pre_decoder ; LN ; FFN ; LN                               (transformer.py:245-262)
 //   logits of position i -> argmax / stroke-5 row -> appended                (sketchformer.py:285-301)
 // attn (optional): the softmax rows of every position, (2N, B, H, max_steps, Le) - see skf_model_greedy_decode_attn.
+// smp (optional, token mode, checked by the caller): the tokens are drawn (skf_model_sample_decode) with the streams stream_ids_host
+// (B ints, null = 0 .. B-1); only the selection differs, and the layer-by-layer steps are then issued eagerly.
 int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
-                      long long eos, int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s) {
+                      long long eos, int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s,
+                      const SkfSampling* smp = nullptr, const int* stream_ids_host = nullptr) {
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
   const Plan& P = M->plan;
@@ -1570,6 +1574,13 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
     limit = M->at<int>(P.dc_limit);
     if (expected_len_host) SKF_HIP(hipMemcpyAsync(limit, expected_len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
     else SKF_HIP(hipMemsetAsync(limit, 0xff, (size_t)B * sizeof(int), s));        // -1: nattn = step + 1
+  }
+  int* stream_ids = nullptr;
+  if (smp) {
+    stream_ids = M->at<int>(P.dc_limit) + B;
+    M->dec_stream_host.resize(B);
+    for (int b = 0; b < B; ++b) M->dec_stream_host[b] = stream_ids_host ? stream_ids_host[b] : b;
+    SKF_HIP(hipMemcpyAsync(stream_ids, M->dec_stream_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
   }
   // pre_decoder and the cross-attention K/V of every layer: once
   if (bott)
@@ -1624,6 +1635,9 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
     SKF_TRY(dense_fwd(M, L.out, x, B, logits, 0, s));
     if (c.continuous)
       return skf_decode_select_continuous(logits, Vout, B, 0, 0, cont, Ti, selfmask, Le + 1, done_step, step_dev, dyn, s);
+    if (smp)
+      return skf_decode_sample_tokens(logits, Vout, B, Vout, 0, 0, 0, tokens, Ti, selfmask, Le + 1, eos_seen, done_step, step_dev, dyn,
+                                      smp, stream_ids, s);
     return skf_decode_select_tokens(logits, Vout, B, Vout, 0, 0, 0, tokens, Ti, selfmask, Le + 1, eos_seen, done_step,
                                     step_dev, dyn, s);
   };
@@ -1653,11 +1667,15 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
     fp.pos = M->pos; fp.tokens = tokens; fp.cont = cont; fp.Ti = Ti; fp.selfmask = selfmask; fp.mask_ld = Le + 1;
     fp.eos_seen = eos_seen; fp.done_step = done_step; fp.step_dev = step_dev; fp.ticket = done_step + 1;
     fp.dyn = dyn; fp.limit = limit; fp.attn = attn; fp.attn_rows = max_steps;
+    if (smp) {
+      fp.sample = 1; fp.temperature = smp->temperature; fp.top_k = smp->top_k; fp.top_p = smp->top_p; fp.seed = smp->seed;
+      fp.stream_ids = stream_ids;
+    }
     SKF_HIP(hipMemsetAsync(fp.ticket, 0, sizeof(int), s));
   }
-  // the captured step has constant arguments and no weight output: with weights requested, the steps are issued eagerly
-  // (g_dec stays as it is)
-  const bool use_graph = !attn;
+  // the captured step has constant arguments, no weight output and the greedy selection: with weights requested or with
+  // sampling, the steps are issued eagerly (g_dec stays as it is)
+  const bool use_graph = !attn && !smp;
   if (fused) {
     for (int i = 0; i < max_steps; ++i) {
       SKF_TRY(skf_decode_fused_launch(fp, s));
@@ -1916,6 +1934,11 @@ extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
   if (cfg->act_dtype == SKF_ACT_BF16) {
     M->bf16 = true;
     M->p16 = build_plan16(*cfg, M->lay);
+    if (!plan16_decode_areas_ok(M->p16)) {
+      delete M;
+      skf_set_error("skf_model_create: internal error, the bf16 plan's decode areas are not distinct allocations");
+      return SKF_EINVAL;
+    }
     // one stream; gradient buckets like the fp32 path (events cannot be recorded for outside waiters in a captured graph)
     if (!cfg->use_graph) {
       M->n_buckets = 2;
@@ -2036,6 +2059,27 @@ extern "C" int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding,
                                (hipStream_t)stream);
   return run_greedy_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights,
                            (hipStream_t)stream);
+}
+
+extern "C" int skf_model_sample_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
+                                       long long sos, long long eos, int max_steps, void* out, int* out_len_host,
+                                       const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream) {
+  SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(out, "null output");
+  SKF_CHECK_ARG(n_valid > 0 && n_valid <= m->cfg.batch, "n_valid must be in [1, batch]");
+  SKF_CHECK_ARG(max_steps > 0 && max_steps <= m->cfg.seq_len, "max_steps must be in [1, seq_len]");
+  SKF_CHECK_ARG(m->cfg.do_reconstruction, "the model was built without a decoder (do_reconstruction = 0)");
+  SKF_TRY(skf_sampling_check(sampling));
+  if (m->cfg.continuous) {
+    skf_set_error("skf_model_sample_decode: a continuous model has a regression head and three pen logits, no categorical distribution "
+                  "over tokens to draw from: sampled decoding is built for token models only");
+    return SKF_EUNSUPPORTED;
+  }
+  if (m->bf16)
+    return run_greedy_decode16(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, nullptr,
+                               (hipStream_t)stream, sampling, stream_ids_host);
+  return run_greedy_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, nullptr,
+                           (hipStream_t)stream, sampling, stream_ids_host);
 }
 
 extern "C" int skf_model_greedy_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,

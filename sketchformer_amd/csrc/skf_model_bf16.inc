@@ -118,7 +118,8 @@ Plan16 build_plan16(const SkfConfig& c, const Layout& L) {
   P.dc_pre = b.take(Me * d * f);
   for (int i = 0; i < N; ++i) { P.dc_kv2.push_back(b.take(Me * 2 * d * f)); P.dc_cache.push_back(b.take(Me * 2 * d * f)); }
   P.dc_tok = b.take(B * (Ls + 1) * 8); P.dc_mask = b.take(B * (Ls + 1)); P.dc_flags = b.take((B + 16) * sizeof(int));
-  P.dc_limit = b.take(B * sizeof(int)); P.dc_dyn = b.take(64);
+  P.dc_limit = b.take(2 * B * sizeof(int));      // [B] key limits, [B] stream ids of a sampled decode
+  P.dc_dyn = b.take(64);
   P.live_len = b.take(B * sizeof(int));
   P.order = b.take(B * sizeof(int));
   P.live1 = b.take(skf_row_blocks_bytes((int)Md, 1)); P.live64 = b.take(skf_row_blocks_bytes((int)Md, 64));
@@ -152,6 +153,18 @@ Plan16 build_plan16(const SkfConfig& c, const Layout& L) {
     reg(hn[1][i], P.dec[i].h, Md, F, F, 1);
   }
   return P;
+}
+
+// The decode scratch of a plan: every area allocated (offset 0 is the staged input, so an area left at its default would alias
+// it), in allocation order, none overlapping the next.  Checked once when a model is created.
+bool plan16_decode_areas_ok(const Plan16& P) {
+  std::vector<size_t> o = {P.dc_pre};
+  for (size_t i = 0; i < P.dc_kv2.size(); ++i) { o.push_back(P.dc_kv2[i]); o.push_back(P.dc_cache[i]); }
+  for (size_t v : {P.dc_tok, P.dc_mask, P.dc_flags, P.dc_limit, P.dc_dyn}) o.push_back(v);
+  if (o[0] == 0 || o.back() + 64 > P.bytes) return false;
+  for (size_t i = 1; i < o.size(); ++i)
+    if (o[i] <= o[i - 1]) return false;
+  return true;
 }
 
 }  // namespace
@@ -480,7 +493,8 @@ int issue_embed_sorts16(SkfModel* M, hipStream_t s) {
 // weights through the one-launch-per-position kernel of the fp32 path (skf_decode_fused.hip); only the embedding it starts
 // from comes from the bf16 encoder.  Token mode (the bf16 path has no continuous mode).
 int run_greedy_decode16(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos, long long eos,
-                        int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s) {
+                        int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s, const SkfSampling* smp = nullptr,
+                        const int* stream_ids_host = nullptr) {
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
   const Plan16& P = M->p16;
@@ -503,6 +517,13 @@ int run_greedy_decode16(SkfModel* M, const float* embedding, const int* expected
     limit = M->at<int>(P.dc_limit);
     if (expected_len_host) SKF_HIP(hipMemcpyAsync(limit, expected_len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
     else SKF_HIP(hipMemsetAsync(limit, 0xff, (size_t)B * sizeof(int), s));
+  }
+  int* stream_ids = nullptr;               // smp: the tokens are drawn (skf_model_sample_decode), streams null = 0 .. B-1
+  if (smp) {
+    stream_ids = M->at<int>(P.dc_limit) + B;
+    M->dec_stream_host.resize(B);
+    for (int b = 0; b < B; ++b) M->dec_stream_host[b] = stream_ids_host ? stream_ids_host[b] : b;
+    SKF_HIP(hipMemcpyAsync(stream_ids, M->dec_stream_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
   }
   // pre_decoder and the cross-attention K|V of every layer, once, in fp32
   float* pre = M->at<float>(P.dc_pre);
@@ -532,6 +553,10 @@ int run_greedy_decode16(SkfModel* M, const float* embedding, const int* expected
   fp.emb_table = M->P(L.dec_emb); fp.pos = M->pos; fp.tokens = tokens; fp.cont = nullptr; fp.Ti = Ti; fp.selfmask = selfmask; fp.mask_ld = Le + 1;
   fp.eos_seen = eos_seen; fp.done_step = done_step; fp.step_dev = step_dev; fp.ticket = done_step + 1; fp.dyn = dyn; fp.limit = limit;
   fp.attn = attn; fp.attn_rows = max_steps;
+  if (smp) {
+    fp.sample = 1; fp.temperature = smp->temperature; fp.top_k = smp->top_k; fp.top_p = smp->top_p; fp.seed = smp->seed;
+    fp.stream_ids = stream_ids;
+  }
   SKF_HIP(hipMemsetAsync(fp.ticket, 0, sizeof(int), s));
   for (int i = 0; i < max_steps; ++i) {
     SKF_TRY(skf_decode_fused_launch(fp, s));

@@ -119,6 +119,20 @@ def logical_shape(e):
     return (e["rows"], e["cols"])
 
 
+SAMPLING_NEEDS_TOKENS = ("sampled decoding is built for token models: a continuous model has a regression head and three pen "
+                         "logits, no categorical distribution over tokens to draw from")
+
+
+def check_sampling(temperature, top_k, top_p):
+    """The parameter ranges of the selection rule (include/skf.h: SkfSampling); ValueError outside them."""
+    if not float(temperature) > 0.0 or float(temperature) == float("inf"):
+        raise ValueError("temperature must be a finite number > 0 (got %r)" % (temperature,))
+    if int(top_k) != top_k or int(top_k) < 0:
+        raise ValueError("top_k must be an integer >= 0, 0 = off (got %r)" % (top_k,))
+    if not 0.0 < float(top_p) <= 1.0:
+        raise ValueError("top_p must be in (0, 1], 1 = off (got %r)" % (top_p,))
+
+
 class TrainEngine:
     """One replica of the sketch-transformer-tf2 train step on one GPU."""
 
@@ -375,6 +389,57 @@ class TrainEngine:
             weights['decoder_layer%d_block1' % (i + 1)] = aw[2 * i, :n_valid, :, :T, :T].cpu().numpy()
             weights['decoder_layer%d_block2' % (i + 1)] = aw[2 * i + 1, :n_valid, :, :T, :].cpu().numpy()
         return res, weights
+
+    def sample_decode(self, embedding=None, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None,
+                      temperature=1.0, top_k=0, top_p=1.0, seed=0, stream_ids=None):
+        """greedy_decode with every token drawn instead of maximised (skf_model_sample_decode; the selection rule is in
+        include/skf.h): logits / temperature, then the top_k largest (0 = off; ties at the threshold all stay), then the nucleus
+        of mass top_p (1 = off), then an inverse-CDF draw in index order with u = skf_sample_uniform(seed, stream_ids[b], position).
+        stream_ids: one integer per batch row (default 0 .. B-1); a row's draws depend on its stream id, not on its batch slot.
+        Token models only (ValueError for a continuous one).  Returns (n_valid, T) int32 incl. the SOS column, like greedy_decode."""
+        B, L = self.cfg.batch, self.cfg.seq_len
+        if self.cfg.continuous:
+            raise ValueError(SAMPLING_NEEDS_TOKENS)
+        check_sampling(temperature, top_k, top_p)
+        n_valid = B if n_valid is None else int(n_valid)
+        max_steps = L if max_steps is None else int(max_steps)
+        emb_ptr, e = None, None
+        if embedding is not None:
+            e = torch.as_tensor(np.asarray(embedding, dtype=np.float32) if not torch.is_tensor(embedding) else embedding)
+            e = e.to(self.device, dtype=torch.float32).contiguous()
+            if self.cfg.lowerdim == 0:
+                want = (B, L, self.cfg.d_model)
+            else:
+                want = (B, self.cfg.lowerdim if self.cfg.attn_version == 2 else self.cfg.d_model)
+            if tuple(e.shape) != want:
+                raise ValueError("embedding must have shape %r" % (want,))
+            emb_ptr = self._p(e)
+        lim = None
+        if expected_len is not None:
+            arr = np.zeros(B, dtype=np.int32)
+            v = np.asarray(expected_len).astype(np.int32).reshape(-1)
+            arr[:len(v)] = v
+            arr[len(v):] = L
+            lim = (C.c_int * B)(*arr.tolist())
+        sid = None
+        if stream_ids is not None:
+            v = np.asarray(stream_ids).astype(np.int64).reshape(-1)
+            if len(v) > B or (v < 0).any() or (v >= 2 ** 31).any():
+                raise ValueError("stream_ids: at most batch=%d integers in [0, 2^31)" % B)
+            arr = np.arange(B, dtype=np.int64)
+            arr[:len(v)] = v
+            sid = (C.c_int * B)(*arr.tolist())
+        smp = _lib.SkfSampling(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xffffffff)
+        out = torch.zeros(B, max_steps + 1, dtype=torch.int64, device=self.device)
+        n_out = C.c_int(0)
+        self._enter()
+        try:
+            _lib.call("skf_model_sample_decode", self.handle, emb_ptr, lim, n_valid, int(sos), int(eos), max_steps,
+                      self._p(out), C.byref(n_out), C.byref(smp), sid, self._stream())
+        finally:
+            self._leave()
+        self.synchronize()
+        return out[:n_valid, :n_out.value].cpu().numpy().astype(np.int32)
 
     class _Staged:
         """What _stage hands to _forward_backward_staged, and to nothing else: device tensors that may still be the CALLER's own."""

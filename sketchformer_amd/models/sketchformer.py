@@ -302,6 +302,86 @@ class Transformer(BaseModel, TransformerMetricsMixin):
             out['class'] = np.concatenate(cls, axis=0).reshape(P, T)
         return out
 
+    def sample_from_embedding(self, emb, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, expected_len=None):
+        """n_samples stochastic reconstructions of every embedding: each token is drawn from softmax(logits / temperature) cut to
+        its top_k largest entries (0 = off) and then to its nucleus of mass top_p (1 = off) - the selection rule of include/skf.h
+        (engine.sample_decode).  emb: any number n of embeddings, a host array or a device tensor (n, E) (it stays where it is).
+        Row i * n_samples + s of the replicated batch is draw s of embedding i and uses random stream i * n_samples + s under
+        `seed`; the rows are decoded in consecutive chunks of batch_size.  Every column after a row's first EOS is set to 0 (what
+        the decoder appends there depends on when the row's chunk stops), so a row depends only on (embedding, parameters, seed,
+        its stream id) - not on n, on batch_size or on its neighbours.  expected_len: per embedding, non-blind models only.
+        Returns {'recon': (n, n_samples, seq_len + 1) int32, 'class': (n, n_samples) int32 or None}."""
+        import torch
+        from .. import engine as _engine
+        if not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        if self.dataset.hps['use_continuous_data']:
+            raise ValueError(_engine.SAMPLING_NEEDS_TOKENS)
+        _engine.check_sampling(temperature, top_k, top_p)
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("n_samples must be >= 1")
+        eng = self.engine
+        if not torch.is_tensor(emb):
+            emb = torch.as_tensor(np.asarray(emb, dtype=np.float32))
+        emb = emb.to(eng.device, dtype=torch.float32)
+        if emb.dim() == (1 if self.hps['lowerdim'] else 2):       # one embedding: (E,) - or (L, d) without a bottleneck
+            emb = emb[None]
+        n = emb.shape[0]
+        if n == 0:
+            raise ValueError("no embedding given")
+        if self.hps['blind_decoder_mask']:
+            expected_len = None                                   # "will be ignored if blind_decoder_mask=True"
+        if expected_len is not None:
+            expected_len = np.repeat(np.asarray(expected_len).astype(np.int32).reshape(-1), n_samples)
+            if len(expected_len) != n * n_samples:
+                raise ValueError("expected_len must hold one length per embedding")
+        B, L = eng.cfg.batch, self.seq_len + 1
+        tok = self.dataset.tokenizer
+        sos = getattr(tok, 'SOS', 0) if tok is not None else 0
+        eos = getattr(tok, 'EOS', 0) if tok is not None else 0
+        rows = emb.repeat_interleave(n_samples, dim=0)            # (n * n_samples, ...) on the device
+        R = rows.shape[0]
+        recon = np.zeros((R, L), dtype=np.int32)
+        cls = []
+        for i in range(0, R, B):
+            chunk = rows[i:i + B]
+            m = chunk.shape[0]
+            if m < B:
+                chunk = torch.cat([chunk, torch.zeros((B - m,) + tuple(chunk.shape[1:]), dtype=torch.float32, device=chunk.device)], dim=0)
+            r = eng.sample_decode(chunk, expected_len=None if expected_len is None else expected_len[i:i + m], n_valid=m,
+                                  sos=sos, eos=eos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                  stream_ids=np.arange(i, i + m))
+            recon[i:i + m, :r.shape[1]] = r
+            if self._has_cls:
+                cls.append(eng.buffer('class_probs')[:m].cpu().numpy().argmax(-1).astype(np.int32))
+        ended = np.cumsum(recon[:, 1:] == eos, axis=1) > 0        # from the first EOS on (column 0 is the start symbol)
+        recon[:, 2:][ended[:, :-1]] = 0
+        return {'recon': recon.reshape(n, n_samples, L),
+                'class': np.concatenate(cls, axis=0).reshape(n, n_samples) if self._has_cls else None}
+
+    def sample(self, inp_seq, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+        """sample_from_embedding on the embeddings of inp_seq (any number of model-ready token sequences); the embeddings go from
+        the encoder to the decoder on the device.  A non-blind model decodes every draw with its input's length as expected_len,
+        like predict."""
+        from .. import engine as _engine
+        if not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        if self.dataset.hps['use_continuous_data']:
+            raise ValueError(_engine.SAMPLING_NEEDS_TOKENS)
+        _engine.check_sampling(temperature, top_k, top_p)
+        if not self.hps['lowerdim']:
+            raise ValueError("sample needs lowerdim > 0 (the bottleneck embedding); without one, pass the (n, L, d) encoder "
+                             "outputs to sample_from_embedding")
+        x = np.asarray(inp_seq)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim == 3 and x.shape[-1] == 1:
+            x = x[..., 0]
+        tlen = None if self.hps['blind_decoder_mask'] else np.sum(x > 0, axis=-1).reshape(-1)
+        return self.sample_from_embedding(self._embed_on_device(x), n_samples=n_samples, temperature=temperature, top_k=top_k,
+                                          top_p=top_p, seed=seed, expected_len=tlen)
+
     def load_reference_checkpoint(self, prefix):
         """Weights (+ Adam slots, optimizer.iterations, current_step) from a checkpoint written by the reference's
         tf.train.Checkpoint(transformer=..., optimizer=...) (core/models.py:321-344), read without TensorFlow."""

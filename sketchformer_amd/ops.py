@@ -539,6 +539,39 @@ def dropout_keep_mask(drop_key, site, rate, n):
     return out.astype(bool)
 
 
+def sample_uniform(seed, stream_id, step):
+    """The uniform of the sampled decode for (seed, stream_id, step): a multiple of 2^-24 in [0, 1) (skf_sample_uniform; host)."""
+    return float(_lib.load().skf_sample_uniform(int(seed) & 0xffffffff, int(stream_id) & 0xffffffff, int(step) & 0xffffffff))
+
+
+def sample_tokens(logits, temperature, top_k, top_p, seed, stream_ids, step):
+    """One token per row of logits (B, V) float32, drawn by the selection rule of include/skf.h (skf_decode_sample_tokens: one
+    workgroup per row): logits / temperature, top_k largest (0 = off), nucleus top_p (1 = off), inverse CDF in index order with
+    u = sample_uniform(seed, stream_ids[b], step).  stream_ids: B integers (sequence or int32 tensor).  -> (B,) int64."""
+    _f32(logits, "logits")
+    if logits.dim() != 2:
+        raise ValueError("logits must be (B, V)")
+    _p(logits)                                                   # CPU tensors: SkfError before anything is allocated
+    B, V = logits.shape
+    dev = logits.device
+    step = int(step)
+    if step < 0:
+        raise ValueError("step must be >= 0")
+    if not torch.is_tensor(stream_ids):
+        stream_ids = torch.tensor([int(v) for v in stream_ids], dtype=torch.int32)
+    stream_ids = stream_ids.to(device=dev, dtype=torch.int32).contiguous()
+    if stream_ids.shape != (B,):
+        raise ValueError("stream_ids must hold one integer per row")
+    smp = _lib.SkfSampling(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xffffffff)
+    # the launch appends to a running (B, step + 2) token image like the decoder's; only its last column is of interest here
+    tokens = torch.zeros(B, step + 2, dtype=torch.int64, device=dev)
+    mask = torch.zeros(B, step + 2, dtype=torch.uint8, device=dev)
+    flags = torch.zeros(B + 1, dtype=torch.int32, device=dev)                    # eos_seen (B), done_step
+    _lib.call("skf_decode_sample_tokens", _p(logits), logits.stride(0), B, V, B, step, -1, _p(tokens), step + 2, _p(mask), step + 2,
+              _p(flags), C.c_void_p(flags.data_ptr() + 4 * B), None, None, C.byref(smp), _p(stream_ids), _stream())
+    return tokens[:, step + 1].clone()
+
+
 def row_normalize(x):
     """(N, d) float32 -> rows divided by max(norm, 1e-12), out of place (skf_row_normalize_f32)."""
     _f32(x, "x")
