@@ -244,7 +244,9 @@ int skf_splitk_reduce_batch(const SkfReduceDesc* descs_dev, int ndesc, int total
  * key_mask: (B, key_mask_ld) bytes, 1 = padded key (create_padding_mask), may be NULL.
  * precision != SKF_PREC_F32: the score products of the dh = 16 kernels run on the bf16 matrix cores with split operands.
  * causal: add the look-ahead mask (needs Lq == Lk).  stats: (B,H,Lq,2) row max of the base-2 logits
- * (q.k * log2(e)/sqrt(dh)) and 1/row-sum - opaque to the caller, kept for the backward.  dh in {16,32,64}. */
+ * (q.k * log2(e)/sqrt(dh)) and 1/row-sum - opaque to the caller, kept for the backward.  dh in {16,32,64}: Lk <= 512 and one
+ * head's operands in 160 KB of LDS, i.e. forward Lk <= 288 at dh 64; backward Lq <= 224 at dh 64 and Lq <= 448 at dh 32 (512 at
+ * dh 16).  Any other dh <= 128: plain fp32 kernels, Lq, Lk <= 1024.  Anything else is refused before a launch. */
 int skf_attention_fwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
                       const unsigned char* key_mask, int key_mask_ld, int causal, int B, int H, int Lq, int Lk, int dh,
                       float* O, int ldo, float* stats, int precision, skf_stream_t stream);
@@ -596,6 +598,8 @@ typedef struct SkfConfig {
    * config) refuses any other value: a binding that is a field short or long is an error, never a read of heap garbage.
    * skf_config_size() returns the library's figure. */
   uint32_t struct_size;
+  /* seq_len <= 512; fp32 path (act_dtype 0) with head size d_model / num_heads = 64: seq_len <= 224, = 32: seq_len <= 448 - what
+   * the attention launches hold in LDS (skf_attention_fwd / skf_attention_bwd); skf_config_validate refuses the rest */
   int32_t batch, seq_len, d_model, num_heads, dff, num_layers;
   int32_t vocab_size, n_classes, lowerdim, attn_version;
   int32_t continuous, blind_decoder_mask, max_pos;

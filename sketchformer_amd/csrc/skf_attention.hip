@@ -647,6 +647,14 @@ int set_smem(K kfn, size_t bytes) {
 }
 
 inline bool mfma_head(int dh) { return dh == 16 || dh == 32 || dh == 64; }
+// S^T on the bf16 pipe follows the Dense arithmetic switch (SKF_ATTN_SPLIT=0 turns it off).  With padded 48-byte plane
+// rows it removed 26 % of the MFMA cycles and changed nothing (the forward is wait-bound: 45 % of the wave cycles parked,
+// and the planes cost the fourth resident workgroup per CU); with unpadded rows (four workgroups per CU again, 2-way bank
+// conflicts) it is 4-11 % faster than the fp32-MFMA tiles: 36.4 / 29.0 / 42.1 vs 39.2 / 30.2 / 47.2 us.
+bool fwd_split(int dh, int precision) {
+  static const bool split_off = skf_knob_is("SKF_ATTN_SPLIT", '0');
+  return dh == 16 && !split_off && precision != SKF_PREC_F32;
+}
 int check_common(const AttnParams& p, int dh) {
   SKF_CHECK_ARG(mfma_head(dh) || skf_attention_any_supported(dh, p.Lq, p.Lk), "head dim must be 16, 32, 64 (MFMA kernels) or any size <= 128 with sequences <= 1024 (fallback)");
   SKF_CHECK_ARG(p.B > 0 && p.H > 0 && p.Lq > 0 && p.Lk > 0, "empty problem");
@@ -656,6 +664,21 @@ int check_common(const AttnParams& p, int dh) {
 }
 
 }  // namespace
+
+// The longest sequences the launches below accept for an MFMA head size (whole 16-row tiles, at most 512): what
+// skf_config_validate holds seq_len against, from the same size functions as the launch checks.
+int skf_attention_fwd_max_lk(int dh, int precision) {
+  int best = 0;
+  for (int L = 16; L <= 512; L += 16)
+    if (fwd_smem(dh, L, fwd_split(dh, precision)) <= kAttnLdsBytes) best = L;
+  return best;
+}
+int skf_attention_bwd_max_lq(int dh) {
+  int best = 0;
+  for (int L = 16; L <= 512; L += 16)
+    if (bwd_smem(dh, L) <= kAttnLdsBytes) best = L;
+  return best;
+}
 
 extern "C" int skf_attention_fwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
                                  const unsigned char* key_mask, int key_mask_ld, int causal, int B, int H, int Lq, int Lk,
@@ -680,14 +703,9 @@ extern "C" int skf_attention_fwd_ordered(const float* Q, int ldq, const float* K
   if (!mfma_head(dh)) return skf_attention_fwd_any(p, dh, (hipStream_t)stream);
   SKF_CHECK_ARG(Lk <= 512, "Lk > 512 not supported");
   SKF_CHECK_ARG((double)Lq * ldo * 4 < 2147483648.0, "one sample's output rows exceed 32-bit byte offsets");
-  // S^T on the bf16 pipe follows the Dense arithmetic switch (SKF_ATTN_SPLIT=0 turns it off).  With padded 48-byte plane
-  // rows it removed 26 % of the MFMA cycles and changed nothing (the forward is wait-bound: 45 % of the wave cycles parked,
-  // and the planes cost the fourth resident workgroup per CU); with unpadded rows (four workgroups per CU again, 2-way bank
-  // conflicts) it is 4-11 % faster than the fp32-MFMA tiles: 36.4 / 29.0 / 42.1 vs 39.2 / 30.2 / 47.2 us.
-  static const bool split_off = skf_knob_is("SKF_ATTN_SPLIT", '0');
-  const bool split = dh == 16 && !split_off && precision != SKF_PREC_F32;
+  const bool split = fwd_split(dh, precision);
   const size_t smem = fwd_smem(dh, Lk, split);
-  SKF_CHECK_ARG(smem <= 160 * 1024, "K/V of one head do not fit in LDS");
+  SKF_CHECK_ARG(smem <= kAttnLdsBytes, "K/V of one head do not fit in LDS");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(B * H), block(256);
 #define SKF_ATTN_FWD(DHV, MT, SP)                               \
@@ -752,6 +770,7 @@ extern "C" int skf_attention_bwd_ordered(const float* Q, int ldq, const float* K
   SKF_CHECK_ARG(Q && K && V && O && dO && stats && dQ && dK && dV, "null operand");
   SKF_CHECK_ARG((lddo & 3) == 0 && (lddq & 3) == 0 && (lddk & 3) == 0 && (lddv & 3) == 0, "row strides must be multiples of 4");
   if (!mfma_head(dh)) return skf_attention_bwd_any(p, dh, (hipStream_t)stream);
+  SKF_CHECK_ARG(Lk <= 512, "Lk > 512 not supported");      // (like the forward, whose statistics every kernel below needs)
   // head size 16 / 32 in the split arithmetic modes: the two-pass kernel on the bf16 matrix cores (skf_attention_bwd2.hip);
   // SKF_PREC_F32 keeps the fp32-MFMA kernel below (SKF_ATTN_BWD2=0 forces it)
   // Head size 16: only the causal (decoder self-attention) calls take it - measured at the cfg-2 shape, the one-pass kernel
@@ -772,7 +791,7 @@ extern "C" int skf_attention_bwd_ordered(const float* Q, int ldq, const float* K
   if (bwd2_shape && precision != SKF_PREC_F32 && !bwd2_off && Lk <= 512 && Lq <= 512)
     return skf_attention_bwd2_launch(p, dh, (hipStream_t)stream);
   const size_t smem = bwd_smem(dh, Lq);
-  SKF_CHECK_ARG(smem <= 160 * 1024, "Q/dO/dQ of one head do not fit in LDS");
+  SKF_CHECK_ARG(smem <= kAttnLdsBytes, "Q/dO/dQ of one head do not fit in LDS");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(B * H), block(256);
 #define SKF_ATTN_BWD(DHV)                                       \

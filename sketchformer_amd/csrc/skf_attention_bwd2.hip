@@ -357,12 +357,18 @@ __global__ __launch_bounds__(256, NC == 1 ? 4 : 2) void attn_bwd2_kernel(AttnPar
 
 }  // namespace
 
+// LDS of one workgroup: six operand planes of R = max(Lq, Lk) rounded up to whole tiles, delta, the key-mask words, two counters
+size_t skf_attention_bwd2_smem(int dh, int Lq, int Lk) {
+  const int nkt = (Lk + 15) >> 4, nqt = (Lq + 15) >> 4;
+  const int R = (nkt > nqt ? nkt : nqt) * 16;
+  return (size_t)6 * R * 2 * dh + (size_t)R * sizeof(float) + 32 * sizeof(unsigned) + 16;
+}
+
 template <int NC>
 static int bwd2_launch(const AttnParams& p, hipStream_t st) {
   const int nkt = (p.Lk + 15) >> 4, nqt = (p.Lq + 15) >> 4;
-  const int R = (nkt > nqt ? nkt : nqt) * 16;
-  const size_t smem = (size_t)6 * R * 32 * NC + (size_t)R * sizeof(float) + 32 * sizeof(unsigned) + 16;
-  SKF_CHECK_ARG(smem <= 160 * 1024, "the operand planes of one head do not fit in LDS");
+  const size_t smem = skf_attention_bwd2_smem(16 * NC, p.Lq, p.Lk);
+  SKF_CHECK_ARG(smem <= kAttnLdsBytes, "the operand planes of one head do not fit in LDS");
   SKF_CHECK_ARG(nkt <= 32 && nqt <= 32, "more than 32 key / query tiles");
   SKF_CHECK_ARG((p.ldq & 3) == 0 && (p.ldk & 3) == 0 && (p.ldv & 3) == 0 && (p.ldo & 3) == 0 && (p.lddo & 3) == 0 && (p.lddq & 3) == 0 &&
                 (p.lddk & 3) == 0 && (p.lddv & 3) == 0, "row strides must be multiples of 4");

@@ -22,6 +22,14 @@ struct AttnParams {
                                   // backward: their tiles are neither staged nor visited, dQ is stored as zeros
 };
 
+// LDS one workgroup may ask for (gfx950: 160 KB per CU): every attention launch holds its operands against it
+constexpr size_t kAttnLdsBytes = 160 * 1024;
+// longest Lk of the forward / Lq of the one-pass backward that fit for head size 16, 32 or 64 (skf_attention.hip), and the
+// LDS of the two-pass backward (skf_attention_bwd2.hip): skf_config_validate refuses what the launches would refuse
+int skf_attention_fwd_max_lk(int dh, int precision);
+int skf_attention_bwd_max_lq(int dh);
+size_t skf_attention_bwd2_smem(int dh, int Lq, int Lk);
+
 // two-pass backward on the bf16 matrix cores with exactly split fp32 operands (head size 16 or 32); returns SKF_OK after launching
 int skf_attention_bwd2_launch(const AttnParams& p, int dh, hipStream_t st);
 

@@ -11,6 +11,7 @@
 #include <map>
 #include <algorithm>
 #include "skf_common.h"
+#include "skf_attention_params.h"
 #include "skf_decode_fused.h"
 
 // ------------------------------------------------------------------ error plumbing
@@ -1889,6 +1890,17 @@ extern "C" int skf_config_validate(const SkfConfig* c) {
   SKF_CHECK_ARG(c->dropout_rate >= 0.f && c->dropout_rate < 1.f, "dropout_rate out of range");
   SKF_CHECK_ARG(c->seq_len <= 512, "seq_len > 512 not supported");
   SKF_CHECK_ARG(c->act_dtype == SKF_ACT_F32 || c->act_dtype == SKF_ACT_BF16, "act_dtype must be 0 (fp32) or 1 (bf16)");
+  if (c->act_dtype == SKF_ACT_F32 && (dh == 16 || dh == 32 || dh == 64)) {
+    // the fp32 MFMA attention kernels keep one head's K / V (forward) or Q / dO (backward) in LDS: the encoder calls have
+    // Lq = Lk = seq_len, and a model whose first step a launch would refuse is refused here (same size functions)
+    const int fmax = skf_attention_fwd_max_lk(dh, c->gemm_precision), bmax = skf_attention_bwd_max_lq(dh);
+    const bool bwd2 = dh == 32 && c->gemm_precision != SKF_PREC_F32 && c->seq_len <= 256;     // (the two-pass kernel's own footprint)
+    if (c->seq_len > fmax || c->seq_len > bmax || (bwd2 && skf_attention_bwd2_smem(dh, c->seq_len, c->seq_len) > kAttnLdsBytes)) {
+      skf_set_error("head size %d: seq_len %d does not fit the fp32 attention kernels (forward: at most %d keys, backward: at most %d query rows)",
+                    dh, c->seq_len, fmax, bmax);
+      return SKF_EUNSUPPORTED;
+    }
+  }
   if (c->act_dtype == SKF_ACT_BF16) {
     // the bf16 path is built for the default structure of the model (what BASELINE cfg 5 trains)
     if (c->continuous || c->attn_version != 1 || c->lowerdim <= 0 || !c->do_classification || !c->do_reconstruction ||

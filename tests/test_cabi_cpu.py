@@ -284,6 +284,36 @@ def test_unsupported_configs_fail_loudly(lib):
         engine.make_config(batch=4, lr_scheduler="step-decay")
 
 
+@pytest.mark.parametrize("d_model,num_heads,precision,longest", [
+    (512, 8, None, 224),       # head size 64: the one-pass backward holds Q / dO of 224 rows (the forward would take 288 keys)
+    (512, 8, 0, 224),
+    (256, 8, None, 448),       # head size 32: two-pass backward up to 256, then the one-pass kernel up to 448 rows
+    (256, 8, 0, 448),
+    (128, 8, None, 512),       # head size 16 fits at the longest sequence the model takes
+    (128, 8, 0, 512),
+    (96, 8, None, 512),        # head size 12: the plain kernels of skf_generic.hip take 1024 positions
+])
+def test_fp32_sequence_limits_of_the_attention_launches_are_refused_at_validate(lib, d_model, num_heads, precision, longest):
+    """skf_attention_fwd / skf_attention_bwd keep one head's operands in LDS and refuse what does not fit; skf_config_validate
+    holds seq_len against the same size functions (hand arithmetic from fwd_smem / bwd_smem of skf_attention.hip: 160 KB hold
+    288 key rows forward and 224 query rows backward at head size 64, 448 query rows backward at head size 32, 512 at 16), so
+    such a model is refused when it is configured and not inside its first step.  The bf16 path streams its keys: unaffected."""
+    from sketchformer_amd import engine
+    mk = lambda L, **kw: engine.make_config(batch=4, seq_len=L, d_model=d_model, num_heads=num_heads, gemm_precision=precision, **kw)
+    assert lib.skf_config_validate(C.byref(mk(longest))) == 0, lib.skf_last_error()
+    assert lib.skf_config_validate(C.byref(mk(longest - 15))) == 0
+    if longest < 512:
+        dh = d_model // num_heads
+        assert lib.skf_config_validate(C.byref(mk(longest + 1))) == -2
+        msg = lib.skf_last_error().decode()
+        assert "head size %d" % dh in msg and "%d query rows" % longest in msg and "%d keys" % (288 if dh == 64 else 512) in msg, msg
+        assert lib.skf_config_validate(C.byref(mk(512))) == -2
+    else:
+        assert lib.skf_config_validate(C.byref(mk(513))) == -1          # the model's own limit
+    if d_model == 512:
+        assert lib.skf_config_validate(C.byref(mk(512, act_dtype="bf16", vocab_size=1004))) == 0, lib.skf_last_error()
+
+
 def test_continuous_layout_names_match_oracle(lib):
     import oracle
     from sketchformer_amd import engine

@@ -514,6 +514,33 @@ def test_any_width_and_head_size(kw, rate, blind):
     assert np.isfinite(eng.step_metrics()["total_loss"])
 
 
+@pytest.mark.parametrize("num_heads", [4, 2], ids=["dh16", "dh32"])
+def test_sequences_above_208_positions(num_heads):
+    """seq_len 225 = 15 key tiles: past the 13 tiles (208 positions) every other model test stays under, where head size 16 leaves
+    attn_fwd<16,13,true> / skf_attention_bwd3 for the 32-tile forward and the one-pass backward (head size 32: the 32-tile forward,
+    attn_bwd2).  B = 8: the step's own row-block lists, live lengths and sample order ride along.  A padded batch with one short
+    row; losses and every gradient against the oracle under the bars of test_any_width_and_head_size."""
+    B = 8
+    eng, ocfg = _mk(B, rate=0.0, seq_len=225, d_model=64, num_heads=num_heads, num_layers=1)
+    x, y = synthetic.token_batch(B, ocfg.seq_len, ocfg.vocab_size, ocfg.n_classes, seed=23, full=True)     # rows reach the 15th tile
+    x[1, 6:] = 0
+    x[3, 100:] = 0
+    x[5, 210:] = 0
+    P = {k: v.astype(np.float64) for k, v in eng.state_dict_numpy().items()}
+    eng.forward_backward(x, None, y)
+    torch.cuda.synchronize()
+    losses, out, G = oracle.loss_and_grads(P, ocfg, x, x, y)
+    m = eng.step_metrics()
+    for k in ("recon_loss", "class_loss", "total_loss"):
+        assert abs(m[k] - losses[k]) < 1e-5 * max(1.0, abs(losses[k])), (k, m[k], losses[k])
+    got = eng.state_dict_numpy("grads")
+    floor = 1e-3 * np.median([np.abs(G[k]).max() for k in G])
+    rel = {k: np.abs(got[k].astype(np.float64) - G[k]).max() / max(np.abs(G[k]).max(), floor) for k in G if not k.endswith("wk/bias")}
+    worst = max((v, k) for k, v in rel.items())
+    assert worst[0] < 1e-3, worst
+    assert np.median(list(rel.values())) < 5e-5
+
+
 def test_host_batches_are_staged_before_the_step_reads_them():
     """train_step on HOST arrays that differ from step to step, with the caller's stream kept busy so that the host-to-device
     copies land late: the step must be ordered behind them (round 3: a single stream hand-over per step was first taken BEFORE
