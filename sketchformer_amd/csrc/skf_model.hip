@@ -301,6 +301,49 @@ struct Bump {
   size_t take(size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
 };
 
+// Scratch of the KV-cached reconstruction (run_decode), the same for both plans.  All fp32: the decoder of a bf16 model runs on the
+// master weights.
+struct DecodeAreas {
+  size_t pre = 0;                 // own_cross plans only (bf16): the expanded embedding (B, L, d) ...
+  std::vector<size_t> kv2;        // ... and the per-layer cross K|V (B, L, 2d); the fp32 plan decodes from its training buffers
+  std::vector<size_t> cache;      // per-layer self-attention K|V of the positions so far (B, L, 2d)
+  size_t img = 0;                 // the running output, (B, L + 1) tokens or stroke-5 rows: the step has constant arguments
+  size_t mask = 0, flags = 0;     // self-attention padding mask (B, L + 1); [B] eos seen, done step, ticket
+  size_t limit = 0;               // [B] key limits of the cross attention, then [B] stream ids of a sampled decode
+  size_t dyn = 0;                 // per-call scalars + the step index
+};
+
+DecodeAreas take_decode_areas(Bump& b, const SkfConfig& c, bool own_cross) {
+  DecodeAreas A;
+  const size_t B = c.batch, L = c.seq_len, d = c.d_model, f = sizeof(float);
+  if (own_cross) A.pre = b.take(B * L * d * f);
+  for (int i = 0; i < c.num_layers; ++i) {
+    if (own_cross) A.kv2.push_back(b.take(B * L * 2 * d * f));
+    A.cache.push_back(b.take(B * L * 2 * d * f));
+  }
+  A.img = b.take(B * (L + 1) * (c.continuous ? 5 * f : 8));
+  A.mask = b.take(B * (L + 1)); A.flags = b.take((B + 16) * sizeof(int));
+  A.limit = b.take(2 * B * sizeof(int));
+  A.dyn = b.take(64);
+  return A;
+}
+
+// Every area allocated (offset 0 is the staged input, so an area left at its default would alias it), in allocation order, none
+// overlapping the next, inside the plan.  Checked once when a model is created.
+bool decode_areas_ok(const DecodeAreas& A, size_t plan_bytes) {
+  std::vector<size_t> o;
+  if (!A.kv2.empty()) o.push_back(A.pre);
+  for (size_t i = 0; i < A.cache.size(); ++i) {
+    if (!A.kv2.empty()) o.push_back(A.kv2[i]);
+    o.push_back(A.cache[i]);
+  }
+  for (size_t v : {A.img, A.mask, A.flags, A.limit, A.dyn}) o.push_back(v);
+  if (o[0] == 0 || o.back() + 64 > plan_bytes || (!A.kv2.empty() && A.kv2.size() != A.cache.size())) return false;
+  for (size_t i = 1; i < o.size(); ++i)
+    if (o[i] <= o[i - 1]) return false;
+  return true;
+}
+
 struct EncAct { size_t x_in, qkv, o, z1, st1, astats, x1, h, z2, st2, x2, hbits, img[2], img_o, img_qkv, img_of; };   // img: pre-split ffn weight images (forward, backward); img_o: Wo^T; img_qkv: this layer's Wqkv (read by the PREVIOUS layer's feed-forward launch)
 struct DecAct { size_t x_in, qkv, o1, z1, st1, astats1, out1, q2, kv2, o2, astats2, z2, st2, out2, h, z3, st3, out3, hbits, img[2], img_o1, img_o2, img_qkv, img_o2f, img_o1f, img_q2, img_q2t; };
 
@@ -326,11 +369,10 @@ struct Plan {
   size_t slab_arena, slab_arena_bytes, descs, n_wgrads;   // deferred split-K reduction (eager path)
   size_t ln_part, ln_part_stride;                          // per-LayerNorm dgamma|dbeta partials [5N][g][2d], reduced in the same batch
   size_t bott_part = 0;                                    // expander / pooling gradient partials (see build_plan)
-  // KV-cached greedy decode (inference): per-layer self-attention K|V cache (B, L, 2d) + one-row-per-sample step buffers
-  std::vector<size_t> dc_cache;
-  size_t dc_x[2], dc_q, dc_o, dc_z, dc_out1, dc_out2, dc_h, dc_logits, dc_stats, dc_mask, dc_flags, dc_limit;
-  size_t dc_tok, dc_cont, dc_kvnew, dc_dyn;
-  size_t live_len = 0, live16 = 0, live32 = 0;   // decoder-side live rows of the step (token mode): per-sample count, block lists   // internal (B, L+1) output image, newest K|V rows, per-call scalars + step index
+  // KV-cached decode (inference): the shared areas + the one-row-per-sample buffers of the layer-by-layer step (newest K|V rows last)
+  DecodeAreas dca;
+  size_t dc_x[2], dc_q, dc_o, dc_z, dc_out1, dc_out2, dc_h, dc_logits, dc_stats, dc_kvnew;
+  size_t live_len = 0, live16 = 0, live32 = 0;   // decoder-side live rows of the step (token mode): per-sample count, block lists
 };
 
 size_t wgrad_ws(int in, int out, int rows) {
@@ -439,13 +481,10 @@ Plan build_plan(const SkfConfig& c) {
     P.emb_sort_bytes = (skf_embed_sort_workspace_bytes((int)B, (int)L, c.vocab_size) + 255) & ~(size_t)255;
     P.emb_sort[0] = b.take(P.emb_sort_bytes); P.emb_sort[1] = b.take(P.emb_sort_bytes);
   }
-  for (int i = 0; i < c.num_layers; ++i) P.dc_cache.push_back(b.take(B * L * 2 * d * f));
+  P.dca = take_decode_areas(b, c, false);          // (pre_decoder and the cross K|V are the training buffers P.pre / P.dec[l].kv2)
   P.dc_x[0] = b.take(B * d * f); P.dc_x[1] = b.take(B * d * f); P.dc_q = b.take(B * d * f); P.dc_o = b.take(B * d * f);
   P.dc_z = b.take(B * d * f); P.dc_out1 = b.take(B * d * f); P.dc_out2 = b.take(B * d * f); P.dc_h = b.take(B * F * f);
-  P.dc_logits = b.take(B * Vout * f); P.dc_stats = b.take(B * 2 * f); P.dc_mask = b.take(B * (L + 1));
-  P.dc_flags = b.take((B + 16) * sizeof(int)); P.dc_limit = b.take(2 * B * sizeof(int));   // [B] key limits, [B] stream ids of a sampled decode
-  P.dc_tok = b.take(B * (L + 1) * 8); P.dc_cont = b.take(B * (L + 1) * 5 * f); P.dc_kvnew = b.take(B * 2 * d * f);
-  P.dc_dyn = b.take(64);
+  P.dc_logits = b.take(B * Vout * f); P.dc_stats = b.take(B * 2 * f); P.dc_kvnew = b.take(B * 2 * d * f);
   P.live_len = b.take(B * sizeof(int));
   P.order = b.take(B * sizeof(int));
   P.live16 = b.take(skf_row_blocks_bytes(B * (L - 1), 16)); P.live32 = b.take(skf_row_blocks_bytes(B * (L - 1), 32));
@@ -525,7 +564,12 @@ struct SkfModel {
     }
     return events[next_event++];
   }
-  std::map<std::string, std::pair<size_t, std::pair<int, int>>> named;
+  // the activations a caller may look at by name (skf_model_buffer / skf_model_buffer_info): filled by register_buffers(16)
+  struct Named { size_t off; int rows, cols, ld, bf16; };
+  std::map<std::string, Named> named;
+  void reg(const std::string& name, size_t off, size_t rows, size_t cols, size_t ld, int is_bf16) {
+    named[name] = {off, (int)rows, (int)cols, (int)ld, is_bf16};
+  }
 
   template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
   float* P(size_t off) const { return params + off; }
@@ -1537,71 +1581,112 @@ int run_backward(SkfModel* M, hipStream_t s) {
 // attn (optional): the softmax rows of every position, (2N, B, H, max_steps, Le) - see skf_model_greedy_decode_attn.
 // smp (optional, token mode, checked by the caller): the tokens are drawn (skf_model_sample_decode) with the streams stream_ids_host
 // (B ints, null = 0 .. B-1); only the selection differs, and the layer-by-layer steps are then issued eagerly.
-int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
-                      long long eos, int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s,
-                      const SkfSampling* smp = nullptr, const int* stream_ids_host = nullptr) {
+//
+// A bf16-trained model decodes the same way, in fp32 on the MASTER weights (only the embedding it starts from comes from the bf16
+// encoder), and only through the one-launch-per-position kernel.  What differs between the two plans is in the view below.
+struct DecodeView {
+  const DecodeAreas* areas = nullptr;
+  float* emb = nullptr;             // (B, E) bottleneck embedding the expander reads; null without a bottleneck
+  float* pre = nullptr;             // (B, L, E) pre_decoder: written by the expander, or a copy of the caller's (B, L, d) encoder output
+  float* enc_out = nullptr;         // no bottleneck: pre_decoder when the caller passes no embedding of its own
+  std::vector<float*> kv2, cache;   // per layer: cross K|V of pre_decoder, self K|V of the positions so far
+  int kv2_precision = 0;            // arithmetic of the cross K|V projection
+  bool classify = false;            // also run the class head on the embedding (classify_from_embedding)
+  bool layerwise = false;           // the plan has the layer-by-layer step's buffers; else the one-launch kernel or nothing
+};
+
+DecodeView decode_view(SkfModel* M) {
+  const SkfConfig& c = M->cfg;
+  const int N = c.num_layers;
+  DecodeView V;
+  V.areas = M->bf16 ? &M->p16.dca : &M->plan.dca;
+  for (int l = 0; l < N; ++l) V.cache.push_back(M->at<float>(V.areas->cache[l]));
+  if (M->bf16) {        // (skf_config_validate: a bf16 model has a bottleneck of width d)
+    V.emb = M->at<float>(M->p16.emb); V.pre = M->at<float>(V.areas->pre);
+    for (int l = 0; l < N; ++l) V.kv2.push_back(M->at<float>(V.areas->kv2[l]));
+    V.kv2_precision = SKF_PREC_BF16X6;
+    return V;
+  }
+  const Plan& P = M->plan;
+  V.emb = has_bott(c) ? M->at<float>(P.emb) : nullptr;
+  V.pre = M->at<float>(P.pre); V.enc_out = M->at<float>(P.enc[N - 1].x2);
+  for (int l = 0; l < N; ++l) V.kv2.push_back(M->at<float>(P.dec[l].kv2));
+  V.kv2_precision = c.gemm_precision;
+  V.classify = has_cls(c);
+  V.layerwise = true;
+  return V;
+}
+
+int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+               long long eos, int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s,
+               const SkfSampling* smp = nullptr, const int* stream_ids_host = nullptr) {
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
-  const Plan& P = M->plan;
+  const Plan& P = M->plan;                             // (the layer-by-layer step and the class head: fp32 plan only)
+  const DecodeView V = decode_view(M);
+  const DecodeAreas& A = *V.areas;
   const int B = c.batch, Le = c.seq_len, d = c.d_model, H = c.num_heads, dh = d / H, N = c.num_layers, F = c.dff;
   const int T = max_steps + 1;                         // columns of the output buffer
   const int Vout = c.continuous ? 5 : c.vocab_size;
-  (void)F;
-  const bool bott = has_bott(c);
-  float* enc_out = M->at<float>(P.enc[N - 1].x2);
+  if (!V.layerwise)
+    SKF_CHECK_ARG(skf_decode_fused_supported(d, H, F, Le, N, Vout), "greedy decode of a bf16 model needs the one-launch decoder (d <= 512, <= 8 layers)");
   // the embedding is (B, E) with a bottleneck, else the whole encoder output (B, L, d) = pre_decoder itself
-  const float* pre = bott ? M->at<float>(P.pre) : enc_out;
-  if (bott) {
-    if (embedding && embedding != M->at<float>(P.emb))
-      SKF_HIP(hipMemcpyAsync(M->at<float>(P.emb), embedding, (size_t)B * L.E * sizeof(float), hipMemcpyDeviceToDevice, s));
-  } else if (embedding && embedding != enc_out) {
-    SKF_HIP(hipMemcpyAsync(M->at<float>(P.pre), embedding, (size_t)B * Le * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-    pre = M->at<float>(P.pre);
+  const float* pre = V.pre;
+  if (V.emb) {
+    if (embedding && embedding != V.emb)
+      SKF_HIP(hipMemcpyAsync(V.emb, embedding, (size_t)B * L.E * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else if (embedding && embedding != V.enc_out) {
+    SKF_HIP(hipMemcpyAsync(V.pre, embedding, (size_t)B * Le * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else {
+    pre = V.enc_out;
   }
-  int* eos_seen = M->at<int>(P.dc_flags);
+  int* eos_seen = M->at<int>(A.flags);
   int* done_step = eos_seen + B;
-  long long* dyn = M->at<long long>(P.dc_dyn);          // [0] n_valid, [1] eos  (read by the selection kernel)
+  long long* dyn = M->at<long long>(A.dyn);             // [0] n_valid, [1] eos  (read by the selection kernel)
   int* step_dev = reinterpret_cast<int*>(dyn + 4);      // index of the position being decoded
-  unsigned char* selfmask = M->at<unsigned char>(P.dc_mask);
+  unsigned char* selfmask = M->at<unsigned char>(A.mask);
   // the running output lives in an internal (B, Le+1) image so that the captured step has constant arguments
   const int Ti = Le + 1;
-  long long* tokens = c.continuous ? nullptr : M->at<long long>(P.dc_tok);
-  float* cont = c.continuous ? M->at<float>(P.dc_cont) : nullptr;
+  long long* tokens = c.continuous ? nullptr : M->at<long long>(A.img);
+  float* cont = c.continuous ? M->at<float>(A.img) : nullptr;
   SKF_TRY(skf_decode_init(tokens, Ti, cont, Ti, selfmask, Le + 1, eos_seen, done_step, B, sos, step_dev, s));
   M->dec_dyn_host[0] = n_valid; M->dec_dyn_host[1] = eos;
   SKF_HIP(hipMemcpyAsync(dyn, M->dec_dyn_host, 2 * sizeof(long long), hipMemcpyHostToDevice, s));
   int* limit = nullptr;                                  // per-sample key limit of the cross attention (non-blind only)
   if (!c.blind_decoder_mask) {
-    limit = M->at<int>(P.dc_limit);
+    limit = M->at<int>(A.limit);
     if (expected_len_host) SKF_HIP(hipMemcpyAsync(limit, expected_len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
     else SKF_HIP(hipMemsetAsync(limit, 0xff, (size_t)B * sizeof(int), s));        // -1: nattn = step + 1
   }
   int* stream_ids = nullptr;
   if (smp) {
-    stream_ids = M->at<int>(P.dc_limit) + B;
+    stream_ids = M->at<int>(A.limit) + B;
     M->dec_stream_host.resize(B);
     for (int b = 0; b < B; ++b) M->dec_stream_host[b] = stream_ids_host ? stream_ids_host[b] : b;
     SKF_HIP(hipMemcpyAsync(stream_ids, M->dec_stream_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
   }
   // pre_decoder and the cross-attention K/V of every layer: once
-  if (bott)
-    SKF_TRY(skf_expander_fwd(M->at<float>(P.emb), M->P(L.exp_w), M->P(L.exp_b), B, Le, L.E, M->at<float>(P.pre), s));
-  for (int l = 0; l < N; ++l)
-    SKF_TRY(dense_fwd(M, L.dec[l].mha2.kv, pre, B * Le, M->at<float>(P.dec[l].kv2), 0, s));
-  if (has_cls(c)) {
+  if (V.emb)
+    SKF_TRY(skf_expander_fwd(V.emb, M->P(L.exp_w), M->P(L.exp_b), B, Le, L.E, V.pre, s));
+  for (int l = 0; l < N; ++l) {
+    const DenseP& w = L.dec[l].mha2.kv;
+    SKF_TRY(skf_gemm_f32(1, 0, B * Le, w.out, w.in, pre, w.in, M->P(w.w), w.ld, V.kv2[l], w.out, M->P(w.b), 0, nullptr, 0, 0, 1,
+                         nullptr, 0, nullptr, 0, V.kv2_precision, s));
+  }
+  if (V.classify) {
     SKF_TRY(classify_fwd(M, false, s));                                                       // classify_from_embedding
     SKF_TRY(skf_softmax_ce(M->at<float>(P.cls_logits), c.n_classes, B, c.n_classes, M->at<long long>(P.labels), 1, 1, 0, 0, 0.f,
                            M->at<float>(P.cls_loss), M->at<float>(P.cls_hit), M->at<float>(P.cls_probs), 0, s));
   }
 
-  float* q = M->at<float>(P.dc_q); float* o = M->at<float>(P.dc_o); float* z = M->at<float>(P.dc_z);
-  float* out1 = M->at<float>(P.dc_out1); float* out2 = M->at<float>(P.dc_out2); float* hbuf = M->at<float>(P.dc_h);
-  float* stats = M->at<float>(P.dc_stats); float* logits = M->at<float>(P.dc_logits);
-  float* kvnew = M->at<float>(P.dc_kvnew);
-  // One decode step.  Every argument is the same for every step and every call (the step index, n_valid and eos are
-  // read from device memory), so the ~50 small launches are captured once into a hipGraph and replayed.
+  // One decode step, layer by layer (V.layerwise).  Every argument is the same for every step and every call (the step index,
+  // n_valid and eos are read from device memory), so the ~50 small launches are captured once into a hipGraph and replayed.
   const size_t aw_blk = (size_t)B * H * max_steps * Le;   // one (B, H, max_steps, Le) block of the attention weights
   auto issue_step = [&]() -> int {
+    float* q = M->at<float>(P.dc_q); float* o = M->at<float>(P.dc_o); float* z = M->at<float>(P.dc_z);
+    float* out1 = M->at<float>(P.dc_out1); float* out2 = M->at<float>(P.dc_out2); float* hbuf = M->at<float>(P.dc_h);
+    float* stats = M->at<float>(P.dc_stats); float* logits = M->at<float>(P.dc_logits);
+    float* kvnew = M->at<float>(P.dc_kvnew);
     float* x = M->at<float>(P.dc_x[0]);
     float* xn = M->at<float>(P.dc_x[1]);
     SKF_TRY(skf_decode_embed(tokens, cont, Ti, B, c.continuous ? nullptr : M->P(L.dec_emb), c.vocab_size,
@@ -1609,7 +1694,7 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
                              M->pos, step_dev, x, s));
     for (int l = 0; l < N; ++l) {
       const DecLayerP& w = L.dec[l];
-      float* cache = M->at<float>(P.dc_cache[l]);                       // (B, Le, 2d): K | V of the positions so far
+      float* cache = V.cache[l];                                        // (B, Le, 2d): K | V of the positions so far
       const DenseP wq{w.mha1.qkv.w, w.mha1.qkv.b, d, d, w.mha1.qkv.ld};
       const DenseP wkv{w.mha1.qkv.w + d, w.mha1.qkv.b + d, d, 2 * d, w.mha1.qkv.ld};
       SKF_TRY(dense_fwd_ld(M, wq, x, d, B, q, d, 0, s));
@@ -1620,7 +1705,7 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
                                      max_steps, Le, s));
       SKF_TRY(dense_fwd(M, w.mha1.o, o, B, z, 0, s));
       SKF_TRY(skf_layernorm_residual_fwd(x, z, M->P(w.ln1.g), M->P(w.ln1.b), out1, stats, B, d, 0.f, 0, M->state, s));
-      const float* kv2 = M->at<float>(P.dec[l].kv2);
+      const float* kv2 = V.kv2[l];
       SKF_TRY(dense_fwd(M, w.mha2.q, out1, B, q, 0, s));
       // cross mask (models/sketchformer.py:172,279-283): none when blind, else keys >= nattn (expected length or step+1)
       SKF_TRY(skf_attention_decode_w(q, d, kv2, kv2 + d, 2 * d, (long long)Le * 2 * d, nullptr, 0, limit, 0, B, H, Le, dh, o, d,
@@ -1644,7 +1729,7 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
   };
   // One launch per position (skf_decode_fused.hip) unless SKF_MODEL_DECODE_LAYERWISE (skf_model_set_flags) asks for the layer-by-layer path above
   const bool fused_off = (M->flags & SKF_MODEL_DECODE_LAYERWISE) != 0;
-  const bool fused = !fused_off && skf_decode_fused_supported(d, H, F, Le, N, Vout);
+  const bool fused = !V.layerwise || (!fused_off && skf_decode_fused_supported(d, H, F, Le, N, Vout));
   SkfDecodeFused fp{};
   if (fused) {
     auto dn = [&](const DenseP& w) {
@@ -1660,7 +1745,7 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
       o.qkv = dn(w.mha1.qkv); o.o = dn(w.mha1.o); o.q2 = dn(w.mha2.q); o.o2 = dn(w.mha2.o); o.f1 = dn(w.f1); o.f2 = dn(w.f2);
       o.ln1_g = M->P(w.ln1.g); o.ln1_b = M->P(w.ln1.b); o.ln2_g = M->P(w.ln2.g); o.ln2_b = M->P(w.ln2.b);
       o.ln3_g = M->P(w.ln3.g); o.ln3_b = M->P(w.ln3.b);
-      o.cache = M->at<float>(P.dc_cache[l]); o.kv2 = M->at<float>(P.dec[l].kv2);
+      o.cache = V.cache[l]; o.kv2 = V.kv2[l];
     }
     fp.out = dn(L.out);
     fp.emb_table = c.continuous ? nullptr : M->P(L.dec_emb);
@@ -1676,25 +1761,7 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
   }
   // the captured step has constant arguments, no weight output and the greedy selection: with weights requested or with
   // sampling, the steps are issued eagerly (g_dec stays as it is)
-  const bool use_graph = !attn && !smp;
-  if (fused) {
-    for (int i = 0; i < max_steps; ++i) {
-      SKF_TRY(skf_decode_fused_launch(fp, s));
-      if ((i & 7) == 7 || i + 1 == max_steps) {
-        int done = -1;
-        SKF_HIP(hipMemcpyAsync(&done, done_step, sizeof(int), hipMemcpyDeviceToHost, s));
-        SKF_HIP(hipStreamSynchronize(s));
-        if (done >= 0 || i + 1 == max_steps) {
-          const int ncols = (done >= 0 ? done + 1 : i + 1) + 1;
-          if (out_len_host) *out_len_host = ncols;
-          const size_t esz = c.continuous ? 5 * sizeof(float) : sizeof(long long);
-          SKF_HIP(hipMemcpy2DAsync(out, (size_t)T * esz, c.continuous ? (const void*)cont : (const void*)tokens, (size_t)Ti * esz,
-                                   (size_t)ncols * esz, B, hipMemcpyDeviceToDevice, s));
-          return SKF_OK;
-        }
-      }
-    }
-  }
+  const bool use_graph = !fused && !attn && !smp;
   if (use_graph && !M->g_dec) {
     hipGraph_t graph = nullptr;
     SKF_HIP(hipStreamSynchronize(s));        // nothing of the setup above may end up inside the captured step
@@ -1707,10 +1774,15 @@ int run_greedy_decode(SkfModel* M, const float* embedding, const int* expected_l
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) { skf_set_error("hipGraphInstantiate (decode step): %s", hipGetErrorString(e)); M->g_dec = nullptr; return SKF_EHIP; }
   }
+  auto issue_position = [&]() -> int {
+    if (fused) return skf_decode_fused_launch(fp, s);
+    if (!use_graph) return issue_step();
+    SKF_HIP(hipGraphLaunch(M->g_dec, s));
+    return SKF_OK;
+  };
   int done = -1, steps_run = 0;
   for (int i = 0; i < max_steps; ++i) {
-    if (use_graph) SKF_HIP(hipGraphLaunch(M->g_dec, s));
-    else SKF_TRY(issue_step());
+    SKF_TRY(issue_position());
     steps_run = i + 1;
     if ((i & 7) == 7 || i + 1 == max_steps) {            // the reference syncs every token; every 8th is enough here
       SKF_HIP(hipMemcpyAsync(&done, done_step, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1737,9 +1809,11 @@ int prologue(SkfModel* M, hipStream_t s) {
 // must not leave it set for the next call on the model, whose batch has other live rows.
 inline void reset_live_rows(SkfModel* M) { M->live16 = M->live32 = nullptr; M->live_rows = 0; }
 
-int stage_inputs(SkfModel* M, const void* inp, const void* tar, int tar_ld, const long long* labels, hipStream_t s) {
+// Where a plan keeps the staged batch; masks: the two padding masks the staging launch may write as well (fp32 plan), or none
+struct StageAreas { size_t inp, tar, labels; bool masks; size_t enc_mask, dec_mask; };
+
+int stage_inputs(SkfModel* M, const StageAreas& P, const void* inp, const void* tar, int tar_ld, const long long* labels, hipStream_t s) {
   const SkfConfig& c = M->cfg;
-  const Plan& P = M->plan;
   reset_live_rows(M);
   M->lists_built = false;
   M->pre_ready = M->masks_ready = nullptr;
@@ -1749,7 +1823,7 @@ int stage_inputs(SkfModel* M, const void* inp, const void* tar, int tar_ld, cons
   const size_t src_row = c.continuous ? (size_t)tar_ld * 5 * sizeof(float) : (size_t)tar_ld * 8;
   // one launch for the three copies (skf_rowops.hip); operands that are not 4-byte aligned take the copy engine below
   // token mode: the two padding masks are written by the same launch (forward_preamble then skips its mask launches)
-  const bool masks = !c.continuous && tar_ld >= c.seq_len;
+  const bool masks = P.masks && !c.continuous && tar_ld >= c.seq_len;
   const int rc = skf_stage_inputs_launch(inp, M->at<char>(P.inp), tar, M->at<char>(P.tar), row, src_row, row < src_row ? row : src_row, c.batch,
                                          labels, M->at<char>(P.labels), s, masks ? M->at<unsigned char>(P.enc_mask) : nullptr,
                                          masks ? M->at<unsigned char>(P.dec_mask) : nullptr, masks ? c.seq_len : 0);
@@ -1936,6 +2010,32 @@ extern "C" size_t skf_model_workspace_bytes(const SkfConfig* cfg) {
   return build_plan(*cfg).bytes;
 }
 
+namespace {
+void register_buffers(SkfModel* M) {
+  const SkfConfig& c = M->cfg;
+  const Plan& P = M->plan;
+  const size_t B = c.batch, L = c.seq_len, Ld = L - 1, d = c.d_model, N = c.num_layers, E = M->lay.E, F = c.dff;
+  const size_t Vout = c.continuous ? 5 : (size_t)c.vocab_size;
+  auto reg = [&](const std::string& n, size_t off, size_t rows, size_t cols) { M->reg(n, off, rows, cols, cols, 0); };
+  reg("logits", P.logits, B * Ld, Vout);
+  reg("class_probs", P.cls_probs, B, c.n_classes);
+  reg("class_logits", P.cls_logits, B, c.n_classes);
+  if (has_bott(c)) reg("embedding", P.emb, B, E);
+  else reg("embedding", P.enc[N - 1].x2, B * L, d);              // no bottleneck: the encoder output (models/sketchformer.py:158-159)
+  reg("enc_output", P.enc[N - 1].x2, B * L, d);
+  reg("dec_output", P.dec[N - 1].out3, B * Ld, d);
+  reg("pre_decoder", has_bott(c) ? P.pre : P.enc[N - 1].x2, B * L, E);
+  reg("bottleneck_attn", P.pool_a, B, L);
+  // the FFN hidden activations relu(x W1 + b1): parity tests read the ReLU branch taken on the device from them
+  for (size_t i = 0; i < N; ++i) {
+    reg("encoder/layer" + std::to_string(i) + "/ffn_h", P.enc[i].h, B * L, F);
+    if (do_recon(c)) reg("decoder/layer" + std::to_string(i) + "/ffn_h", P.dec[i].h, B * Ld, F);
+  }
+  reg("enc_embed_out", P.enc[0].x_in, B * L, d);
+  reg("dec_embed_out", P.dec[0].x_in, B * Ld, d);
+}
+}  // namespace
+
 extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
   SKF_CHECK_ARG(out, "null out");
   int rc = skf_config_validate(cfg);
@@ -1946,11 +2046,17 @@ extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
   if (cfg->act_dtype == SKF_ACT_BF16) {
     M->bf16 = true;
     M->p16 = build_plan16(*cfg, M->lay);
-    if (!plan16_decode_areas_ok(M->p16)) {
-      delete M;
-      skf_set_error("skf_model_create: internal error, the bf16 plan's decode areas are not distinct allocations");
-      return SKF_EINVAL;
-    }
+    register_buffers16(M);
+  } else {
+    M->plan = build_plan(*cfg);
+    register_buffers(M);
+  }
+  if (!decode_areas_ok(M->bf16 ? M->p16.dca : M->plan.dca, M->bf16 ? M->p16.bytes : M->plan.bytes)) {
+    skf_set_error("skf_model_create: internal error, the %s plan's decode areas are not distinct allocations", M->bf16 ? "bf16" : "fp32");
+    delete M;
+    return SKF_EINVAL;
+  }
+  if (M->bf16) {
     // one stream; gradient buckets like the fp32 path (events cannot be recorded for outside waiters in a captured graph)
     if (!cfg->use_graph) {
       M->n_buckets = 2;
@@ -1959,31 +2065,6 @@ extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
     *out = M;
     return SKF_OK;
   }
-  M->plan = build_plan(*cfg);
-  const Plan& P = M->plan;
-  const int B = cfg->batch, L = cfg->seq_len, Ld = L - 1, d = cfg->d_model, N = cfg->num_layers;
-  auto reg = [&](const char* n, size_t off, int r, int c) { M->named[n] = {off, {r, c}}; };
-  reg("logits", P.logits, B * Ld, cfg->continuous ? 5 : cfg->vocab_size);
-  reg("class_probs", P.cls_probs, B, cfg->n_classes);
-  reg("class_logits", P.cls_logits, B, cfg->n_classes);
-  if (has_bott(*cfg)) reg("embedding", P.emb, B, M->lay.E);
-  else reg("embedding", P.enc[N - 1].x2, B * L, d);              // no bottleneck: the encoder output (models/sketchformer.py:158-159)
-  reg("enc_output", P.enc[N - 1].x2, B * L, d);
-  reg("dec_output", P.dec[N - 1].out3, B * Ld, d);
-  reg("pre_decoder", has_bott(*cfg) ? P.pre : P.enc[N - 1].x2, B * L, M->lay.E);
-  reg("bottleneck_attn", P.pool_a, B, L);
-  // the FFN hidden activations relu(x W1 + b1): parity tests read the ReLU branch taken on the device from them
-  static char hnames[2][64][24];
-  for (int i = 0; i < N && i < 64; ++i) {
-    snprintf(hnames[0][i], sizeof(hnames[0][i]), "encoder/layer%d/ffn_h", i);
-    reg(hnames[0][i], P.enc[i].h, B * L, cfg->dff);
-    if (do_recon(*cfg)) {
-      snprintf(hnames[1][i], sizeof(hnames[1][i]), "decoder/layer%d/ffn_h", i);
-      reg(hnames[1][i], P.dec[i].h, B * Ld, cfg->dff);
-    }
-  }
-  reg("enc_embed_out", P.enc[0].x_in, B * L, d);
-  reg("dec_embed_out", P.dec[0].x_in, B * Ld, d);
   // measured on MI355X: eager launches + a wgrad side stream beat hipGraph replay (graph nodes of different
   // streams do not overlap, 7.50 vs 7.72 ms/step), so the side stream is only used on the eager path
   // (round 5: use_graph = 2 captures the two-stream step - capture_or_run)
@@ -2030,68 +2111,79 @@ extern "C" int skf_model_bind(SkfModel* m, float* params, float* grads, float* a
   return SKF_OK;
 }
 
+namespace {
+// The batch into the plan's staging areas, with the `inputs_staged` event behind the copies (stage_with_event).  A bf16 model first makes
+// sure its weight-image table is there, and its forward writes the padding masks itself.
+int stage_batch(SkfModel* m, const void* inp, const void* tar, int tar_ld, const long long* labels, hipStream_t s) {
+  return stage_with_event(m, s, [&]() -> int {
+    if (!m->bf16) {
+      const Plan& P = m->plan;
+      return stage_inputs(m, {P.inp, P.tar, P.labels, true, P.enc_mask, P.dec_mask}, inp, tar, tar_ld, labels, s);
+    }
+    const Plan16& P = m->p16;
+    SKF_TRY(ensure_cast_table16(m, s));
+    return stage_inputs(m, {P.inp, P.tar, P.labels, false, 0, 0}, inp, tar, tar_ld, labels, s);
+  });
+}
+}  // namespace
+
 extern "C" int skf_model_forward(SkfModel* m, const void* inp, const void* tar, int tar_ld, int training,
                                  skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
   hipStream_t s = (hipStream_t)stream;
-  if (m->bf16) {
-    SKF_TRY(stage_with_event(m, s, [&]() { return stage_inputs16(m, inp, tar, tar_ld, nullptr, s); }));
-    if (training) SKF_TRY(prologue(m, s));
-    return run_forward16(m, training != 0, false, s);
-  }
-  SKF_TRY(stage_with_event(m, s, [&]() { return stage_inputs(m, inp, tar, tar_ld, nullptr, s); }));
+  SKF_TRY(stage_batch(m, inp, tar, tar_ld, nullptr, s));
   if (training) SKF_TRY(prologue(m, s));
-  return run_forward(m, training != 0, false, s);
+  return m->bf16 ? run_forward16(m, training != 0, false, s) : run_forward(m, training != 0, false, s);
 }
 
 extern "C" int skf_model_encode(SkfModel* m, const void* inp, skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
   hipStream_t s = (hipStream_t)stream;
-  if (m->bf16) {
-    SKF_TRY(stage_with_event(m, s, [&]() { return stage_inputs16(m, inp, inp, m->cfg.seq_len, nullptr, s); }));
-    return run_forward16(m, false, false, s, true);
-  }
-  SKF_TRY(stage_with_event(m, s, [&]() { return stage_inputs(m, inp, inp, m->cfg.seq_len, nullptr, s); }));
-  return run_forward(m, false, false, s, true);
+  SKF_TRY(stage_batch(m, inp, inp, m->cfg.seq_len, nullptr, s));
+  return m->bf16 ? run_forward16(m, false, false, s, true) : run_forward(m, false, false, s, true);
 }
+
+namespace {
+// The three reconstruction entries.  `entry` names the caller in the error text; sampled: skf_model_sample_decode (tokens are drawn).
+int decode_entry(const char* entry, SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                 long long eos, int max_steps, void* out, int* out_len_host, float* attn_weights, bool sampled,
+                 const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream) {
+#define SKF_ENTRY_CHECK(cond, msg) \
+  do { if (!(cond)) { skf_set_error("%s: %s (%s)", entry, msg, #cond); return SKF_EINVAL; } } while (0)
+  SKF_ENTRY_CHECK(m && m->ws, "model not bound");
+  SKF_ENTRY_CHECK(out, "null output");
+  SKF_ENTRY_CHECK(n_valid > 0 && n_valid <= m->cfg.batch, "n_valid must be in [1, batch]");
+  SKF_ENTRY_CHECK(max_steps > 0 && max_steps <= m->cfg.seq_len, "max_steps must be in [1, seq_len]");
+  SKF_ENTRY_CHECK(m->cfg.do_reconstruction, "the model was built without a decoder (do_reconstruction = 0)");
+  SKF_ENTRY_CHECK(!attn_weights || m->cfg.blind_decoder_mask || expected_len_host,
+                  "attention weights of a non-blind decoder need expected_len (with nattn = i + 1 the cached rows differ from the "
+                  "reference's last pass)");
+#undef SKF_ENTRY_CHECK
+  if (sampled) {
+    SKF_TRY(skf_sampling_check(sampling));
+    if (m->cfg.continuous) {
+      skf_set_error("skf_model_sample_decode: a continuous model has a regression head and three pen logits, no categorical distribution "
+                    "over tokens to draw from: sampled decoding is built for token models only");
+      return SKF_EUNSUPPORTED;
+    }
+  }
+  return run_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights, (hipStream_t)stream,
+                    sampled ? sampling : nullptr, stream_ids_host);
+}
+}  // namespace
 
 extern "C" int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
                                             long long sos, long long eos, int max_steps, void* out, int* out_len_host,
                                             float* attn_weights, skf_stream_t stream) {
-  SKF_CHECK_ARG(m && m->ws, "model not bound");
-  SKF_CHECK_ARG(out, "null output");
-  SKF_CHECK_ARG(n_valid > 0 && n_valid <= m->cfg.batch, "n_valid must be in [1, batch]");
-  SKF_CHECK_ARG(max_steps > 0 && max_steps <= m->cfg.seq_len, "max_steps must be in [1, seq_len]");
-  SKF_CHECK_ARG(m->cfg.do_reconstruction, "the model was built without a decoder (do_reconstruction = 0)");
-  SKF_CHECK_ARG(!attn_weights || m->cfg.blind_decoder_mask || expected_len_host,
-                "attention weights of a non-blind decoder need expected_len (with nattn = i + 1 the cached rows differ from the "
-                "reference's last pass)");
-  if (m->bf16)
-    return run_greedy_decode16(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights,
-                               (hipStream_t)stream);
-  return run_greedy_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights,
-                           (hipStream_t)stream);
+  return decode_entry(__func__, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights, false,
+                      nullptr, nullptr, stream);
 }
 
 extern "C" int skf_model_sample_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
                                        long long sos, long long eos, int max_steps, void* out, int* out_len_host,
                                        const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream) {
-  SKF_CHECK_ARG(m && m->ws, "model not bound");
-  SKF_CHECK_ARG(out, "null output");
-  SKF_CHECK_ARG(n_valid > 0 && n_valid <= m->cfg.batch, "n_valid must be in [1, batch]");
-  SKF_CHECK_ARG(max_steps > 0 && max_steps <= m->cfg.seq_len, "max_steps must be in [1, seq_len]");
-  SKF_CHECK_ARG(m->cfg.do_reconstruction, "the model was built without a decoder (do_reconstruction = 0)");
-  SKF_TRY(skf_sampling_check(sampling));
-  if (m->cfg.continuous) {
-    skf_set_error("skf_model_sample_decode: a continuous model has a regression head and three pen logits, no categorical distribution "
-                  "over tokens to draw from: sampled decoding is built for token models only");
-    return SKF_EUNSUPPORTED;
-  }
-  if (m->bf16)
-    return run_greedy_decode16(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, nullptr,
-                               (hipStream_t)stream, sampling, stream_ids_host);
-  return run_greedy_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, nullptr,
-                           (hipStream_t)stream, sampling, stream_ids_host);
+  return decode_entry(__func__, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, nullptr, true, sampling,
+                      stream_ids_host, stream);
 }
 
 extern "C" int skf_model_greedy_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
@@ -2143,8 +2235,8 @@ extern "C" int skf_model_forward_backward(SkfModel* m, const void* inp, const vo
   SKF_CHECK_ARG(m && m->ws, "model not bound");
   SKF_CHECK_ARG(labels, "null labels");
   hipStream_t s = (hipStream_t)stream;
+  SKF_TRY(stage_batch(m, inp, tar, tar_ld, labels, s));
   if (m->bf16) {
-    SKF_TRY(stage_with_event(m, s, [&]() { return stage_inputs16(m, inp, tar, tar_ld, labels, s); }));
     return capture_or_run(m, &m->g_fb, s, [&]() -> int {
       SKF_TRY(prologue(m, s));
       SKF_TRY(issue_embed_sorts16(m, s));
@@ -2152,7 +2244,6 @@ extern "C" int skf_model_forward_backward(SkfModel* m, const void* inp, const vo
       return run_backward16(m, s);
     });
   }
-  SKF_TRY(stage_with_event(m, s, [&]() { return stage_inputs(m, inp, tar, tar_ld, labels, s); }));
   return capture_or_run(m, &m->g_fb, s, [&]() -> int {
     SKF_TRY(prologue(m, s));
     SKF_TRY(issue_embed_sorts(m, s));
@@ -2218,36 +2309,26 @@ extern "C" int skf_model_apply_gradients_range(SkfModel* m, size_t offset, size_
 
 extern "C" int skf_model_buffer_info(SkfModel* m, const char* name, void** ptr, int* rows, int* cols, int* ld, int* is_bf16) {
   SKF_CHECK_ARG(m && m->ws && name && ptr && rows && cols && ld && is_bf16, "bad argument");
-  if (m->bf16) {
-    auto it = m->p16.named.find(name);
-    if (it == m->p16.named.end()) { skf_set_error("skf_model_buffer_info: unknown buffer '%s'", name); return SKF_EINVAL; }
-    *ptr = m->ws + it->second.off; *rows = it->second.rows; *cols = it->second.cols; *ld = it->second.ld; *is_bf16 = it->second.bf16;
-    return SKF_OK;
+  auto it = m->named.find(name);
+  if (it == m->named.end()) {
+    skf_set_error("%s: unknown buffer '%s'", m->bf16 ? "skf_model_buffer_info" : "skf_model_buffer", name);
+    return SKF_EINVAL;
   }
-  float* p = nullptr;
-  int rc = skf_model_buffer(m, name, &p, rows, cols);
-  if (rc) return rc;
-  *ptr = p; *ld = *cols; *is_bf16 = 0;
+  const SkfModel::Named& n = it->second;
+  *ptr = m->ws + n.off; *rows = n.rows; *cols = n.cols; *ld = n.ld; *is_bf16 = n.bf16;
   return SKF_OK;
 }
 
 extern "C" int skf_model_buffer(SkfModel* m, const char* name, float** ptr, int* rows, int* cols) {
   SKF_CHECK_ARG(m && m->ws && name && ptr, "bad argument");
-  if (m->bf16) {
-    auto it16 = m->p16.named.find(name);
-    if (it16 == m->p16.named.end() || it16->second.bf16) {
-      skf_set_error("skf_model_buffer: '%s' is not an fp32 buffer of this bf16 model (use skf_model_buffer_info)", name);
-      return SKF_EINVAL;
-    }
-    *ptr = reinterpret_cast<float*>(m->ws + it16->second.off);
-    if (rows) *rows = it16->second.rows;
-    if (cols) *cols = it16->second.cols;
-    return SKF_OK;
-  }
   auto it = m->named.find(name);
+  if (m->bf16 && (it == m->named.end() || it->second.bf16)) {
+    skf_set_error("skf_model_buffer: '%s' is not an fp32 buffer of this bf16 model (use skf_model_buffer_info)", name);
+    return SKF_EINVAL;
+  }
   if (it == m->named.end()) { skf_set_error("skf_model_buffer: unknown buffer '%s'", name); return SKF_EINVAL; }
-  *ptr = m->at<float>(it->second.first);
-  if (rows) *rows = it->second.second.first;
-  if (cols) *cols = it->second.second.second;
+  *ptr = m->at<float>(it->second.off);
+  if (rows) *rows = it->second.rows;
+  if (cols) *cols = it->second.cols;
   return SKF_OK;
 }

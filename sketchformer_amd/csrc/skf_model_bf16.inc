@@ -32,15 +32,11 @@ struct Plan16 {
   // LayerNorm gamma / beta gradients: every LayerNorm backward of the step leaves its [g][2d] partials in its own slab; two
   // batched reductions (decoder side, encoder side = the two gradient buckets) replace 80 small column-sum launches
   size_t ln_slabs = 0, ln_descs = 0; int ln_n = 0, ln_n_dec = 0, ln_blocks_dec = 0, ln_blocks_enc = 0, ln_cursor = 0; bool ln_batched = false;
-  // greedy reconstruction (fp32, on the master weights): expanded embedding, per-layer cross K|V and self K|V caches, running output
-  size_t dc_pre = 0, dc_tok = 0, dc_mask = 0, dc_flags = 0, dc_limit = 0, dc_dyn = 0;
-  std::vector<size_t> dc_kv2, dc_cache;
+  DecodeAreas dca;                                 // greedy / sampled reconstruction (fp32, on the master weights: run_decode)
   size_t order = 0;                                // samples sorted by length (skf_sample_order)
   size_t live_len = 0, live1 = 0, live64 = 0;      // live decoder rows of the step (skf_row_blocks.hip): row list, 64-row blocks
   size_t emb_sort[2] = {0, 0}, emb_sort_bytes = 0;
   std::map<size_t, Img16> img;          // keyed by DenseP.w (offset of the fp32 kernel in the flat buffer)
-  struct Named { size_t off; int rows, cols, ld, bf16; };
-  std::map<std::string, Named> named;
 };
 
 namespace {
@@ -115,11 +111,7 @@ Plan16 build_plan16(const SkfConfig& c, const Layout& L) {
   P.cast_descs_bytes = 256 * sizeof(SkfCastDesc); P.cast_descs = b.take(P.cast_descs_bytes);
   P.ln_n = 5 * (int)c.num_layers; P.ln_n_dec = 3 * (int)c.num_layers;
   P.ln_slabs = b.take((size_t)P.ln_n * P.ln_ws_bytes); P.ln_descs = b.take((size_t)P.ln_n * sizeof(SkfReduceDesc));
-  P.dc_pre = b.take(Me * d * f);
-  for (int i = 0; i < N; ++i) { P.dc_kv2.push_back(b.take(Me * 2 * d * f)); P.dc_cache.push_back(b.take(Me * 2 * d * f)); }
-  P.dc_tok = b.take(B * (Ls + 1) * 8); P.dc_mask = b.take(B * (Ls + 1)); P.dc_flags = b.take((B + 16) * sizeof(int));
-  P.dc_limit = b.take(2 * B * sizeof(int));      // [B] key limits, [B] stream ids of a sampled decode
-  P.dc_dyn = b.take(64);
+  P.dca = take_decode_areas(b, c, true);
   P.live_len = b.take(B * sizeof(int));
   P.order = b.take(B * sizeof(int));
   P.live1 = b.take(skf_row_blocks_bytes((int)Md, 1)); P.live64 = b.take(skf_row_blocks_bytes((int)Md, 64));
@@ -134,37 +126,7 @@ Plan16 build_plan16(const SkfConfig& c, const Layout& L) {
   }
   add_img(P, b, L.bott_w); add_img(P, b, L.out);
   P.bytes = b.off;
-  auto reg = [&](const char* n, size_t off, size_t r, size_t cc, size_t ld, int bf) { P.named[n] = {off, (int)r, (int)cc, (int)ld, bf}; };
-  reg("logits", P.logits, Md, c.vocab_size, P.ld_logits, 1);
-  reg("class_probs", P.cls_probs, B, c.n_classes, c.n_classes, 0);
-  reg("class_logits", P.cls_logits, B, c.n_classes, c.n_classes, 0);
-  reg("embedding", P.emb, B, d, d, 0);
-  reg("enc_output", enc_out, Me, d, d, 1);
-  reg("dec_output", dec_out, Md, d, d, 1);
-  reg("pre_decoder", P.pre, Me, d, d, 1);
-  reg("bottleneck_attn", P.pool_a, B, Ls, Ls, 0);
-  reg("enc_embed_out", P.enc[0].x_in, Me, d, d, 1);
-  reg("dec_embed_out", P.dec[0].x_in, Md, d, d, 1);
-  static char hn[2][64][24];
-  for (int i = 0; i < N && i < 64; ++i) {
-    snprintf(hn[0][i], sizeof(hn[0][i]), "encoder/layer%d/ffn_h", i);
-    reg(hn[0][i], P.enc[i].h, Me, F, F, 1);
-    snprintf(hn[1][i], sizeof(hn[1][i]), "decoder/layer%d/ffn_h", i);
-    reg(hn[1][i], P.dec[i].h, Md, F, F, 1);
-  }
   return P;
-}
-
-// The decode scratch of a plan: every area allocated (offset 0 is the staged input, so an area left at its default would alias
-// it), in allocation order, none overlapping the next.  Checked once when a model is created.
-bool plan16_decode_areas_ok(const Plan16& P) {
-  std::vector<size_t> o = {P.dc_pre};
-  for (size_t i = 0; i < P.dc_kv2.size(); ++i) { o.push_back(P.dc_kv2[i]); o.push_back(P.dc_cache[i]); }
-  for (size_t v : {P.dc_tok, P.dc_mask, P.dc_flags, P.dc_limit, P.dc_dyn}) o.push_back(v);
-  if (o[0] == 0 || o.back() + 64 > P.bytes) return false;
-  for (size_t i = 1; i < o.size(); ++i)
-    if (o[i] <= o[i - 1]) return false;
-  return true;
 }
 
 }  // namespace
@@ -173,8 +135,29 @@ namespace {
 
 inline void* w16(SkfModel* M, size_t off) { return M->ws + off; }
 
+// the named activations of the bf16 plan (bf16 unless said otherwise: row pitch `ld` elements)
+void register_buffers16(SkfModel* M) {
+  const SkfConfig& c = M->cfg;
+  const Plan16& P = M->p16;
+  const size_t B = c.batch, Ls = c.seq_len, d = c.d_model, F = c.dff, Me = B * Ls, Md = B * (Ls - 1), N = c.num_layers;
+  M->reg("logits", P.logits, Md, c.vocab_size, P.ld_logits, 1);
+  M->reg("class_probs", P.cls_probs, B, c.n_classes, c.n_classes, 0);
+  M->reg("class_logits", P.cls_logits, B, c.n_classes, c.n_classes, 0);
+  M->reg("embedding", P.emb, B, d, d, 0);
+  M->reg("enc_output", P.enc[N - 1].x2, Me, d, d, 1);
+  M->reg("dec_output", P.dec[N - 1].out3, Md, d, d, 1);
+  M->reg("pre_decoder", P.pre, Me, d, d, 1);
+  M->reg("bottleneck_attn", P.pool_a, B, Ls, Ls, 0);
+  M->reg("enc_embed_out", P.enc[0].x_in, Me, d, d, 1);
+  M->reg("dec_embed_out", P.dec[0].x_in, Md, d, d, 1);
+  for (size_t i = 0; i < N; ++i) {
+    M->reg("encoder/layer" + std::to_string(i) + "/ffn_h", P.enc[i].h, Me, F, F, 1);
+    M->reg("decoder/layer" + std::to_string(i) + "/ffn_h", P.dec[i].h, Md, F, F, 1);
+  }
+}
+
 // descriptor table of the weight images, uploaded once per binding of the parameter buffer (outside any graph capture:
-// stage_inputs16 calls it)
+// every call builds it in front of its staging copies, stage_batch)
 int ensure_cast_table16(SkfModel* M, hipStream_t s) {
   Plan16& P = M->p16;
   if (P.cast_for == M->params && P.tables_ws == M->ws) return SKF_OK;
@@ -227,7 +210,7 @@ int ensure_cast_table16(SkfModel* M, hipStream_t s) {
 int refresh_images16(SkfModel* M, hipStream_t s) {
   SkfProfScope ps(s, "weight_images_bf16", 0.0, 0.0);
   const Plan16& P = M->p16;
-  SKF_CHECK_ARG(P.cast_for == M->params && P.tables_ws == M->ws, "weight-image table not built (stage_inputs16 does it)");
+  SKF_CHECK_ARG(P.cast_for == M->params && P.tables_ws == M->ws, "weight-image table not built (the staging of a call does it)");
   return skf_cast_weight_bf16_batch(reinterpret_cast<const SkfCastDesc*>(M->ws + P.cast_descs), P.cast_n, P.cast_blocks, s);
 }
 // y[rows][w.out] = x . W + b (act)
@@ -487,112 +470,6 @@ int issue_embed_sorts16(SkfModel* M, hipStream_t s) {
   const int B = c.batch, Le = c.seq_len, Ld = c.seq_len - 1, d = c.d_model;
   SKF_TRY(skf_embed_sort(M->at<long long>(P.inp), Le, B, Le, c.vocab_size, M->G(M->lay.enc_emb), d, M->at<char>(P.emb_sort[0]), P.emb_sort_bytes, s));
   return skf_embed_sort(M->at<long long>(P.tar), Le, B, Ld, c.vocab_size, M->G(M->lay.dec_emb), d, M->at<char>(P.emb_sort[1]), P.emb_sort_bytes, s);
-}
-
-// Greedy reconstruction for a bf16-trained model (models/sketchformer.py:255-311): the decoder runs in fp32 on the MASTER
-// weights through the one-launch-per-position kernel of the fp32 path (skf_decode_fused.hip); only the embedding it starts
-// from comes from the bf16 encoder.  Token mode (the bf16 path has no continuous mode).
-int run_greedy_decode16(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos, long long eos,
-                        int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s, const SkfSampling* smp = nullptr,
-                        const int* stream_ids_host = nullptr) {
-  const SkfConfig& c = M->cfg;
-  const Layout& L = M->lay;
-  const Plan16& P = M->p16;
-  const int B = c.batch, Le = c.seq_len, d = c.d_model, H = c.num_heads, N = c.num_layers, F = c.dff, Vout = c.vocab_size;
-  const int T = max_steps + 1, Ti = Le + 1;
-  SKF_CHECK_ARG(skf_decode_fused_supported(d, H, F, Le, N, Vout), "greedy decode of a bf16 model needs the one-launch decoder (d <= 512, <= 8 layers)");
-  float* emb = M->at<float>(P.emb);
-  if (embedding && embedding != emb) SKF_HIP(hipMemcpyAsync(emb, embedding, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-  int* eos_seen = M->at<int>(P.dc_flags);
-  int* done_step = eos_seen + B;
-  long long* dyn = M->at<long long>(P.dc_dyn);
-  int* step_dev = reinterpret_cast<int*>(dyn + 4);
-  unsigned char* selfmask = M->at<unsigned char>(P.dc_mask);
-  long long* tokens = M->at<long long>(P.dc_tok);
-  SKF_TRY(skf_decode_init(tokens, Ti, nullptr, Ti, selfmask, Le + 1, eos_seen, done_step, B, sos, step_dev, s));
-  M->dec_dyn_host[0] = n_valid; M->dec_dyn_host[1] = eos;
-  SKF_HIP(hipMemcpyAsync(dyn, M->dec_dyn_host, 2 * sizeof(long long), hipMemcpyHostToDevice, s));
-  int* limit = nullptr;
-  if (!c.blind_decoder_mask) {
-    limit = M->at<int>(P.dc_limit);
-    if (expected_len_host) SKF_HIP(hipMemcpyAsync(limit, expected_len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    else SKF_HIP(hipMemsetAsync(limit, 0xff, (size_t)B * sizeof(int), s));
-  }
-  int* stream_ids = nullptr;               // smp: the tokens are drawn (skf_model_sample_decode), streams null = 0 .. B-1
-  if (smp) {
-    stream_ids = M->at<int>(P.dc_limit) + B;
-    M->dec_stream_host.resize(B);
-    for (int b = 0; b < B; ++b) M->dec_stream_host[b] = stream_ids_host ? stream_ids_host[b] : b;
-    SKF_HIP(hipMemcpyAsync(stream_ids, M->dec_stream_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-  }
-  // pre_decoder and the cross-attention K|V of every layer, once, in fp32
-  float* pre = M->at<float>(P.dc_pre);
-  SKF_TRY(skf_expander_fwd(emb, M->P(L.exp_w), M->P(L.exp_b), B, Le, d, pre, s));
-  for (int l = 0; l < N; ++l) {
-    const DenseP& w = L.dec[l].mha2.kv;
-    SKF_TRY(skf_gemm_f32(1, 0, B * Le, w.out, w.in, pre, w.in, M->P(w.w), w.ld, M->at<float>(P.dc_kv2[l]), w.out, M->P(w.b), 0, nullptr, 0, 0, 1,
-                         nullptr, 0, nullptr, 0, SKF_PREC_BF16X6, s));
-  }
-  SkfDecodeFused fp{};
-  auto dn = [&](const DenseP& w) {
-    SkfDecDense r{M->P(w.w), M->P(w.b), w.in, w.out, w.ld, 0};
-    r.vec4 = (w.ld & 3) == 0 && (w.out & 3) == 0 && ((uintptr_t)r.w & 15) == 0;
-    return r;
-  };
-  fp.B = B; fp.Le = Le; fp.d = d; fp.H = H; fp.F = F; fp.N = N; fp.Vout = Vout; fp.vocab = c.vocab_size;
-  fp.blind = c.blind_decoder_mask ? 1 : 0; fp.hs_len = F > Vout ? F : Vout;
-  for (int l = 0; l < N; ++l) {
-    const DecLayerP& w = L.dec[l];
-    SkfDecLayer& o = fp.layer[l];
-    o.qkv = dn(w.mha1.qkv); o.o = dn(w.mha1.o); o.q2 = dn(w.mha2.q); o.o2 = dn(w.mha2.o); o.f1 = dn(w.f1); o.f2 = dn(w.f2);
-    o.ln1_g = M->P(w.ln1.g); o.ln1_b = M->P(w.ln1.b); o.ln2_g = M->P(w.ln2.g); o.ln2_b = M->P(w.ln2.b);
-    o.ln3_g = M->P(w.ln3.g); o.ln3_b = M->P(w.ln3.b);
-    o.cache = M->at<float>(P.dc_cache[l]); o.kv2 = M->at<float>(P.dc_kv2[l]);
-  }
-  fp.out = dn(L.out);
-  fp.emb_table = M->P(L.dec_emb); fp.pos = M->pos; fp.tokens = tokens; fp.cont = nullptr; fp.Ti = Ti; fp.selfmask = selfmask; fp.mask_ld = Le + 1;
-  fp.eos_seen = eos_seen; fp.done_step = done_step; fp.step_dev = step_dev; fp.ticket = done_step + 1; fp.dyn = dyn; fp.limit = limit;
-  fp.attn = attn; fp.attn_rows = max_steps;
-  if (smp) {
-    fp.sample = 1; fp.temperature = smp->temperature; fp.top_k = smp->top_k; fp.top_p = smp->top_p; fp.seed = smp->seed;
-    fp.stream_ids = stream_ids;
-  }
-  SKF_HIP(hipMemsetAsync(fp.ticket, 0, sizeof(int), s));
-  for (int i = 0; i < max_steps; ++i) {
-    SKF_TRY(skf_decode_fused_launch(fp, s));
-    if ((i & 7) == 7 || i + 1 == max_steps) {
-      int done = -1;
-      SKF_HIP(hipMemcpyAsync(&done, done_step, sizeof(int), hipMemcpyDeviceToHost, s));
-      SKF_HIP(hipStreamSynchronize(s));
-      if (done >= 0 || i + 1 == max_steps) {
-        const int ncols = (done >= 0 ? done + 1 : i + 1) + 1;
-        if (out_len_host) *out_len_host = ncols;
-        SKF_HIP(hipMemcpy2DAsync(out, (size_t)T * 8, tokens, (size_t)Ti * 8, (size_t)ncols * 8, B, hipMemcpyDeviceToDevice, s));
-        return SKF_OK;
-      }
-    }
-  }
-  return SKF_OK;
-}
-
-int stage_inputs16(SkfModel* M, const void* inp, const void* tar, int tar_ld, const long long* labels, hipStream_t s) {
-  const SkfConfig& c = M->cfg;
-  const Plan16& P = M->p16;
-  M->live16 = M->live32 = nullptr; M->live_rows = 0; M->lists_built = false;
-  SKF_CHECK_ARG(inp && tar, "null input");
-  SKF_TRY(ensure_cast_table16(M, s));
-  const size_t row = (size_t)c.seq_len * 8, src_row = (size_t)tar_ld * 8;
-  {
-    const int rc = skf_stage_inputs_launch(inp, M->at<char>(P.inp), tar, M->at<char>(P.tar), row, src_row, row < src_row ? row : src_row, c.batch,
-                                           labels, M->at<char>(P.labels), s);
-    if (rc != SKF_EUNSUPPORTED) return rc;
-  }
-  SKF_HIP(hipMemcpyAsync(M->at<char>(P.inp), inp, row * c.batch, hipMemcpyDeviceToDevice, s));
-  if (tar_ld == c.seq_len) SKF_HIP(hipMemcpyAsync(M->at<char>(P.tar), tar, row * c.batch, hipMemcpyDeviceToDevice, s));
-  else SKF_HIP(hipMemcpy2DAsync(M->at<char>(P.tar), row, tar, src_row, row < src_row ? row : src_row, c.batch, hipMemcpyDeviceToDevice, s));
-  if (labels) SKF_HIP(hipMemcpyAsync(M->at<char>(P.labels), labels, (size_t)c.batch * 8, hipMemcpyDeviceToDevice, s));
-  else SKF_HIP(hipMemsetAsync(M->at<char>(P.labels), 0, (size_t)c.batch * 8, s));
-  return SKF_OK;
 }
 
 }  // namespace

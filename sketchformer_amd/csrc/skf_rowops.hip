@@ -1196,7 +1196,7 @@ int skf_stage_inputs_launch(const void* inp, void* dinp, const void* tar, void* 
   if (mask_L > 0 && (!emask || !dmask || (size_t)mask_L * 8 > row || (size_t)(mask_L - 1) * 8 > src_row)) mask_L = 0;
   const int total = (int)((row + copy) / 4) * batch + 2 * batch + (mask_L > 0 ? (2 * mask_L - 1) * batch : 0);
   int grid = skf_cdiv(total, 256); if (grid > 512) grid = 512;
-  // tail audit: parked by stage_with_event (skf_model.hip) around stage_inputs / stage_inputs16, which launch nothing behind a successful return
+  // tail audit: parked by stage_with_event (skf_model.hip) around stage_inputs (stage_batch), which launches nothing behind a successful return
   SKF_LAUNCH_TAIL(stage_inputs_kernel, dim3(grid), dim3(256), 0, st, (const unsigned*)inp, (unsigned*)dinp, (const unsigned*)tar,
                      (unsigned*)dtar, (int)(row / 4), (int)(src_row / 4), (int)(copy / 4), batch, (const unsigned*)labels, (unsigned*)dlabels,
                      emask, dmask, mask_L);

@@ -341,49 +341,14 @@ class TrainEngine:
         if with_attn_weights and not self.cfg.blind_decoder_mask and expected_len is None:
             raise ValueError("attention weights of a non-blind decoder need expected_len: with nattn = i + 1 the rows decoded "
                              "earlier were masked differently from the reference's last pass")
-        emb_ptr = None
-        if embedding is not None:
-            e = torch.as_tensor(np.asarray(embedding, dtype=np.float32) if not torch.is_tensor(embedding) else embedding)
-            e = e.to(self.device, dtype=torch.float32).contiguous()
-            if self.cfg.lowerdim == 0:      # no bottleneck: the "embedding" is the encoder output (B, L, d)
-                want = (B, L, self.cfg.d_model)
-            else:                           # SelfAttnV2 projects to lowerdim
-                want = (B, self.cfg.lowerdim if self.cfg.attn_version == 2 else self.cfg.d_model)
-            if tuple(e.shape) != want:
-                raise ValueError("embedding must have shape %r" % (want,))
-            emb_ptr = self._p(e)
-        lim = None
-        if expected_len is not None:
-            arr = np.zeros(B, dtype=np.int32)
-            v = np.asarray(expected_len).astype(np.int32).reshape(-1)
-            arr[:len(v)] = v
-            arr[len(v):] = L
-            lim = (C.c_int * B)(*arr.tolist())
-        if self.cfg.continuous:
-            out = torch.zeros(B, max_steps + 1, 5, dtype=torch.float32, device=self.device)
-        else:
-            out = torch.zeros(B, max_steps + 1, dtype=torch.int64, device=self.device)
-        n_out = C.c_int(0)
         aw = None
         if with_attn_weights:       # every row of a decoded position is written by the kernels: no memset
             aw = torch.empty(2 * self.cfg.num_layers, B, self.cfg.num_heads, max_steps, L, dtype=torch.float32,
                              device=self.device)
-        self._enter()
-        try:
-            if aw is None:
-                _lib.call("skf_model_greedy_decode", self.handle, emb_ptr, lim, n_valid, int(sos), int(eos), max_steps,
-                          self._p(out), C.byref(n_out), self._stream())
-            else:
-                _lib.call("skf_model_greedy_decode_attn", self.handle, emb_ptr, lim, n_valid, int(sos), int(eos), max_steps,
-                          self._p(out), C.byref(n_out), self._p(aw), self._stream())
-        finally:
-            self._leave()
-        self.synchronize()
-        res = out[:n_valid, :n_out.value].cpu().numpy()
-        res = res if self.cfg.continuous else res.astype(np.int32)
         if aw is None:
-            return res
-        T = n_out.value - 1
+            return self._decode_call("skf_model_greedy_decode", embedding, expected_len, n_valid, sos, eos, max_steps)[0]
+        res, n_out = self._decode_call("skf_model_greedy_decode_attn", embedding, expected_len, n_valid, sos, eos, max_steps, self._p(aw))
+        T = n_out - 1
         weights = {}
         for i in range(self.cfg.num_layers):
             weights['decoder_layer%d_block1' % (i + 1)] = aw[2 * i, :n_valid, :, :T, :T].cpu().numpy()
@@ -403,24 +368,6 @@ class TrainEngine:
         check_sampling(temperature, top_k, top_p)
         n_valid = B if n_valid is None else int(n_valid)
         max_steps = L if max_steps is None else int(max_steps)
-        emb_ptr, e = None, None
-        if embedding is not None:
-            e = torch.as_tensor(np.asarray(embedding, dtype=np.float32) if not torch.is_tensor(embedding) else embedding)
-            e = e.to(self.device, dtype=torch.float32).contiguous()
-            if self.cfg.lowerdim == 0:
-                want = (B, L, self.cfg.d_model)
-            else:
-                want = (B, self.cfg.lowerdim if self.cfg.attn_version == 2 else self.cfg.d_model)
-            if tuple(e.shape) != want:
-                raise ValueError("embedding must have shape %r" % (want,))
-            emb_ptr = self._p(e)
-        lim = None
-        if expected_len is not None:
-            arr = np.zeros(B, dtype=np.int32)
-            v = np.asarray(expected_len).astype(np.int32).reshape(-1)
-            arr[:len(v)] = v
-            arr[len(v):] = L
-            lim = (C.c_int * B)(*arr.tolist())
         sid = None
         if stream_ids is not None:
             v = np.asarray(stream_ids).astype(np.int64).reshape(-1)
@@ -430,16 +377,54 @@ class TrainEngine:
             arr[:len(v)] = v
             sid = (C.c_int * B)(*arr.tolist())
         smp = _lib.SkfSampling(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xffffffff)
-        out = torch.zeros(B, max_steps + 1, dtype=torch.int64, device=self.device)
+        return self._decode_call("skf_model_sample_decode", embedding, expected_len, n_valid, sos, eos, max_steps, C.byref(smp), sid)[0]
+
+    def _decode_embedding(self, embedding):
+        """The caller's embedding as a float32 device tensor of the shape the decoder starts from, or None for None."""
+        if embedding is None:
+            return None
+        B, L = self.cfg.batch, self.cfg.seq_len
+        e = torch.as_tensor(np.asarray(embedding, dtype=np.float32) if not torch.is_tensor(embedding) else embedding)
+        e = e.to(self.device, dtype=torch.float32).contiguous()
+        if self.cfg.lowerdim == 0:      # no bottleneck: the "embedding" is the encoder output (B, L, d)
+            want = (B, L, self.cfg.d_model)
+        else:                           # SelfAttnV2 projects to lowerdim
+            want = (B, self.cfg.lowerdim if self.cfg.attn_version == 2 else self.cfg.d_model)
+        if tuple(e.shape) != want:
+            raise ValueError("embedding must have shape %r" % (want,))
+        return e
+
+    def _expected_len(self, expected_len):
+        """One key limit per batch row as c_int[B] (rows past the given ones: seq_len), or None for None."""
+        if expected_len is None:
+            return None
+        B = self.cfg.batch
+        arr = np.zeros(B, dtype=np.int32)
+        v = np.asarray(expected_len).astype(np.int32).reshape(-1)
+        arr[:len(v)] = v
+        arr[len(v):] = self.cfg.seq_len
+        return (C.c_int * B)(*arr.tolist())
+
+    def _decode_call(self, entry, embedding, expected_len, n_valid, sos, eos, max_steps, *extra):
+        """One reconstruction call of the C ABI (``entry``; ``extra``: its arguments between out_len and the stream) ->
+        (the n_valid decoded rows on the host: int32 tokens or float32 stroke-5 rows, their column count)."""
+        B = self.cfg.batch
+        e = self._decode_embedding(embedding)
+        lim = self._expected_len(expected_len)
+        if self.cfg.continuous:
+            out = torch.zeros(B, max_steps + 1, 5, dtype=torch.float32, device=self.device)
+        else:
+            out = torch.zeros(B, max_steps + 1, dtype=torch.int64, device=self.device)
         n_out = C.c_int(0)
         self._enter()
         try:
-            _lib.call("skf_model_sample_decode", self.handle, emb_ptr, lim, n_valid, int(sos), int(eos), max_steps,
-                      self._p(out), C.byref(n_out), C.byref(smp), sid, self._stream())
+            _lib.call(entry, self.handle, None if e is None else self._p(e), lim, n_valid, int(sos), int(eos), max_steps,
+                      self._p(out), C.byref(n_out), *extra, self._stream())
         finally:
             self._leave()
         self.synchronize()
-        return out[:n_valid, :n_out.value].cpu().numpy().astype(np.int32)
+        res = out[:n_valid, :n_out.value].cpu().numpy()
+        return (res if self.cfg.continuous else res.astype(np.int32)), n_out.value
 
     class _Staged:
         """What _stage hands to _forward_backward_staged, and to nothing else: device tensors that may still be the CALLER's own."""

@@ -203,16 +203,13 @@ class Transformer(BaseModel, TransformerMetricsMixin):
             raise ValueError("at most batch_size=%d embeddings per call" % B)
         pad = np.zeros((B,) + emb.shape[1:], dtype=np.float32)
         pad[:n] = emb
-        tok = self.dataset.tokenizer
         if self.hps['blind_decoder_mask']:
             expected_len = None                     # "will be ignored if blind_decoder_mask=True"
         if with_attn_weights and expected_len is None and not self.hps['blind_decoder_mask']:
             raise ValueError("attn_weights of a non-blind decoder need expected_len (with nattn = i + 1 the decoded rows "
                              "were masked differently from the reference's last pass)")
-        res = self.engine.greedy_decode(pad, expected_len=expected_len, n_valid=n,
-                                        sos=getattr(tok, 'SOS', 0) if tok is not None else 0,
-                                        eos=getattr(tok, 'EOS', 0) if tok is not None else 0,
-                                        with_attn_weights=with_attn_weights)
+        sos, eos = self._sos_eos()
+        res = self.engine.greedy_decode(pad, expected_len=expected_len, n_valid=n, sos=sos, eos=eos, with_attn_weights=with_attn_weights)
         recon, weights = res if with_attn_weights else (res, None)
         out = {'recon': recon, 'attn_weights': weights}
         if self._has_cls:
@@ -237,6 +234,32 @@ class Transformer(BaseModel, TransformerMetricsMixin):
             out['recon'] = dec['recon']
             out['attn_weights'] = dec['attn_weights']
         return out
+
+    def _sos_eos(self):
+        """(SOS, EOS) of the dataset's tokenizer; (0, 0) without one."""
+        tok = self.dataset.tokenizer
+        return (getattr(tok, 'SOS', 0), getattr(tok, 'EOS', 0)) if tok is not None else (0, 0)
+
+    def _decode_in_chunks(self, rows, decode):
+        """Reconstructions of any number R of embeddings (device tensor, one per row) in consecutive chunks of batch_size rows.  The
+        last chunk is zero-padded; ``decode(chunk, i, m)`` gets the batch_size rows that start at row i, m of them valid, and
+        returns their (m, T[, 5]) reconstruction, which is zero-padded to seq_len + 1 columns.
+        Returns (recon (R, seq_len + 1[, 5]), class (R,) int32 or None)."""
+        import torch
+        B, L = self.engine.cfg.batch, self.seq_len + 1
+        recon, cls = [], []
+        for i in range(0, rows.shape[0], B):
+            chunk = rows[i:i + B]
+            m = chunk.shape[0]
+            if m < B:
+                chunk = torch.cat([chunk, torch.zeros((B - m,) + tuple(chunk.shape[1:]), dtype=torch.float32, device=chunk.device)], dim=0)
+            r = decode(chunk, i, m)
+            pad = np.zeros((m, L) + r.shape[2:], dtype=r.dtype)
+            pad[:, :r.shape[1]] = r
+            recon.append(pad)
+            if self._has_cls:
+                cls.append(self.engine.buffer('class_probs')[:m].cpu().numpy().argmax(-1).astype(np.int32))
+        return np.concatenate(recon, axis=0), (np.concatenate(cls, axis=0) if self._has_cls else None)
 
     def _embed_on_device(self, x):
         """Bottleneck embeddings of any number of model-ready sequences as ONE device (P, E) float32 tensor: encoded in chunks of
@@ -279,27 +302,12 @@ class Transformer(BaseModel, TransformerMetricsMixin):
         out = {'embedding': z.cpu().numpy(), 'recon': None, 'class': None}
         if not decode:
             return out
-        B, L = self.engine.cfg.batch, self.seq_len + 1
-        tok = self.dataset.tokenizer
-        flat = z.view(P * T, E)
-        recon, cls = [], []
-        for i in range(0, P * T, B):
-            chunk = flat[i:i + B]
-            n = chunk.shape[0]
-            if n < B:
-                chunk = torch.cat([chunk, torch.zeros(B - n, E, dtype=torch.float32, device=z.device)], dim=0)
-            r = self.engine.greedy_decode(chunk, expected_len=None, n_valid=n,
-                                          sos=getattr(tok, 'SOS', 0) if tok is not None else 0,
-                                          eos=getattr(tok, 'EOS', 0) if tok is not None else 0)
-            pad = np.zeros((n, L) + r.shape[2:], dtype=r.dtype)
-            pad[:, :r.shape[1]] = r
-            recon.append(pad)
-            if self._has_cls:
-                cls.append(self.engine.buffer('class_probs')[:n].cpu().numpy().argmax(-1).astype(np.int32))
-        recon = np.concatenate(recon, axis=0)
+        sos, eos = self._sos_eos()
+        recon, cls = self._decode_in_chunks(z.view(P * T, E), lambda chunk, i, m: self.engine.greedy_decode(
+            chunk, expected_len=None, n_valid=m, sos=sos, eos=eos))
         out['recon'] = recon.reshape((P, T) + recon.shape[1:])
-        if self._has_cls:
-            out['class'] = np.concatenate(cls, axis=0).reshape(P, T)
+        if cls is not None:
+            out['class'] = cls.reshape(P, T)
         return out
 
     def sample_from_embedding(self, emb, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0, expected_len=None):
@@ -336,29 +344,14 @@ class Transformer(BaseModel, TransformerMetricsMixin):
             expected_len = np.repeat(np.asarray(expected_len).astype(np.int32).reshape(-1), n_samples)
             if len(expected_len) != n * n_samples:
                 raise ValueError("expected_len must hold one length per embedding")
-        B, L = eng.cfg.batch, self.seq_len + 1
-        tok = self.dataset.tokenizer
-        sos = getattr(tok, 'SOS', 0) if tok is not None else 0
-        eos = getattr(tok, 'EOS', 0) if tok is not None else 0
+        sos, eos = self._sos_eos()
         rows = emb.repeat_interleave(n_samples, dim=0)            # (n * n_samples, ...) on the device
-        R = rows.shape[0]
-        recon = np.zeros((R, L), dtype=np.int32)
-        cls = []
-        for i in range(0, R, B):
-            chunk = rows[i:i + B]
-            m = chunk.shape[0]
-            if m < B:
-                chunk = torch.cat([chunk, torch.zeros((B - m,) + tuple(chunk.shape[1:]), dtype=torch.float32, device=chunk.device)], dim=0)
-            r = eng.sample_decode(chunk, expected_len=None if expected_len is None else expected_len[i:i + m], n_valid=m,
-                                  sos=sos, eos=eos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                                  stream_ids=np.arange(i, i + m))
-            recon[i:i + m, :r.shape[1]] = r
-            if self._has_cls:
-                cls.append(eng.buffer('class_probs')[:m].cpu().numpy().argmax(-1).astype(np.int32))
+        recon, cls = self._decode_in_chunks(rows, lambda chunk, i, m: eng.sample_decode(
+            chunk, expected_len=None if expected_len is None else expected_len[i:i + m], n_valid=m, sos=sos, eos=eos,
+            temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, stream_ids=np.arange(i, i + m)))
         ended = np.cumsum(recon[:, 1:] == eos, axis=1) > 0        # from the first EOS on (column 0 is the start symbol)
         recon[:, 2:][ended[:, :-1]] = 0
-        return {'recon': recon.reshape(n, n_samples, L),
-                'class': np.concatenate(cls, axis=0).reshape(n, n_samples) if self._has_cls else None}
+        return {'recon': recon.reshape(n, n_samples, self.seq_len + 1), 'class': None if cls is None else cls.reshape(n, n_samples)}
 
     def sample(self, inp_seq, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=0):
         """sample_from_embedding on the embeddings of inp_seq (any number of model-ready token sequences); the embeddings go from

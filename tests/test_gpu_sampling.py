@@ -154,6 +154,21 @@ def test_top_k_1_is_greedy_bf16_model():
     assert other.shape[1] != want.shape[1] or not np.array_equal(other, want)
 
 
+def test_top_k_1_is_greedy_nonblind_bf16_model_with_stream_ids():
+    """A non-blind bf16 model with expected_len and stream ids of its own: the key limits and the stream ids are the two halves
+    of one decode area, and both reach the one-launch kernel through the driver the fp32 model uses."""
+    B = 4
+    eng, ocfg = _build(B, blind=False, act_dtype="bf16", **SMALL16)
+    emb, tlen = _inputs(eng, ocfg, B, seed=7)
+    sos, eos = _sos_eos(ocfg)
+    ids = [11, 5, 300, 2]
+    want = eng.greedy_decode(emb, expected_len=tlen, sos=sos, eos=eos)
+    got = eng.sample_decode(emb, expected_len=tlen, sos=sos, eos=eos, top_k=1, seed=4, stream_ids=ids)
+    assert got.dtype == want.dtype and np.array_equal(got, want)
+    again = eng.sample_decode(emb, expected_len=tlen, sos=sos, eos=eos, top_k=1, seed=4, stream_ids=ids)
+    assert np.array_equal(again, got)
+
+
 # ---------------------------------------------------------------- 4. model decode against the oracle, step by step
 def _teacher_forced_logits(P, ocfg, emb, recon, expected_len):
     """the oracle's logits of every position on the device's own prefix: (n, T, V), T = recon length - 1"""

@@ -168,3 +168,14 @@ def test_bf16_plan_keeps_its_decode_areas_apart(lib):
     m = C.c_void_p()
     assert lib.skf_model_create(C.byref(cfg), C.byref(m)) == 0, lib.skf_last_error()
     lib.skf_model_destroy(m)
+
+
+def test_fp32_plan_keeps_its_decode_areas_apart(lib):
+    """The same check runs on the fp32 plan, whose decode areas come from the same allocation (its stream ids, too, are the second
+    half of the key-limit area): an fp32 model that captures its step creates no stream or event, so it is created without a device"""
+    from sketchformer_amd import engine
+    cfg = engine.make_config(batch=4, seq_len=24, d_model=128, num_heads=2, dff=128, num_layers=2, vocab_size=52, n_classes=7,
+                             lowerdim=64, dropout_rate=0.0, use_graph=True)
+    m = C.c_void_p()
+    assert lib.skf_model_create(C.byref(cfg), C.byref(m)) == 0, lib.skf_last_error()
+    lib.skf_model_destroy(m)
