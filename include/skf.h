@@ -473,6 +473,39 @@ int skf_decode_sample_tokens(const float* logits, int ld, int B, int V, int n_va
                              int* done_step, int* step_dev, const long long* dyn, const SkfSampling* sampling,
                              const int* stream_ids, skf_stream_t stream);
 
+/* ---- beam search: the W most likely reconstructions of a sketch ----
+ * A batch of B rows decodes n = B / W sketches: rows g W .. g W + W - 1 are the beams of sketch g (1 <= W <= SKF_BEAM_MAX).
+ * One position is two launches.  The position kernel gives every row its W best (log p, token) pairs of the row's log-softmax
+ * (fp32: one max, one sum of expf in a fixed order), log p descending, then token ascending.  The selection rule of
+ * skf_beam_advance then merges the offers of a sketch:
+ *   a live beam r offers (score[r] + logp[r][k], token[r][k]) for k < W; a finished beam (it has emitted EOS) offers exactly one
+ *   candidate, itself: (score[r], PAD = 0); a beam of score -inf offers nothing finite; NaN ranks as -inf.
+ *   The W best offers survive, ordered by score descending, then parent beam ascending, then token ascending.  Survivor r' writes
+ *   token [r'][step + 1], mask byte (token == 0), its score, the sticky finished flag, its length (the position of its EOS; for a
+ *   live beam the positions emitted so far) and row r' of the next ancestry table.
+ * Ancestry: no K/V row, mask byte or token is ever copied.  (row, position) is written once, at step == position; hypothesis r is
+ *   the list anc[r][0..step] of the rows ("slots") that hold its positions: anc'[r'][0..step] = anc[parent][0..step],
+ *   anc'[r'][step + 1] = r'.  Two tables (2, rows, ancestry_ld): the position `step` reads table step & 1 and writes the other.
+ * Scores are fp32 sums in step order and nothing uses a floating-point atomic: two calls are bit-equal.
+ * skf_beam_advance: one such merge on caller buffers (device): cand_logp / cand_tok (n W, W); scores, finished, lengths (n W),
+ *   updated in place; parent: optional (n W) ints, the parent beam of every survivor.
+ * skf_beam_finish: the final order on caller buffers (device).  The W hypotheses of every sketch are ordered by
+ *   scores / ((5 + lengths) / 6)^length_alpha descending, then beam index ascending; out_scores (n, W) and out_lengths (n, W) are the
+ *   inputs in that order (the raw sums); out_tokens (n, W, T): hypothesis r read through its ancestry row,
+ *   tokens[ancestry[r][j]][j] for j < ncols, zeros from ncols on.  ancestry (n W, ancestry_ld): ONE table. */
+#define SKF_BEAM_MAX 8
+typedef struct SkfBeam {
+  uint32_t struct_size; /* sizeof(SkfBeam) */
+  int32_t beam_width;   /* W in [1, min(SKF_BEAM_MAX, vocab_size, batch)] */
+  float length_alpha;   /* >= 0; final order by score / ((5 + len) / 6)^length_alpha; 0 = the raw sum */
+} SkfBeam;
+int skf_beam_finish(const float* scores, const int* lengths, const int* ancestry, int ancestry_ld, const long long* tokens,
+                    int tok_ld, int n, int beam_width, int ncols, int T, float length_alpha, long long* out_tokens,
+                    float* out_scores, int* out_lengths, skf_stream_t stream);
+int skf_beam_advance(const float* cand_logp, const int* cand_tok, int n, int beam_width, int step, long long eos,
+                     float* scores, int* finished, int* lengths, int* ancestry, int ancestry_ld, long long* tokens,
+                     int tok_ld, unsigned char* selfmask, int mask_ld, int* parent, skf_stream_t stream);
+
 /* ------------------------------------------------------------------ bf16 path (BASELINE cfg 5)
  * bf16 storage + v_mfma_f32_32x32x16_bf16 with fp32 accumulation, fp32 master weights / optimizer state (SkfConfig.act_dtype
  * = SKF_ACT_BF16).  `void*` tensors below are bf16 (2 bytes per element, pitches in elements); parameters, statistics,
@@ -731,6 +764,24 @@ int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int*
 int skf_model_sample_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
                             long long sos, long long eos, int max_steps, void* out, int* out_len_host,
                             const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream);
+/* skf_model_beam_decode: beam-search reconstruction (the rule above) of n = batch / beam_width sketches, token models only.
+ *   embedding: (n, E) device floats [(n, L, d) without a bottleneck], required; it is replicated into the W rows of every sketch on
+ *   the device, and so is expected_len_host (n host ints; required when blind_decoder_mask == 0).  Only the first n_valid <= n
+ *   sketches take part in the stop test: the decode ends at the first position after which every one of their beams is finished.
+ *   out_tokens (n, W, max_steps + 1) int64 [column 0 = SOS, zeros from *out_len_host on], out_scores (n, W) the raw fp32 sums of
+ *   log p, out_lengths (n, W): device buffers, the hypotheses of a sketch ordered by score / ((5 + len) / 6)^length_alpha
+ *   descending, then beam index ascending.  A finished hypothesis carries PADs behind its EOS and keeps its score.
+ *   Always one position launch + one advance launch per position: SKF_MODEL_DECODE_LAYERWISE does not affect it (there are no beams
+ *   on the layer-by-layer path).  Blocking like the greedy entry (stop test every 8 positions).  Keeps no state.
+ *   SKF_EINVAL: a continuous model (its output is one deterministic row, nothing to rank); beam_width outside
+ *   [1, min(8, vocab_size, batch)]; length_alpha < 0 or not finite; a model the one-launch beam kernel does not serve; a non-blind
+ *   model without expected_len_host; n_valid outside [1, n].
+ *   The buffers "decode/tokens" (B, 2 (L + 1)) [int64 image seen as floats] and "decode/ancestry" (B, L + 1) [ints] hold the running
+ *   image and the ancestry table the hypotheses of the last call were gathered through.  They are diagnostics (the tests re-read
+ *   the hypotheses through them) and NOT part of the stable interface: names, shapes and element views may change. */
+int skf_model_beam_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                          long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths,
+                          int* out_len_host, const SkfBeam* beam, skf_stream_t stream);
 /* look up an internal activation by name ("logits", "class_probs", "embedding", "enc_output", ...); skf_model_buffer serves
  * fp32 buffers, skf_model_buffer_info any buffer with its row pitch (elements) and element type (bf16 models keep their
  * activations in bf16) */

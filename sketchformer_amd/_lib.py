@@ -91,6 +91,19 @@ class SkfSampling(C.Structure):
             self.struct_size = C.sizeof(SkfSampling)
 
 
+class SkfBeam(C.Structure):
+    """include/skf.h: struct SkfBeam, field for field (skf_model_beam_decode)."""
+    _fields_ = [("struct_size", C.c_uint32), ("beam_width", C.c_int32), ("length_alpha", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(SkfBeam)
+
+
+BEAM_MAX = 8                                          # SKF_BEAM_MAX
+
+
 class SkfParamEntry(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32),
                 ("row_stride", C.c_int32)]
@@ -245,6 +258,9 @@ SIGNATURES = {
     "skf_model_greedy_decode_attn": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, C.POINTER(_I), _P, _P]),
     "skf_model_sample_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, C.POINTER(_I), C.POINTER(SkfSampling),
                                      C.POINTER(_I), _P]),
+    "skf_beam_finish": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "skf_beam_advance": (_I, [_P, _P, _I, _I, _I, C.c_longlong, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P]),
+    "skf_model_beam_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, _P, _P, C.POINTER(_I), C.POINTER(SkfBeam), _P]),
     "skf_model_apply_gradients": (_I, [_P, _F, _P]),
     "skf_model_buffer": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]),
     "skf_model_buffer_info": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),

@@ -30,9 +30,17 @@ struct SkfDecodeFused {
   // sample != 0 (token mode): the token is drawn by the selection rule of include/skf.h with u = uniform(seed, stream_ids[b], step)
   int sample; float temperature; int top_k; float top_p; unsigned seed;
   const int* stream_ids;                          // (B) device
+  // beam != 0 (token mode, skf_model_beam_decode): beam width W; the first beam_rows = n W rows are at work (the grid).  The
+  // workgroup reads the history of its hypothesis through row b of ancestry table step & 1 and writes its W best (log p, token)
+  // pairs; tokens, flags, ticket and step index belong to beam_advance_kernel (skf_beam.hip)
+  int beam, beam_rows;
+  const int* anc;                                 // (2, B, Le + 1)
+  float* cand_lp; int* cand_tok;                  // (B, W), log p descending, then token ascending
 };
 
 bool skf_decode_fused_supported(int d, int H, int F, int Le, int N, int Vout);
+// the same for the beam instantiation, whose workgroup also keeps the offsets of its history (2 (Le + 1) ints) in LDS
+bool skf_decode_beam_supported(int d, int H, int F, int Le, int N, int Vout);
 int skf_decode_fused_launch(const SkfDecodeFused& p, hipStream_t st);
 
 // SkfSampling as the public entries take it: struct_size, temperature > 0, top_k >= 0, 0 < top_p <= 1 (SKF_EINVAL otherwise)
@@ -44,3 +52,20 @@ int skf_attention_decode_w(const float* Q, int ldq, const float* K, const float*
                            const unsigned char* key_mask, int key_mask_ld, const int* key_limit, int key_limit_all, int B, int H,
                            int Lk, int dh, float* O, int ldo, const int* step_dev, const float* K_new, const float* V_new, int ld_new,
                            int limit_from_step, float* attn, int attn_rows, int attn_ld, hipStream_t stream);
+
+// ---- beam search (skf_beam.hip).  State of n sketches x W beams in rows g W + k of B-row areas.
+struct SkfBeamState {
+  int n, W, B;
+  float* cand_lp; int* cand_tok;                  // (B, W): what the position kernel offers
+  float* scores; int* finished; int* lengths;     // (B): fp32 sum of log p, sticky EOS flag, position of the EOS (else positions emitted)
+  int* anc; int anc_ld;                           // (2, B, anc_ld) ancestry tables
+  long long* tokens; int Ti; unsigned char* selfmask; int mask_ld;
+  int* parent;                                    // optional (B): the parent beam of every survivor (stand-alone entry)
+  int* done_step; int* step_dev; int* ticket; const long long* dyn;      // null in the stand-alone entry: step, n_valid, eos are arguments
+};
+int skf_beam_check(const SkfBeam* b);
+int skf_beam_replicate(void* dst, const void* src, int n, int W, size_t cols_4byte, hipStream_t st);
+int skf_beam_init(const SkfBeamState& s, hipStream_t st);
+int skf_beam_advance_launch(const SkfBeamState& s, int step, int n_valid, long long eos, hipStream_t st);
+int skf_beam_gather(const SkfBeamState& s, int table, int ncols, int T, float alpha, long long* out_tokens, float* out_scores,
+                    int* out_lengths, hipStream_t st);

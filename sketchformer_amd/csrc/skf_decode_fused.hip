@@ -122,10 +122,14 @@ __device__ __forceinline__ void add_ln(const float* a, const float* r, const flo
 // 11 us of this function).  Three phases through LDS: scores[h][j] (dot product folded over the DH/4 adjacent lanes of a
 // head), softmax per head (wave = head), weighted sum of V (partials per key slice, folded in a fixed order).
 // aw non-null: head h's probabilities also go to aw[h * aw_hs + j] (lanes over keys: contiguous stores), zeros from Lk to aw_len.
-template <int DH>
+// INDIRECT (beam search): key j of the hypothesis lives in another row's slot - Kb, Vb and mask are the bases of slot 0, and
+// koff[j] / moff[j] (LDS, 32-bit, made once per position from the ancestry row) are the offsets of its K | V row in floats and of
+// its mask byte; the direct form is the code it was before the beam instantiation existed.
+template <int DH, bool INDIRECT = false>
 __device__ __forceinline__ void attend(const float* q_lds, const float* __restrict__ Kb, const float* __restrict__ Vb, int ld_kv, int Lk,
                        const unsigned char* __restrict__ mask, int limit, int d, int H, float* sc, int LkP, float* part,
-                       float* o_lds, int tid, float* __restrict__ aw, size_t aw_hs, int aw_len) {
+                       float* o_lds, int tid, float* __restrict__ aw, size_t aw_hs, int aw_len, const unsigned* koff = nullptr,
+                       const unsigned* moff = nullptr) {
   const int nc4 = d >> 2, jl = tid / nc4, c4 = tid - jl * nc4, JP = NT / nc4;
   const int h = (4 * c4) / DH;
   const f32x4 q4 = *reinterpret_cast<const f32x4*>(q_lds + 4 * c4);
@@ -139,7 +143,12 @@ __device__ __forceinline__ void attend(const float* q_lds, const float* __restri
 #define SKF_LOAD_ROWS(base, r, j0)                                                                              \
   _Pragma("unroll") for (int u = 0; u < NR; ++u) {                                                              \
     const int j = (j0) + u * JP;                                                                                \
-    r[u] = *reinterpret_cast<const f32x4*>((base) + (size_t)(j < Lk ? j : Lk - 1) * ld_kv + 4 * c4);           \
+    if constexpr (INDIRECT) {                                                                                   \
+      const int jc = j < Lk ? j : Lk - 1;                                                                       \
+      r[u] = *reinterpret_cast<const f32x4*>((base) + koff[jc] + 4 * c4);                                      \
+    } else {                                                                                                    \
+      r[u] = *reinterpret_cast<const f32x4*>((base) + (size_t)(j < Lk ? j : Lk - 1) * ld_kv + 4 * c4);         \
+    }                                                                                                           \
   }
 #define SKF_SCORES(j0)                                                                                          \
   _Pragma("unroll") for (int u = 0; u < NR; ++u) {                                                              \
@@ -147,7 +156,9 @@ __device__ __forceinline__ void attend(const float* q_lds, const float* __restri
     float dot = q4[0] * kv[u][0] + q4[1] * kv[u][1] + q4[2] * kv[u][2] + q4[3] * kv[u][3];                      \
     _Pragma("unroll") for (int o = 1; o < DH / 4; o <<= 1) dot += __shfl_xor(dot, o, 64);                       \
     if (j < Lk && (c4 & (DH / 4 - 1)) == 0) {                                                                   \
-      const bool masked = (mask && mask[j]) || j >= limit;                                                      \
+      bool masked;                                                                                              \
+      if constexpr (INDIRECT) masked = mask[moff[j]] || j >= limit;                                             \
+      else masked = (mask && mask[j]) || j >= limit;                                                            \
       sc[h * LkP + j] = dot / scale_div + (masked ? -1e9f : 0.f);                                               \
     }                                                                                                           \
   }
@@ -198,9 +209,71 @@ __device__ __forceinline__ void attend(const float* q_lds, const float* __restri
   __syncthreads();
 }
 
+// Beam search: the row's log-softmax in place (one max, one sum of expf, both folded in a fixed order) and its W best (log p, token)
+// pairs, log p descending, then token ascending.  NaN ranks as -inf.  W rounds of a workgroup arg-max over the entries behind the
+// previous pick in that order (W <= 8, W <= V).  hs[0..V): the logits, complete and visible; scratch: 32 floats.
+__device__ __forceinline__ void beam_candidates(float* hs, int V, int W, float* __restrict__ cand_lp, int* __restrict__ cand_tok,
+                                                float* scratch, int tid) {
+  float* wv = scratch;                                  // [8] per-wave value
+  int* wj = reinterpret_cast<int*>(scratch + 8);        // [8] per-wave index
+  const int lane = tid & 63, wave = tid >> 6;
+  float m = -INFINITY;
+  for (int j = tid; j < V; j += NT) {
+    float v = hs[j];
+    if (!(v == v)) { v = -INFINITY; hs[j] = v; }
+    m = fmaxf(m, v);
+  }
+  m = wave_max(m);
+  if (lane == 0) wv[wave] = m;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) m = fmaxf(m, wv[w]);
+  float se = 0.f;
+  for (int j = tid; j < V; j += NT) se += expf(hs[j] - m);
+  se = wave_sum(se);
+  __syncthreads();
+  if (lane == 0) wv[wave] = se;
+  __syncthreads();
+  se = 0.f;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) se += wv[w];
+  const float lse = m + logf(se);
+  for (int j = tid; j < V; j += NT) {
+    float lp = hs[j] - lse;
+    if (!(lp == lp)) lp = -INFINITY;                    // a row without a finite maximum has no distribution
+    hs[j] = lp;
+  }
+  float pv = INFINITY;
+  int pj = -1;
+  for (int k = 0; k < W; ++k) {
+    __syncthreads();                                    // hs complete; wv / wj free again
+    float bv = -INFINITY;
+    int bj = 0x7fffffff;
+    for (int j = tid; j < V; j += NT) {
+      const float v = hs[j];
+      const bool behind = v < pv || (v == pv && j > pj);
+      if (behind && (v > bv || (v == bv && j < bj))) { bv = v; bj = j; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64); const int oj = __shfl_xor(bj, o, 64);
+      if (ov > bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
+    }
+    if (lane == 0) { wv[wave] = bv; wj[wave] = bj; }
+    __syncthreads();
+    bv = wv[0]; bj = wj[0];
+#pragma unroll
+    for (int w = 1; w < NT / 64; ++w)
+      if (wv[w] > bv || (wv[w] == bv && wj[w] < bj)) { bv = wv[w]; bj = wj[w]; }
+    if (tid == 0) { cand_lp[k] = bv; cand_tok[k] = bj < V ? bj : 0; }
+    pv = bv; pj = bj;
+  }
+}
+
 // AW: the instantiation that writes the attention weights; the other one is the decoder without that output.
 // SAMPLE: the token is drawn (temperature / top-k / nucleus, skf_sample.h) instead of maximised; what follows the choice is shared.
-template <int DH, bool AW, bool SAMPLE>
+// BEAM: the history is read through the ancestry table and the kernel ends with the row's W best candidates (skf_beam.hip).
+template <int DH, bool AW, bool SAMPLE, bool BEAM = false>
 __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -217,6 +290,18 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   float* sc = red + 16;            // [H][LkP] attention scores / probabilities
   const int LkP = p.Le + 1;
   const int step = *p.step_dev;
+  // BEAM: where positions 0..step of the hypothesis live, as offsets from slot 0: [Le + 1] K | V rows (floats), [Le + 1] mask bytes
+  unsigned* koff = reinterpret_cast<unsigned*>(sc + p.H * LkP);
+  unsigned* moff = koff + LkP;
+  if constexpr (BEAM) {
+    const int* ar = p.anc + ((size_t)(step & 1) * p.B + b) * LkP;
+    for (int j = tid; j <= step; j += NT) {
+      int a = ar[j];
+      a = j == step ? b : (a < 0 ? 0 : (a >= p.B ? p.B - 1 : a));           // the newest row is the workgroup's own
+      koff[j] = ((unsigned)a * (unsigned)p.Le + (unsigned)j) * (unsigned)(2 * d);      // (the launcher checks B Le 2d < 2^32)
+      moff[j] = (unsigned)a * (unsigned)p.mask_ld + (unsigned)j;
+    }
+  }
   const int n_valid = (int)p.dyn[0];
   const long long eos = p.dyn[1];
 
@@ -249,8 +334,12 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
     float* cache = w.cache + (size_t)b * p.Le * 2 * d;             // (Le, 2d): K | V of the positions so far
     for (int c = tid; c < 2 * d; c += NT) cache[(size_t)step * 2 * d + c] = qkv[d + c];
     __syncthreads();               // the appended row is read back below: workgroup-scope visibility of the global stores
-    attend<DH>(qkv, cache, cache + d, 2 * d, step + 1, smask, 0x7fffffff, d, p.H, sc, LkP, part, os, tid,
-               aw ? aw + (size_t)(2 * l) * aw_blk : nullptr, aw_hs, p.Le);
+    if constexpr (BEAM)
+      attend<DH, true>(qkv, w.cache, w.cache + d, 2 * d, step + 1, p.selfmask, 0x7fffffff, d, p.H, sc, LkP, part, os, tid, nullptr, 0, 0,
+                       koff, moff);
+    else
+      attend<DH>(qkv, cache, cache + d, 2 * d, step + 1, smask, 0x7fffffff, d, p.H, sc, LkP, part, os, tid,
+                 aw ? aw + (size_t)(2 * l) * aw_blk : nullptr, aw_hs, p.Le);
     dense(w.o, os, ys, 0, part, tid);
     add_ln(xs, ys, w.ln1_g, w.ln1_b, o1, d, red, tid);
     dense(w.q2, o1, qkv, 0, part, tid);
@@ -265,6 +354,10 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   }
   dense(p.out, xs, hs, 0, part, tid);          // logits of the position (F >= Vout is not assumed: hs holds max(F, Vout))
 
+  if constexpr (BEAM) {
+    beam_candidates(hs, p.Vout, p.beam, p.cand_lp + (size_t)b * p.beam, p.cand_tok + (size_t)b * p.beam, part, tid);
+    return;
+  }
   __shared__ float s_mx[NT / 64];
   __shared__ int s_am[NT / 64];
   if (p.tokens) {
@@ -337,8 +430,32 @@ bool skf_decode_fused_supported(int d, int H, int F, int Le, int N, int Vout) {
          (size_t)(8 * d + (F > Vout ? F : Vout) + 4 * NT + 16 + H * (Le + 1)) * sizeof(float) <= 159 * 1024;
 }
 
+bool skf_decode_beam_supported(int d, int H, int F, int Le, int N, int Vout) {
+  return skf_decode_fused_supported(d, H, F, Le, N, Vout) &&
+         (size_t)(8 * d + (F > Vout ? F : Vout) + 4 * NT + 16 + (H + 2) * (Le + 1)) * sizeof(float) <= 159 * 1024;
+}
+
 int skf_decode_fused_launch(const SkfDecodeFused& p, hipStream_t st) {
   const int dh = p.d / p.H;
+  if (p.beam) {
+    if (p.attn || p.sample || !p.tokens || !p.anc || !p.cand_lp || !p.cand_tok || p.beam > SKF_BEAM_MAX || p.beam > p.Vout ||
+        p.beam_rows < p.beam || p.beam_rows > p.B || (unsigned long long)p.B * p.Le * 2 * p.d >= (1ull << 32) || p.mask_ld != p.Le + 1) {
+      skf_set_error("%s: beam search needs token mode, its ancestry and candidate areas, 1 <= W <= min(8, vocab) and no attention output", __func__);
+      return SKF_EINVAL;
+    }
+    const size_t smem = skf_decode_fused_lds_bytes(p) + (size_t)2 * (p.Le + 1) * sizeof(int);
+    SkfProfScope ps(st, "decode_position_beam", 0.0, 0.0);
+#define SKF_DB(DHV)                                                                                                  \
+  {                                                                                                                  \
+    SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_position_kernel<DHV, false, false, true>),       \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));                              \
+    hipLaunchKernelGGL((decode_position_kernel<DHV, false, false, true>), dim3(p.beam_rows), dim3(NT), smem, st, p); \
+  }
+    if (dh == 16) SKF_DB(16) else if (dh == 32) SKF_DB(32) else SKF_DB(64)
+#undef SKF_DB
+    SKF_LAUNCH_CHECK();
+    return SKF_OK;
+  }
   const size_t smem = skf_decode_fused_lds_bytes(p);
   SkfProfScope ps(st, "decode_position", 0.0, 0.0);
 #define SKF_DF(DHV, AWV, SMV)                                                                                        \

@@ -311,6 +311,9 @@ struct DecodeAreas {
   size_t mask = 0, flags = 0;     // self-attention padding mask (B, L + 1); [B] eos seen, done step, ticket
   size_t limit = 0;               // [B] key limits of the cross attention, then [B] stream ids of a sampled decode
   size_t dyn = 0;                 // per-call scalars + the step index
+  // beam search (skf_beam.hip), rows g W + k: two ancestry tables (2, B, L + 1) ints; the W <= 8 candidates of a row, (B, 8) log p
+  // then (B, 8) tokens; [B] scores, [B] finished flags, [B] lengths
+  size_t anc = 0, cand = 0, beam = 0;
 };
 
 DecodeAreas take_decode_areas(Bump& b, const SkfConfig& c, bool own_cross) {
@@ -325,6 +328,9 @@ DecodeAreas take_decode_areas(Bump& b, const SkfConfig& c, bool own_cross) {
   A.mask = b.take(B * (L + 1)); A.flags = b.take((B + 16) * sizeof(int));
   A.limit = b.take(2 * B * sizeof(int));
   A.dyn = b.take(64);
+  A.anc = b.take(2 * B * (L + 1) * sizeof(int));
+  A.cand = b.take(2 * B * SKF_BEAM_MAX * sizeof(float));
+  A.beam = b.take(3 * B * sizeof(int));
   return A;
 }
 
@@ -337,7 +343,7 @@ bool decode_areas_ok(const DecodeAreas& A, size_t plan_bytes) {
     if (!A.kv2.empty()) o.push_back(A.kv2[i]);
     o.push_back(A.cache[i]);
   }
-  for (size_t v : {A.img, A.mask, A.flags, A.limit, A.dyn}) o.push_back(v);
+  for (size_t v : {A.img, A.mask, A.flags, A.limit, A.dyn, A.anc, A.cand, A.beam}) o.push_back(v);
   if (o[0] == 0 || o.back() + 64 > plan_bytes || (!A.kv2.empty() && A.kv2.size() != A.cache.size())) return false;
   for (size_t i = 1; i < o.size(); ++i)
     if (o[i] <= o[i - 1]) return false;
@@ -1582,8 +1588,15 @@ int run_backward(SkfModel* M, hipStream_t s) {
 // smp (optional, token mode, checked by the caller): the tokens are drawn (skf_model_sample_decode) with the streams stream_ids_host
 // (B ints, null = 0 .. B-1); only the selection differs, and the layer-by-layer steps are then issued eagerly.
 //
+// bm (optional, token mode, checked by the caller): beam search (skf_model_beam_decode).  The batch holds n = B / W sketches, the
+// embedding and expected_len_host have n rows and are replicated into the W rows of a sketch on the device; a position is the beam
+// instantiation of the one-launch kernel plus beam_advance_kernel (always: there are no beams on the layer-by-layer path), and the
+// hypotheses are gathered through the last ancestry table into bm_out.
+//
 // A bf16-trained model decodes the same way, in fp32 on the MASTER weights (only the embedding it starts from comes from the bf16
 // encoder), and only through the one-launch-per-position kernel.  What differs between the two plans is in the view below.
+struct BeamOut { long long* tokens; float* scores; int* lengths; };
+
 struct DecodeView {
   const DecodeAreas* areas = nullptr;
   float* emb = nullptr;             // (B, E) bottleneck embedding the expander reads; null without a bottleneck
@@ -1619,7 +1632,8 @@ DecodeView decode_view(SkfModel* M) {
 
 int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
                long long eos, int max_steps, void* out, int* out_len_host, float* attn, hipStream_t s,
-               const SkfSampling* smp = nullptr, const int* stream_ids_host = nullptr) {
+               const SkfSampling* smp = nullptr, const int* stream_ids_host = nullptr, const SkfBeam* bm = nullptr,
+               const BeamOut* bm_out = nullptr) {
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
   const Plan& P = M->plan;                             // (the layer-by-layer step and the class head: fp32 plan only)
@@ -1630,9 +1644,12 @@ int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host
   const int Vout = c.continuous ? 5 : c.vocab_size;
   if (!V.layerwise)
     SKF_CHECK_ARG(skf_decode_fused_supported(d, H, F, Le, N, Vout), "greedy decode of a bf16 model needs the one-launch decoder (d <= 512, <= 8 layers)");
+  const int W = bm ? bm->beam_width : 1, nsk = B / W;    // beam search: nsk sketches in rows g W + k
   // the embedding is (B, E) with a bottleneck, else the whole encoder output (B, L, d) = pre_decoder itself
   const float* pre = V.pre;
-  if (V.emb) {
+  if (bm) {                                              // (n, ...) rows, each replicated into its sketch's W rows
+    SKF_TRY(skf_beam_replicate(V.emb ? V.emb : V.pre, embedding, nsk, W, V.emb ? (size_t)L.E : (size_t)Le * d, s));
+  } else if (V.emb) {
     if (embedding && embedding != V.emb)
       SKF_HIP(hipMemcpyAsync(V.emb, embedding, (size_t)B * L.E * sizeof(float), hipMemcpyDeviceToDevice, s));
   } else if (embedding && embedding != V.enc_out) {
@@ -1655,8 +1672,21 @@ int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host
   int* limit = nullptr;                                  // per-sample key limit of the cross attention (non-blind only)
   if (!c.blind_decoder_mask) {
     limit = M->at<int>(A.limit);
-    if (expected_len_host) SKF_HIP(hipMemcpyAsync(limit, expected_len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    if (bm) {                                            // one limit per sketch, through the area's second half
+      SKF_HIP(hipMemcpyAsync(limit + B, expected_len_host, (size_t)nsk * sizeof(int), hipMemcpyHostToDevice, s));
+      SKF_TRY(skf_beam_replicate(limit, limit + B, nsk, W, 1, s));
+    } else if (expected_len_host) SKF_HIP(hipMemcpyAsync(limit, expected_len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
     else SKF_HIP(hipMemsetAsync(limit, 0xff, (size_t)B * sizeof(int), s));        // -1: nattn = step + 1
+  }
+  SkfBeamState bs{};
+  if (bm) {
+    bs.n = nsk; bs.W = W; bs.B = B;
+    bs.cand_lp = M->at<float>(A.cand); bs.cand_tok = reinterpret_cast<int*>(bs.cand_lp + (size_t)B * SKF_BEAM_MAX);
+    bs.scores = M->at<float>(A.beam); bs.finished = reinterpret_cast<int*>(bs.scores + B); bs.lengths = bs.finished + B;
+    bs.anc = M->at<int>(A.anc); bs.anc_ld = Le + 1;
+    bs.tokens = tokens; bs.Ti = Ti; bs.selfmask = selfmask; bs.mask_ld = Le + 1;
+    bs.done_step = done_step; bs.step_dev = step_dev; bs.ticket = done_step + 1; bs.dyn = dyn;
+    SKF_TRY(skf_beam_init(bs, s));
   }
   int* stream_ids = nullptr;
   if (smp) {
@@ -1729,7 +1759,7 @@ int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host
   };
   // One launch per position (skf_decode_fused.hip) unless SKF_MODEL_DECODE_LAYERWISE (skf_model_set_flags) asks for the layer-by-layer path above
   const bool fused_off = (M->flags & SKF_MODEL_DECODE_LAYERWISE) != 0;
-  const bool fused = !V.layerwise || (!fused_off && skf_decode_fused_supported(d, H, F, Le, N, Vout));
+  const bool fused = bm || !V.layerwise || (!fused_off && skf_decode_fused_supported(d, H, F, Le, N, Vout));
   SkfDecodeFused fp{};
   if (fused) {
     auto dn = [&](const DenseP& w) {
@@ -1757,11 +1787,14 @@ int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host
       fp.sample = 1; fp.temperature = smp->temperature; fp.top_k = smp->top_k; fp.top_p = smp->top_p; fp.seed = smp->seed;
       fp.stream_ids = stream_ids;
     }
+    if (bm) {
+      fp.beam = W; fp.beam_rows = nsk * W; fp.anc = bs.anc; fp.cand_lp = bs.cand_lp; fp.cand_tok = bs.cand_tok;
+    }
     SKF_HIP(hipMemsetAsync(fp.ticket, 0, sizeof(int), s));
   }
   // the captured step has constant arguments, no weight output and the greedy selection: with weights requested or with
   // sampling, the steps are issued eagerly (g_dec stays as it is)
-  const bool use_graph = !fused && !attn && !smp;
+  const bool use_graph = !fused && !attn && !smp && !bm;
   if (use_graph && !M->g_dec) {
     hipGraph_t graph = nullptr;
     SKF_HIP(hipStreamSynchronize(s));        // nothing of the setup above may end up inside the captured step
@@ -1775,6 +1808,10 @@ int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host
     if (e != hipSuccess) { skf_set_error("hipGraphInstantiate (decode step): %s", hipGetErrorString(e)); M->g_dec = nullptr; return SKF_EHIP; }
   }
   auto issue_position = [&]() -> int {
+    if (bm) {
+      SKF_TRY(skf_decode_fused_launch(fp, s));
+      return skf_beam_advance_launch(bs, 0, 0, 0, s);      // (step, n_valid and eos come from device memory)
+    }
     if (fused) return skf_decode_fused_launch(fp, s);
     if (!use_graph) return issue_step();
     SKF_HIP(hipGraphLaunch(M->g_dec, s));
@@ -1792,6 +1829,12 @@ int run_decode(SkfModel* M, const float* embedding, const int* expected_len_host
   }
   const int ncols = (done >= 0 ? done + 1 : steps_run) + 1;     // start symbol + emitted positions
   if (out_len_host) *out_len_host = ncols;
+  if (bm) {      // after steps_run positions the current table is steps_run & 1; columns behind ncols are written as zeros
+    SKF_TRY(skf_beam_gather(bs, steps_run & 1, ncols, T, bm->length_alpha, bm_out->tokens, bm_out->scores, bm_out->lengths, s));
+    if (steps_run & 1)      // "decode/ancestry" is table 0: leave the table that was read there
+      SKF_HIP(hipMemcpyAsync(bs.anc, bs.anc + (size_t)B * bs.anc_ld, (size_t)B * bs.anc_ld * sizeof(int), hipMemcpyDeviceToDevice, s));
+    return SKF_OK;
+  }
   // hand the valid columns to the caller's (B, max_steps + 1[, 5]) buffer
   const size_t esz = c.continuous ? 5 * sizeof(float) : sizeof(long long);
   SKF_HIP(hipMemcpy2DAsync(out, (size_t)T * esz, c.continuous ? (const void*)cont : (const void*)tokens, (size_t)Ti * esz,
@@ -2051,6 +2094,12 @@ extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
     M->plan = build_plan(*cfg);
     register_buffers(M);
   }
+  {   // the running image and the ancestry tables of the last reconstruction (4-byte words; see skf_model_beam_decode)
+    const DecodeAreas& A = M->bf16 ? M->p16.dca : M->plan.dca;
+    const size_t B = cfg->batch, L1 = cfg->seq_len + 1;
+    if (!cfg->continuous) M->reg("decode/tokens", A.img, B, 2 * L1, 2 * L1, 0);
+    M->reg("decode/ancestry", A.anc, B, L1, L1, 0);
+  }
   if (!decode_areas_ok(M->bf16 ? M->p16.dca : M->plan.dca, M->bf16 ? M->p16.bytes : M->plan.bytes)) {
     skf_set_error("skf_model_create: internal error, the %s plan's decode areas are not distinct allocations", M->bf16 ? "bf16" : "fp32");
     delete M;
@@ -2144,10 +2193,12 @@ extern "C" int skf_model_encode(SkfModel* m, const void* inp, skf_stream_t strea
 }
 
 namespace {
-// The three reconstruction entries.  `entry` names the caller in the error text; sampled: skf_model_sample_decode (tokens are drawn).
+// The four reconstruction entries.  `entry` names the caller in the error text; sampled: skf_model_sample_decode (tokens are drawn);
+// beam: skf_model_beam_decode (out = the tokens of beam_out).
 int decode_entry(const char* entry, SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
                  long long eos, int max_steps, void* out, int* out_len_host, float* attn_weights, bool sampled,
-                 const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream) {
+                 const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream, const SkfBeam* beam = nullptr,
+                 const BeamOut* beam_out = nullptr) {
 #define SKF_ENTRY_CHECK(cond, msg) \
   do { if (!(cond)) { skf_set_error("%s: %s (%s)", entry, msg, #cond); return SKF_EINVAL; } } while (0)
   SKF_ENTRY_CHECK(m && m->ws, "model not bound");
@@ -2168,9 +2219,34 @@ int decode_entry(const char* entry, SkfModel* m, const float* embedding, const i
     }
   }
   return run_decode(m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, attn_weights, (hipStream_t)stream,
-                    sampled ? sampling : nullptr, stream_ids_host);
+                    sampled ? sampling : nullptr, stream_ids_host, beam_out ? beam : nullptr, beam_out);
 }
 }  // namespace
+
+extern "C" int skf_model_beam_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                                     long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths,
+                                     int* out_len_host, const SkfBeam* beam, skf_stream_t stream) {
+  // what depends on the configuration alone is answered first (a model that is not bound yet is told the same)
+#define SKF_BEAM_CHECK(cond, msg) \
+  do { if (!(cond)) { skf_set_error("%s: %s (%s)", __func__, msg, #cond); return SKF_EINVAL; } } while (0)
+  SKF_BEAM_CHECK(m, "null model");
+  SKF_TRY(skf_beam_check(beam));
+  const SkfConfig& c = m->cfg;
+  SKF_BEAM_CHECK(!c.continuous, "a continuous model decodes one deterministic stroke-5 row per position, with nothing to rank: "
+                                "beam search is built for token models only");
+  SKF_BEAM_CHECK(c.do_reconstruction, "the model was built without a decoder (do_reconstruction = 0)");
+  SKF_BEAM_CHECK(beam->beam_width <= c.vocab_size && beam->beam_width <= c.batch, "beam_width must be in [1, min(8, vocab_size, batch)]");
+  SKF_BEAM_CHECK(n_valid >= 1 && n_valid <= c.batch / beam->beam_width, "n_valid must be in [1, batch / beam_width]");
+  SKF_BEAM_CHECK(skf_decode_beam_supported(c.d_model, c.num_heads, c.dff, c.seq_len, c.num_layers, c.vocab_size) &&
+                     (unsigned long long)c.batch * c.seq_len * 2 * c.d_model < (1ull << 32),
+                 "beam search needs the one-launch decoder with room for its ancestry row (d <= 512, <= 8 layers, head size 16 / 32 / 64)");
+  SKF_BEAM_CHECK(c.blind_decoder_mask || expected_len_host, "beam search of a non-blind decoder needs expected_len");
+  SKF_BEAM_CHECK(embedding && out_tokens && out_scores && out_lengths, "null embedding or output");
+#undef SKF_BEAM_CHECK
+  const BeamOut bo{out_tokens, out_scores, out_lengths};
+  return decode_entry(__func__, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out_tokens, out_len_host, nullptr, false,
+                      nullptr, nullptr, stream, beam, &bo);
+}
 
 extern "C" int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,
                                             long long sos, long long eos, int max_steps, void* out, int* out_len_host,

@@ -133,6 +133,21 @@ def check_sampling(temperature, top_k, top_p):
         raise ValueError("top_p must be in (0, 1], 1 = off (got %r)" % (top_p,))
 
 
+BEAM_NEEDS_TOKENS = ("beam search is built for token models: a continuous model decodes one deterministic stroke-5 row per "
+                     "position, with nothing to rank")
+
+
+def check_beam(beam_width, length_alpha, vocab_size=None, batch=None):
+    """The parameter ranges of beam search (include/skf.h: SkfBeam); ValueError outside them."""
+    if int(beam_width) != beam_width or not 1 <= int(beam_width) <= _lib.BEAM_MAX:
+        raise ValueError("beam_width must be an integer in [1, %d] (got %r)" % (_lib.BEAM_MAX, beam_width))
+    for what, cap in (("vocab_size", vocab_size), ("batch", batch)):
+        if cap is not None and int(beam_width) > cap:
+            raise ValueError("beam_width must not exceed %s=%d (got %r)" % (what, cap, beam_width))
+    if not float(length_alpha) >= 0.0 or float(length_alpha) == float("inf"):
+        raise ValueError("length_alpha must be a finite number >= 0 (got %r)" % (length_alpha,))
+
+
 class TrainEngine:
     """One replica of the sketch-transformer-tf2 train step on one GPU."""
 
@@ -379,11 +394,49 @@ class TrainEngine:
         smp = _lib.SkfSampling(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xffffffff)
         return self._decode_call("skf_model_sample_decode", embedding, expected_len, n_valid, sos, eos, max_steps, C.byref(smp), sid)[0]
 
-    def _decode_embedding(self, embedding):
-        """The caller's embedding as a float32 device tensor of the shape the decoder starts from, or None for None."""
+    def beam_decode(self, embedding, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None, beam_width=4,
+                    length_alpha=0.0):
+        """Beam-search reconstruction (skf_model_beam_decode; the selection rule is in include/skf.h): the beam_width most likely
+        reconstructions of n = batch // beam_width sketches.  embedding: (n, E) array / tensor [(n, L, d) without a bottleneck];
+        expected_len: one length per sketch, required by a non-blind decoder.  Returns (tokens (n_valid, W, T) int32 incl. the SOS
+        column, scores (n_valid, W) float32: the sums of log p, lengths (n_valid, W) int32: the position of a hypothesis's EOS, or
+        the positions decoded when it has none); the hypotheses of a sketch are ordered by score / ((5 + length) / 6)^length_alpha,
+        best first.  Token models only (ValueError for a continuous one)."""
+        B, L = self.cfg.batch, self.cfg.seq_len
+        if self.cfg.continuous:
+            raise ValueError(BEAM_NEEDS_TOKENS)
+        check_beam(beam_width, length_alpha, self.cfg.vocab_size, B)
+        W = int(beam_width)
+        n = B // W
+        if not self.cfg.blind_decoder_mask and expected_len is None:
+            raise ValueError("beam search of a non-blind decoder needs expected_len")
+        n_valid = n if n_valid is None else int(n_valid)
+        if not 1 <= n_valid <= n:
+            raise ValueError("n_valid must be in [1, batch // beam_width = %d]" % n)
+        max_steps = L if max_steps is None else int(max_steps)
+        e = self._decode_embedding(embedding, rows=n)
+        lim = self._expected_len(expected_len, rows=n)
+        out = torch.zeros(n, W, max_steps + 1, dtype=torch.int64, device=self.device)
+        scores = torch.zeros(n, W, dtype=torch.float32, device=self.device)
+        lengths = torch.zeros(n, W, dtype=torch.int32, device=self.device)
+        n_out = C.c_int(0)
+        bm = _lib.SkfBeam(beam_width=W, length_alpha=float(length_alpha))
+        self._enter()
+        try:
+            _lib.call("skf_model_beam_decode", self.handle, self._p(e), lim, n_valid, int(sos), int(eos), max_steps, self._p(out),
+                      self._p(scores), self._p(lengths), C.byref(n_out), C.byref(bm), self._stream())
+        finally:
+            self._leave()
+        self.synchronize()
+        return (out[:n_valid, :, :n_out.value].cpu().numpy().astype(np.int32), scores[:n_valid].cpu().numpy(),
+                lengths[:n_valid].cpu().numpy())
+
+    def _decode_embedding(self, embedding, rows=None):
+        """The caller's embedding as a float32 device tensor of the shape the decoder starts from (``rows`` of them: the batch
+        unless given), or None for None."""
         if embedding is None:
             return None
-        B, L = self.cfg.batch, self.cfg.seq_len
+        B, L = self.cfg.batch if rows is None else rows, self.cfg.seq_len
         e = torch.as_tensor(np.asarray(embedding, dtype=np.float32) if not torch.is_tensor(embedding) else embedding)
         e = e.to(self.device, dtype=torch.float32).contiguous()
         if self.cfg.lowerdim == 0:      # no bottleneck: the "embedding" is the encoder output (B, L, d)
@@ -394,11 +447,11 @@ class TrainEngine:
             raise ValueError("embedding must have shape %r" % (want,))
         return e
 
-    def _expected_len(self, expected_len):
-        """One key limit per batch row as c_int[B] (rows past the given ones: seq_len), or None for None."""
+    def _expected_len(self, expected_len, rows=None):
+        """One key limit per batch row (or per one of ``rows``) as c_int[B] (rows past the given ones: seq_len), or None for None."""
         if expected_len is None:
             return None
-        B = self.cfg.batch
+        B = self.cfg.batch if rows is None else rows
         arr = np.zeros(B, dtype=np.int32)
         v = np.asarray(expected_len).astype(np.int32).reshape(-1)
         arr[:len(v)] = v

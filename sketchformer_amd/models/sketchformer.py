@@ -261,6 +261,92 @@ class Transformer(BaseModel, TransformerMetricsMixin):
                 cls.append(self.engine.buffer('class_probs')[:m].cpu().numpy().argmax(-1).astype(np.int32))
         return np.concatenate(recon, axis=0), (np.concatenate(cls, axis=0) if self._has_cls else None)
 
+    def _beam_chunks(self, rows, decode, B, cls_stride):
+        """_decode_in_chunks for beam search: chunks of B = batch_size // beam_width sketches (the last one zero-padded);
+        ``decode(chunk, i, m)`` returns ((m, W, T) tokens, extras...), the T axis is zero-padded to seq_len + 1 columns and the extras
+        (scores, lengths) are concatenated as they are; the class of sketch r is read from batch row r * cls_stride.
+        Returns (recon (R, W, seq_len + 1), [extras...], class (R,) int32 or None)."""
+        import torch
+        L = self.seq_len + 1
+        recon, extras, cls = [], None, []
+        for i in range(0, rows.shape[0], B):
+            chunk = rows[i:i + B]
+            m = chunk.shape[0]
+            if m < B:
+                chunk = torch.cat([chunk, torch.zeros((B - m,) + tuple(chunk.shape[1:]), dtype=torch.float32, device=chunk.device)], dim=0)
+            r, *rest = decode(chunk, i, m)
+            pad = np.zeros(r.shape[:2] + (L,), dtype=r.dtype)
+            pad[:, :, :r.shape[2]] = r
+            recon.append(pad)
+            extras = [[x] for x in rest] if extras is None else [a + [x] for a, x in zip(extras, rest)]
+            if self._has_cls:
+                cls.append(self.engine.buffer('class_probs')[:m * cls_stride:cls_stride].cpu().numpy().argmax(-1).astype(np.int32))
+        return (np.concatenate(recon, axis=0), [np.concatenate(a, axis=0) for a in extras],
+                (np.concatenate(cls, axis=0) if self._has_cls else None))
+
+    def beam_search_from_embedding(self, emb, beam_width=4, length_alpha=0.0, expected_len=None):
+        """The beam_width most likely reconstructions of every embedding (engine.beam_decode; the selection rule is in
+        include/skf.h).  emb: any number n of embeddings, a host array or a device tensor (n, E); they are decoded in consecutive
+        chunks of batch_size // beam_width sketches.  Every column after a hypothesis's EOS is 0, so a sketch's result depends
+        neither on n, nor on its chunk, nor on its neighbours.  expected_len: per embedding, required by a non-blind model.
+        Returns {'recon': (n, W, seq_len + 1) int32, best first, 'score': (n, W) float32 sums of log p, 'length': (n, W) int32,
+        'class': (n,) int32 or None}."""
+        import torch
+        from .. import engine as _engine
+        if not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        if self.dataset.hps['use_continuous_data']:
+            raise ValueError(_engine.BEAM_NEEDS_TOKENS)
+        _engine.check_beam(beam_width, length_alpha)
+        eng = self.engine
+        _engine.check_beam(beam_width, length_alpha, eng.cfg.vocab_size, eng.cfg.batch)
+        W = int(beam_width)
+        if not torch.is_tensor(emb):
+            emb = torch.as_tensor(np.asarray(emb, dtype=np.float32))
+        emb = emb.to(eng.device, dtype=torch.float32)
+        if emb.dim() == (1 if self.hps['lowerdim'] else 2):       # one embedding: (E,) - or (L, d) without a bottleneck
+            emb = emb[None]
+        n = emb.shape[0]
+        if n == 0:
+            raise ValueError("no embedding given")
+        if self.hps['blind_decoder_mask']:
+            expected_len = None                                   # "will be ignored if blind_decoder_mask=True"
+        elif expected_len is None:
+            raise ValueError("beam search of a non-blind decoder needs expected_len")
+        else:
+            expected_len = np.asarray(expected_len).astype(np.int32).reshape(-1)
+            if len(expected_len) != n:
+                raise ValueError("expected_len must hold one length per embedding")
+        sos, eos = self._sos_eos()
+        recon, (score, length), cls = self._beam_chunks(emb, lambda chunk, i, m: eng.beam_decode(
+            chunk, expected_len=None if expected_len is None else expected_len[i:i + m], n_valid=m, sos=sos, eos=eos,
+            beam_width=W, length_alpha=length_alpha), eng.cfg.batch // W, W)
+        ended = np.cumsum(recon[:, :, 1:] == eos, axis=2) > 0     # from the first EOS on (column 0 is the start symbol)
+        recon[:, :, 2:][ended[:, :, :-1]] = 0
+        return {'recon': recon, 'score': score, 'length': length, 'class': cls}
+
+    def beam_search(self, inp_seq, beam_width=4, length_alpha=0.0):
+        """beam_search_from_embedding on the embeddings of inp_seq (any number of model-ready token sequences); the embeddings go
+        from the encoder to the decoder on the device.  A non-blind model decodes with its input's length as expected_len, like
+        predict."""
+        from .. import engine as _engine
+        if not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        if self.dataset.hps['use_continuous_data']:
+            raise ValueError(_engine.BEAM_NEEDS_TOKENS)
+        _engine.check_beam(beam_width, length_alpha)
+        if not self.hps['lowerdim']:
+            raise ValueError("beam_search needs lowerdim > 0 (the bottleneck embedding); without one, pass the (n, L, d) encoder "
+                             "outputs to beam_search_from_embedding")
+        x = np.asarray(inp_seq)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim == 3 and x.shape[-1] == 1:
+            x = x[..., 0]
+        tlen = None if self.hps['blind_decoder_mask'] else np.sum(x > 0, axis=-1).reshape(-1)
+        return self.beam_search_from_embedding(self._embed_on_device(x), beam_width=beam_width, length_alpha=length_alpha,
+                                               expected_len=tlen)
+
     def _embed_on_device(self, x):
         """Bottleneck embeddings of any number of model-ready sequences as ONE device (P, E) float32 tensor: encoded in chunks of
         batch_size, every chunk's rows copied out of the 'embedding' buffer device to device."""

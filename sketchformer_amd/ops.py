@@ -572,6 +572,70 @@ def sample_tokens(logits, temperature, top_k, top_p, seed, stream_ids, step):
     return tokens[:, step + 1].clone()
 
 
+def beam_step(cand_logp, cand_tok, scores, finished, anc, step, eos, lengths=None):
+    """One merge of beam search on caller tensors (skf_beam_advance; the selection rule is in include/skf.h).  n sketches of W beams:
+    cand_logp (n W, W) float32 and cand_tok (n W, W) int32: every beam's W candidates; scores (n W,) float32, finished (n W,)
+    int32, lengths (n W,) int32 (default zeros): the beams before the step; anc (n W, >= step + 2) int32: the ancestry rows
+    of position `step`.  Nothing is modified.  -> dict(parent, token, score, finished, length: (n W,), anc: like anc, row r' =
+    the parent's row up to `step`, then r')."""
+    _f32(cand_logp, "cand_logp")
+    _f32(scores, "scores")
+    if cand_logp.dim() != 2 or cand_tok.shape != cand_logp.shape:
+        raise ValueError("cand_logp and cand_tok must both be (n * W, W)")
+    R, W = cand_logp.shape
+    step = int(step)
+    if not 1 <= W <= _lib.BEAM_MAX or R % W:
+        raise ValueError("need 1 <= W <= %d and n * W rows" % _lib.BEAM_MAX)
+    if step < 0 or anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < step + 2:
+        raise ValueError("anc must be (n * W, >= step + 2) and step >= 0")
+    _p(cand_logp)
+    dev = cand_logp.device
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()      # noqa: E731
+    cand_logp, cand_tok = cand_logp.contiguous(), i32(cand_tok)
+    sc = scores.to(dev).contiguous().clone()
+    fin = i32(finished).clone()
+    ln = torch.zeros(R, dtype=torch.int32, device=dev) if lengths is None else i32(lengths).clone()
+    if sc.shape != (R,) or fin.shape != (R,) or ln.shape != (R,):
+        raise ValueError("scores, finished and lengths hold one entry per beam")
+    ld = anc.shape[1]
+    tables = torch.zeros(2, R, ld, dtype=torch.int32, device=dev)
+    tables[step & 1] = i32(anc)
+    tokens = torch.zeros(R, step + 2, dtype=torch.int64, device=dev)
+    mask = torch.zeros(R, step + 2, dtype=torch.uint8, device=dev)
+    parent = torch.zeros(R, dtype=torch.int32, device=dev)
+    _lib.call("skf_beam_advance", _p(cand_logp), _p(cand_tok), R // W, W, step, int(eos), _p(sc), _p(fin), _p(ln), _p(tables), ld,
+              _p(tokens), step + 2, _p(mask), step + 2, _p(parent), _stream())
+    return dict(parent=parent, token=tokens[:, step + 1].clone(), pad=mask[:, step + 1].clone(), score=sc, finished=fin, length=ln,
+                anc=tables[(step + 1) & 1])
+
+
+def beam_finish(scores, lengths, anc, tokens, beam_width, length_alpha=0.0, ncols=None):
+    """The final order of beam search on caller tensors (skf_beam_finish).  scores (n W,) float32, lengths (n W,) int32, anc (n W, ld)
+    int32: the ancestry rows, tokens (n W, T) int64: the running image.  -> (tokens (n, W, T) int64: every hypothesis read through
+    its ancestry row, zeros from ncols (default T) on; scores (n, W); lengths (n, W)), each sketch ordered by
+    score / ((5 + length) / 6)^length_alpha descending, then beam index; the scores are the raw sums."""
+    _f32(scores, "scores")
+    _p(scores)
+    dev = scores.device
+    R, W = scores.shape[0], int(beam_width)
+    if not 1 <= W <= _lib.BEAM_MAX or R % W or R == 0:
+        raise ValueError("need 1 <= W <= %d and n * W rows" % _lib.BEAM_MAX)
+    lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+    anc = anc.to(device=dev, dtype=torch.int32).contiguous()
+    tokens = tokens.to(device=dev, dtype=torch.int64).contiguous()
+    T = tokens.shape[1]
+    ncols = T if ncols is None else int(ncols)
+    if lengths.shape != (R,) or anc.dim() != 2 or anc.shape[0] != R or tokens.shape[0] != R or not 1 <= ncols <= min(T, anc.shape[1]):
+        raise ValueError("lengths (n W,), anc (n W, >= ncols), tokens (n W, T) and 1 <= ncols <= T")
+    n = R // W
+    out = torch.zeros(n, W, T, dtype=torch.int64, device=dev)
+    osc = torch.zeros(n, W, dtype=torch.float32, device=dev)
+    oln = torch.zeros(n, W, dtype=torch.int32, device=dev)
+    _lib.call("skf_beam_finish", _p(scores.contiguous()), _p(lengths), _p(anc), anc.shape[1], _p(tokens), T, n, W, ncols, T,
+              float(length_alpha), _p(out), _p(osc), _p(oln), _stream())
+    return out, osc, oln
+
+
 def row_normalize(x):
     """(N, d) float32 -> rows divided by max(norm, 1e-12), out of place (skf_row_normalize_f32)."""
     _f32(x, "x")
