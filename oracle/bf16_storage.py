@@ -5,7 +5,7 @@ heads).  TEST INFRASTRUCTURE ONLY (see oracle/__init__.py): tests/test_gpu_bf16_
 this restatement at a bar an order of magnitude below the one against the float64 oracle - what is left is fp32-vs-float64
 accumulation order and the rare value that sits within that distance of a bf16 rounding boundary.
 
-The storage points follow sketchformer_amd/csrc/skf_model_bf16.inc (launch sequence), skf_bf16_gemm.hip (Dense: bf16 operands,
+The storage points follow sketchformer_amd/csrc/skf_model_bf16.hip (launch sequence), skf_bf16_gemm.hip (Dense: bf16 operands,
 fp32 accumulate, fp32 bias, result rounded; an accumulating launch rounds the product, adds the old value in fp32 and rounds
 again), skf_bf16_rowops.hip (embedding, residual + LayerNorm with moments of the ROUNDED z, cross-entropy gradient in place,
 pooling, expander) and skf_bf16_attention.hip (64-key blocks with a running maximum, the unnormalised probabilities of a block

@@ -74,6 +74,19 @@ double skf_prof_list_fraction(const int* list);
 double skf_prof_attention_fraction(const unsigned char* key_mask, int mask_ld, int causal, int B, int Lq, int Lk,
                                    const int* q_live, int qtile, int ktile);
 
+// Launchers that the step orchestrator (skf_model*.hip) calls and include/skf.h does not declare.  skf_optimizer.hip: the Adam sweep;
+// advance != 0 = the sweep of a whole step, which also performs skf_step_epilogue's increment.  skf_rowops.hip: the pooling scorer's /
+// the expander's backward without their column sums (the partials are left for the batched reduction), and the staging launch.
+int skf_adam_step_launch(float* w, const float* g, float* m, float* v, size_t n, void* step_state, float grad_scale, float beta1, float beta2,
+                         float eps, int advance, hipStream_t stream);
+int skf_pool_bwd_partials(float* u_inout_dpre, const float* Vw, const float* x, const float* a, const float* demb, int B, int L, int U, int d,
+                          float* dx, float* dV_part, hipStream_t s);
+int skf_expander_bwd_partials(const float* dpre, const float* emb, const float* w, int B, int L, int d, float* demb, int demb_accumulate,
+                              float* p1, float* p2, hipStream_t s);
+int skf_stage_inputs_launch(const void* inp, void* dinp, const void* tar, void* dtar, size_t row, size_t src_row, size_t copy, int batch,
+                            const void* labels, void* dlabels, hipStream_t st, unsigned char* emask = nullptr, unsigned char* dmask = nullptr,
+                            int mask_L = 0);
+
 static inline int skf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // An event that means "everything this stream was given so far is complete" costs the stream ~5 us as a packet of its own

@@ -1,5 +1,5 @@
 // The position-wise feed-forward block of builders/layers/transformer.py:194-198 (`point_wise_feed_forward_network`:
-// Dense(dff, relu) -> Dense(d_model)) as ONE launch per direction (skf_ffn_fused.hip); shared with skf_model.hip.
+// Dense(dff, relu) -> Dense(d_model)) as ONE launch per direction (skf_ffn_fused.hip); shared with skf_model_fwd.hip / skf_model_bwd.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -963,7 +963,7 @@ int launch_ffn(const FfnFusedParams& p, hipStream_t st) {
   const double bytes = 4.0 * ((double)p.M * FD * (MODE == 0 ? 4 : 3) + (double)p.M * FF + (POST ? (double)p.M * p.n2 : 0.0) + (PRE ? 4.0 * p.M * FD : 0.0)) + 2.0 * image_bytes(P) / 2;
   SkfProfScope ps(st, tag.c_str(), flops, bytes);
   ps.done(flops * live, bytes * live);
-  // tail audit: parked by ffn_bwd / ffn_ln_bwd (skf_model.hip) around skf_ffn_fused_bwd[_ln]_f32; every entry point of this file is ONE launch
+  // tail audit: parked by ffn_bwd / ffn_ln_bwd (skf_model_bwd.hip) around skf_ffn_fused_bwd[_ln]_f32; every entry point of this file is ONE launch
   SKF_LAUNCH_TAIL((ffn_fused_kernel<P, MODE, LNB, POST, PRE>), dim3(grid), dim3(512), smem, st, p);
   SKF_LAUNCH_CHECK();
   return SKF_OK;

@@ -1,4 +1,4 @@
-// bf16 path of the train-step orchestrator (BASELINE cfg 5; included by skf_model.hip).
+// bf16 path of the train-step orchestrator (BASELINE cfg 5); its workspace plan is build_plan16 (skf_model_layout.hip).
 //
 // The same launch sequence as run_forward / run_backward (models/sketchformer.py:131-181, 325-349) with bf16 activations:
 // Dense layers on skf_gemm_bf16 / skf_gemm_bf16_wgrad, attention on the streaming kernels, row stages on the *_bf16 row
@@ -8,132 +8,14 @@
 // its loss) run on the fp32 kernels.  One stream, weight gradients in line (partial tiles + their reduction), two gradient
 // buckets like the fp32 path.  Structure restrictions (skf_config_validate): token mode, attn_version 1, bottleneck +
 // classifier + decoder, no class buffers, head size 64.
-#if SKF_BF16_PART == 1   // ---- data structures + workspace plan (before struct SkfModel)
-namespace {
+#include "skf_model_internal.h"
 
-struct Img16 { size_t w = 0, wt = 0; int in = 0, out = 0, ld_src = 0, ldw = 0, ldt = 0; size_t src = 0; };
-struct Enc16 { size_t x_in, qkv, o, olo, z1, st1, astats, x1, h, z2, st2, x2, hbits; };
-struct Dec16 { size_t x_in, qkv, o1, olo1, z1, st1, astats1, out1, q2, kv2, o2, olo2, astats2, z2, st2, out2, h, z3, st3, out3, hbits; };
-
-}  // namespace
-
-struct Plan16 {
-  size_t bytes = 0;
-  size_t inp = 0, tar = 0, labels = 0, enc_mask = 0, dec_mask = 0;
-  std::vector<Enc16> enc;
-  std::vector<Dec16> dec;
-  size_t u = 0, pool_a = 0, emb = 0, cls_logits = 0, cls_probs = 0, pre = 0, logits = 0;
-  int ld_logits = 0;
-  size_t recon_loss = 0, recon_hit = 0, cls_loss = 0, cls_hit = 0;
-  size_t gA = 0, gB = 0, dy = 0, dqkv = 0, dh = 0, dO = 0, dpre = 0, dkv2 = 0, dq2 = 0, demb = 0;
-  size_t slab = 0, slab_bytes = 0, small_ws = 0, small_ws_bytes = 0, attn_ws = 0, attn_ws_bytes = 0, ln_ws = 0, ln_ws_bytes = 0;
-  size_t cast_descs = 0, cast_descs_bytes = 0; int cast_n = 0, cast_blocks = 0; const float* cast_for = nullptr;   // weight-image descriptor table
-  const char* tables_ws = nullptr;
-  // LayerNorm gamma / beta gradients: every LayerNorm backward of the step leaves its [g][2d] partials in its own slab; two
-  // batched reductions (decoder side, encoder side = the two gradient buckets) replace 80 small column-sum launches
-  size_t ln_slabs = 0, ln_descs = 0; int ln_n = 0, ln_n_dec = 0, ln_blocks_dec = 0, ln_blocks_enc = 0, ln_cursor = 0; bool ln_batched = false;
-  DecodeAreas dca;                                 // greedy / sampled reconstruction (fp32, on the master weights: run_decode)
-  size_t order = 0;                                // samples sorted by length (skf_sample_order)
-  size_t live_len = 0, live1 = 0, live64 = 0;      // live decoder rows of the step (skf_row_blocks.hip): row list, 64-row blocks
-  size_t emb_sort[2] = {0, 0}, emb_sort_bytes = 0;
-  std::map<size_t, Img16> img;          // keyed by DenseP.w (offset of the fp32 kernel in the flat buffer)
-};
-
-namespace {
-
-inline int pad8(int n) { return (n + 7) & ~7; }
-
-void add_img(Plan16& P, Bump& b, const DenseP& w) {
-  Img16 im;
-  im.in = w.in; im.out = w.out; im.ld_src = w.ld; im.src = w.w;
-  im.ldw = pad8(w.out); im.ldt = pad8(w.in);
-  im.w = b.take((size_t)w.in * im.ldw * 2);
-  im.wt = b.take((size_t)w.out * im.ldt * 2);
-  P.img[w.w] = im;
-}
-
-Plan16 build_plan16(const SkfConfig& c, const Layout& L) {
-  Plan16 P;
-  Bump b;
-  const size_t B = c.batch, Ls = c.seq_len, Ld = c.seq_len - 1, d = c.d_model, F = c.dff, U = c.lowerdim;
-  const size_t Me = B * Ls, Md = B * Ld, H = c.num_heads, f = sizeof(float), h2 = 2;
-  const int N = c.num_layers;
-  P.inp = b.take(B * Ls * 8); P.tar = b.take(B * Ls * 8); P.labels = b.take(B * 8);
-  P.enc_mask = b.take(B * Ls); P.dec_mask = b.take(B * Ls);
-  for (int i = 0; i < N; ++i) {
-    Enc16 a;
-    a.x_in = b.take(Me * d * h2); a.qkv = b.take(Me * 3 * d * h2); a.o = b.take(Me * d * h2); a.olo = b.take(Me * d * h2); a.z1 = b.take(Me * d * h2);
-    a.st1 = b.take(Me * 2 * f); a.astats = b.take(B * H * Ls * 2 * f); a.x1 = b.take(Me * d * h2);
-    a.h = b.take(Me * F * h2); a.z2 = b.take(Me * d * h2); a.st2 = b.take(Me * 2 * f); a.x2 = 0;
-    a.hbits = b.take(skf_gemm_bf16_relu_bits_bytes((int)Me, (int)F));      // sign bits of h for the ffn input gradient (0 bytes: dff % 8 != 0)
-    P.enc.push_back(a);
-  }
-  const size_t enc_out = b.take(Me * d * h2);
-  for (int i = 0; i < N; ++i) P.enc[i].x2 = (i + 1 < N) ? P.enc[i + 1].x_in : enc_out;
-  P.u = b.take(Me * U * h2); P.pool_a = b.take(B * Ls * f); P.emb = b.take(B * d * f);
-  P.cls_logits = b.take(B * c.n_classes * f); P.cls_probs = b.take(B * c.n_classes * f);
-  P.pre = b.take(Me * d * h2);
-  for (int i = 0; i < N; ++i) {
-    Dec16 a;
-    a.x_in = b.take(Md * d * h2); a.qkv = b.take(Md * 3 * d * h2); a.o1 = b.take(Md * d * h2); a.olo1 = b.take(Md * d * h2); a.z1 = b.take(Md * d * h2);
-    a.st1 = b.take(Md * 2 * f); a.astats1 = b.take(B * H * Ld * 2 * f); a.out1 = b.take(Md * d * h2);
-    a.q2 = b.take(Md * d * h2); a.kv2 = b.take(Me * 2 * d * h2); a.o2 = b.take(Md * d * h2); a.olo2 = b.take(Md * d * h2);
-    a.astats2 = b.take(B * H * Ld * 2 * f); a.z2 = b.take(Md * d * h2); a.st2 = b.take(Md * 2 * f);
-    a.out2 = b.take(Md * d * h2); a.h = b.take(Md * F * h2); a.z3 = b.take(Md * d * h2); a.st3 = b.take(Md * 2 * f);
-    a.hbits = b.take(skf_gemm_bf16_relu_bits_bytes((int)Md, (int)F));
-    a.out3 = 0;
-    P.dec.push_back(a);
-  }
-  const size_t dec_out = b.take(Md * d * h2);
-  for (int i = 0; i < N; ++i) P.dec[i].out3 = (i + 1 < N) ? P.dec[i + 1].x_in : dec_out;
-  P.ld_logits = pad8(c.vocab_size);
-  P.logits = b.take(Md * (size_t)P.ld_logits * h2);
-  P.recon_loss = b.take(Md * f); P.recon_hit = b.take(Md * f); P.cls_loss = b.take(B * f); P.cls_hit = b.take(B * f);
-  P.gA = b.take(Me * d * h2); P.gB = b.take(Me * d * h2); P.dy = b.take(Me * d * h2); P.dO = b.take(Me * d * h2);
-  P.dqkv = b.take(Me * 3 * d * h2); P.dh = b.take(Me * F * h2); P.dpre = b.take(Me * d * h2);
-  P.dkv2 = b.take(Me * 2 * d * h2); P.dq2 = b.take(Md * d * h2); P.demb = b.take(B * d * f);
-  // weight-gradient slab: the largest (in, out) pair of the model at its default split count
-  size_t g = 0;
-  auto mx = [&](int in, int out, size_t rows) {
-    const size_t v = skf_gemm_bf16_wgrad_workspace_bytes(in, out, (int)rows, skf_gemm_bf16_wgrad_splits(in, out, (int)rows));
-    if (v > g) g = v;
-  };
-  mx((int)d, (int)(3 * d), Me); mx((int)d, (int)d, Me); mx((int)d, (int)F, Me); mx((int)F, (int)d, Me); mx((int)d, (int)(2 * d), Me);
-  mx((int)d, c.vocab_size, Md); mx((int)d, (int)U, Me);
-  const size_t small = skf_gemm_workspace_bytes((int)d, c.n_classes, (int)B, 8, 1);
-  if (small > g) g = small;
-  P.slab_bytes = g; P.slab = b.take(g);
-  size_t s = B * U * f;
-  if (2 * B * Ls * f > s) s = 2 * B * Ls * f;
-  P.small_ws_bytes = s; P.small_ws = b.take(s);
-  P.attn_ws_bytes = skf_attention_bf16_bwd_workspace_bytes((int)B, (int)H, (int)Ls); P.attn_ws = b.take(P.attn_ws_bytes);
-  P.ln_ws_bytes = skf_layernorm_bwd_bf16_workspace_bytes((int)Me, (int)d); P.ln_ws = b.take(P.ln_ws_bytes);
-  P.cast_descs_bytes = 256 * sizeof(SkfCastDesc); P.cast_descs = b.take(P.cast_descs_bytes);
-  P.ln_n = 5 * (int)c.num_layers; P.ln_n_dec = 3 * (int)c.num_layers;
-  P.ln_slabs = b.take((size_t)P.ln_n * P.ln_ws_bytes); P.ln_descs = b.take((size_t)P.ln_n * sizeof(SkfReduceDesc));
-  P.dca = take_decode_areas(b, c, true);
-  P.live_len = b.take(B * sizeof(int));
-  P.order = b.take(B * sizeof(int));
-  P.live1 = b.take(skf_row_blocks_bytes((int)Md, 1)); P.live64 = b.take(skf_row_blocks_bytes((int)Md, 64));
-  if (c.vocab_size <= 12288) {
-    P.emb_sort_bytes = (skf_embed_sort_workspace_bytes((int)B, (int)Ls, c.vocab_size) + 255) & ~(size_t)255;
-    P.emb_sort[0] = b.take(P.emb_sort_bytes); P.emb_sort[1] = b.take(P.emb_sort_bytes);
-  }
-  for (const auto& e : L.enc) { add_img(P, b, e.mha.qkv); add_img(P, b, e.mha.o); add_img(P, b, e.f1); add_img(P, b, e.f2); }
-  for (const auto& e : L.dec) {
-    add_img(P, b, e.mha1.qkv); add_img(P, b, e.mha1.o); add_img(P, b, e.mha2.q); add_img(P, b, e.mha2.kv); add_img(P, b, e.mha2.o);
-    add_img(P, b, e.f1); add_img(P, b, e.f2);
-  }
-  add_img(P, b, L.bott_w); add_img(P, b, L.out);
-  P.bytes = b.off;
-  return P;
-}
-
-}  // namespace
-#else                     // ---- the launch sequences (after the fp32 helpers)
+namespace skf_model_detail {
 namespace {
 
 inline void* w16(SkfModel* M, size_t off) { return M->ws + off; }
+
+}  // namespace
 
 // the named activations of the bf16 plan (bf16 unless said otherwise: row pitch `ld` elements)
 void register_buffers16(SkfModel* M) {
@@ -207,6 +89,7 @@ int ensure_cast_table16(SkfModel* M, hipStream_t s) {
   }
   return SKF_OK;
 }
+namespace {
 int refresh_images16(SkfModel* M, hipStream_t s) {
   SkfProfScope ps(s, "weight_images_bf16", 0.0, 0.0);
   const Plan16& P = M->p16;
@@ -272,7 +155,8 @@ int ln16_reduce(SkfModel* M, bool first, hipStream_t s) {
   return skf_splitk_reduce_batch(descs + P.ln_n_dec, P.ln_n - P.ln_n_dec, P.ln_blocks_enc, s);
 }
 
-int run_forward16(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool encoder_only = false) {
+}  // namespace
+int run_forward16(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool encoder_only) {
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
   const Plan16& P = M->p16;
@@ -472,5 +356,4 @@ int issue_embed_sorts16(SkfModel* M, hipStream_t s) {
   return skf_embed_sort(M->at<long long>(P.tar), Le, B, Ld, c.vocab_size, M->G(M->lay.dec_emb), d, M->at<char>(P.emb_sort[1]), P.emb_sort_bytes, s);
 }
 
-}  // namespace
-#endif
+}  // namespace skf_model_detail

@@ -130,7 +130,7 @@ extern "C" int skf_step_epilogue(void* step_state, skf_stream_t stream) {
   return SKF_OK;
 }
 
-// internal (skf_model.hip): advance != 0 = the sweep of a whole step, which also performs skf_step_epilogue's increment
+// internal (skf_model.hip; declared in skf_common.h): advance != 0 = the sweep of a whole step, which also performs skf_step_epilogue's increment
 int skf_adam_step_launch(float* w, const float* g, float* m, float* v, size_t n, void* step_state, float grad_scale, float beta1, float beta2,
                          float eps, int advance, hipStream_t stream) {
   SKF_CHECK_ARG(w && g && m && v && step_state, "null operand");

@@ -1449,7 +1449,7 @@ extern "C" int skf_pool_bwd(float* u_inout_dpre, const float* Vw, const float* x
   SKF_LAUNCH_CHECK();
   return SKF_OK;
 }
-// internal (skf_model.hip): the launch without the column sum - dV_part[B][U] is left for a batched reduction (a "slab" of B splits of a 1 x U matrix)
+// internal (skf_model_bwd.hip): the launch without the column sum - dV_part[B][U] is left for a batched reduction (a "slab" of B splits of a 1 x U matrix)
 int skf_pool_bwd_partials(float* u_inout_dpre, const float* Vw, const float* x, const float* a, const float* demb, int B, int L, int U, int d,
                           float* dx, float* dV_part, hipStream_t s) {
   SkfProfScope ps(s, "pool_bwd", 0.0, 8.0 * B * L * (U + d));
@@ -1486,7 +1486,7 @@ extern "C" int skf_expander_bwd(const float* dpre, const float* emb, const float
   SKF_LAUNCH_CHECK();
   return SKF_OK;
 }
-// internal (skf_model.hip): the launch without the two column sums - p1 / p2 [B][L] (dw / dbias partials) are left for a batched reduction
+// internal (skf_model_bwd.hip): the launch without the two column sums - p1 / p2 [B][L] (dw / dbias partials) are left for a batched reduction
 int skf_expander_bwd_partials(const float* dpre, const float* emb, const float* w, int B, int L, int d, float* demb, int demb_accumulate,
                               float* p1, float* p2, hipStream_t s) {
   SkfProfScope ps(s, "expander_bwd", 0.0, 8.0 * B * L * d);

@@ -141,19 +141,55 @@ _RETIRED_KNOBS = (
 )
 
 
+# the translation units of the step orchestrator (skf_model_internal.h is what they share)
+_MODEL_UNITS = ("skf_model", "skf_model_prof", "skf_model_layout", "skf_model_sched", "skf_model_fwd", "skf_model_bwd", "skf_model_decode",
+                "skf_model_bf16")
+
+
 def test_train_step_schedule_has_no_knobs():
     """The train step's stream / event schedule and the Dense / LayerNorm routing are fixed: the A/B knobs that once switched
     them (even in measurement builds) are gone, the step's orchestrator reads no knob at all, and the integration guide and the
     knob table of tools/ do not name the retired ones."""
     import glob
     csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
-    for name in ("skf_model.hip", "skf_model_bf16.inc"):
+    units = sorted(os.path.basename(p) for p in glob.glob(os.path.join(csrc, "skf_model*")))
+    for stem in _MODEL_UNITS:      # (a rename must not empty the loop below)
+        assert any(u.startswith(stem + ".") for u in units), (stem, units)
+    assert "skf_model_internal.h" in units
+    for name in units:
         assert "skf_knob(" not in open(os.path.join(csrc, name)).read(), name
     pattern = re.compile(r"\b(%s)\b" % "|".join(_RETIRED_KNOBS))
     docs = [os.path.join(ROOT, "INTEGRATION.md"), os.path.join(ROOT, "tools", "README.md")]
     for path in glob.glob(os.path.join(csrc, "*")) + docs:
         m = pattern.search(open(path, encoding="utf-8").read())
         assert m is None, "%s names the retired knob %s" % (path, m.group(1))
+
+
+def test_library_sources_are_the_build_list():
+    """Every .hip file of csrc/ is compiled and nothing is textually included as code: a forgotten unit fails here, not at dlopen."""
+    from sketchformer_amd import build
+    csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert sorted(f for f in files if f.endswith(".hip")) == sorted(build.SOURCES)
+    assert len(set(build.SOURCES)) == len(build.SOURCES)
+    assert not [f for f in files if f.endswith(".inc")]
+    for f in files:
+        text = open(os.path.join(csrc, f), encoding="utf-8").read()
+        m = re.search(r'#\s*include\s*"[^"\n]*\.(hip|inc)"', text)
+        assert m is None, "%s: %s" % (f, m.group(0))
+
+
+def test_library_has_no_unresolved_symbol_of_its_own(lib):
+    """A helper that one unit declares (skf_model_internal.h) and no unit defines links into a shared library all the same and only
+    fails when first called.  The weak `w _ZTH...` entries are the optional initialisers of the extern thread_local variables
+    (null by design: both are constant-initialised); every other undefined symbol that names skf_ is a missing definition."""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--undefined-only", os.path.join(ROOT, "sketchformer_amd", "libskf.so")],
+                         capture_output=True, text=True, check=True).stdout
+    lines = [ln.split() for ln in out.splitlines() if "skf_" in ln]
+    assert len(out.splitlines()) > 20
+    missing = [ln for ln in lines if not (ln[0] == "w" and ln[1].startswith("_ZTH"))]
+    assert missing == [], missing
 
 
 def test_launch_attached_events_and_input_handover_have_one_owner():
