@@ -14,8 +14,8 @@
  *  - launches are asynchronous on `stream` (a hipStream_t cast to void*), re-entrant,
  *    and keep no global state besides a thread-local error string (the opt-in launch
  *    profiler below is a measurement facility of the calling process, off by default).
- *    The library reads no environment variable: tuning / ablation knobs exist only in
- *    -DSKF_MEASURE=1 builds (csrc/skf_common.h: skf_knob), never in the shipped .so.
+ *    The library reads no environment variable and has no build-time switch: there is one
+ *    build, the shipped one.
  *  - return 0 on success, negative on error (never throws across the ABI);
  *    skf_last_error() describes the last failure on the calling thread.
  */

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256, MAXT <= 13 ? 4 : 1) void attn_fwd_kernel(AttnP
   // A head is a 64..256-byte slice of every activation row, i.e. half (or less) of each 128-byte line it touches; the
   // other half belongs to the neighbouring head.  XCD-contiguous ids put all heads of a sample on ONE XCD (one L2),
   // consecutively in time, so the neighbour's half is an L2 hit instead of a second HBM fetch of the same line.
-  int bh = p.xcd_remap ? skf_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  int bh = skf_xcd_remap(blockIdx.x, gridDim.x);
   if (p.order) { const int k = skf_deal_rank(blockIdx.x, p.H); bh = min(max(p.order[k / p.H], 0), p.B - 1) * p.H + k % p.H; }   // (clamped: a list that is no permutation must not leave the tensors)
   const int b = bh / p.H, h = bh % p.H;
   const int nkt = (p.Lk + 15) >> 4, nqt = (p.Lq + 15) >> 4;
@@ -96,14 +96,6 @@ __global__ __launch_bounds__(256, MAXT <= 13 ? 4 : 1) void attn_fwd_kernel(AttnP
       dst[c] = row < p.Lq ? v : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
-#if SKF_MEASURE     // clock stamps of a few workgroups (tools/attn_fwd_timeline.py): measurement builds only
-  long long* fdbg = (p.dbg && lane == 0 && (blockIdx.x % 131) == 0 && blockIdx.x / 131 < 8) ? p.dbg + ((blockIdx.x / 131) * 4 + wave) * 16 : nullptr;
-  int fdbi = 0;
-#define SKF_FSTAMP() do { if (fdbg && fdbi < 16) fdbg[fdbi++] = wall_clock64(); } while (0)
-#else
-#define SKF_FSTAMP() do { } while (0)
-#endif
-  SKF_FSTAMP();      // start
   load_q((wave + bh) & 3, qnext);
   // ---- stage K, V^T (zero-filled tail rows) and the key mask.  All global loads of the prologue are issued before the first wait
   // (clamped, always valid addresses; rows past Lk zeroed afterwards): the guarded form - `if (row < Lk) load` inside a 256-element
@@ -157,7 +149,6 @@ __global__ __launch_bounds__(256, MAXT <= 13 ? 4 : 1) void attn_fwd_kernel(AttnP
     for (int o = 32; o > 0; o >>= 1) lv = max(lv, __shfl_xor(lv, o, 64));
     if (lane == 0) last_valid[wave] = lv;
   }
-  SKF_FSTAMP();      // this wave's share of K / V staged
   __syncthreads();
   if (tid < nkt) {
     int f = 0;
@@ -165,7 +156,6 @@ __global__ __launch_bounds__(256, MAXT <= 13 ? 4 : 1) void attn_fwd_kernel(AttnP
     Tf[tid] = f;
   }
   __syncthreads();
-  SKF_FSTAMP();      // staging complete
 
   // Causal tile skipping is exact only when key 0 is visible to every query
   // (then every row max is a real score and masked probabilities are exactly 0).
@@ -292,7 +282,6 @@ __global__ __launch_bounds__(256, MAXT <= 13 ? 4 : 1) void attn_fwd_kernel(AttnP
     }
     __builtin_amdgcn_raw_buffer_store_b64((attn_u32x2){__builtin_bit_cast(unsigned, mx), __builtin_bit_cast(unsigned, rinv)}, st_rsrc,
                                           (qok && g == 0) ? (unsigned)qrow * 8u : 0x7ffffff0u, 0, 0);
-    SKF_FSTAMP();    // one per query tile
   }
 }
 
@@ -301,15 +290,9 @@ __global__ __launch_bounds__(256, MAXT <= 13 ? 4 : 1) void attn_fwd_kernel(AttnP
 // consecutive key tiles, and when nkt = 4*(KTW-1)+1 (L = 193..208 at dh=16) the odd 13th key tile is SHARED: every wave
 // holds its fragments and processes it for the query tiles with (qt & 3) == wave; the four partial dK/dV are summed
 // through LDS at the end (work per wave 42.25 pairs instead of 52 / 39 / 39 / 39).
-#ifndef SKF_ATTN_BWD_WAVES
-#define SKF_ATTN_BWD_WAVES 2   // waves per SIMD the register allocation aims at (3 = 168 VGPRs)
-#endif
-#ifndef SKF_ATTN_BWD_TRP
-#define SKF_ATTN_BWD_TRP 0     // transpose patches per wave: 0 = one per key tile of the wave (KTW); 1 = one shared patch (20 -> 5 KB of LDS at dh = 16:
-                               // three workgroups per CU instead of two when SKF_ATTN_BWD_WAVES = 3)
-#endif
+constexpr int kAttnBwdWaves = 2;   // waves per SIMD the register allocation aims at (3 = 168 VGPRs: 4.66 against 4.64 ms/step, profiles/r03f_flag_sweep_ln_bwd.txt)
 template <int DH, int KTW, bool CAUSAL>
-__global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, kAttnBwdWaves) void attn_bwd_kernel(AttnParams p) {
   constexpr int NC = DH / 16;
   constexpr int LD = DH + 4;
   constexpr int TLD = 20;
@@ -317,7 +300,7 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
   // A head is a 64..256-byte slice of every activation row, i.e. half (or less) of each 128-byte line it touches; the
   // other half belongs to the neighbouring head.  XCD-contiguous ids put all heads of a sample on ONE XCD (one L2),
   // consecutively in time, so the neighbour's half is an L2 hit instead of a second HBM fetch of the same line.
-  int bh = p.xcd_remap ? skf_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  int bh = skf_xcd_remap(blockIdx.x, gridDim.x);
   if (p.order) { const int k = skf_deal_rank(blockIdx.x, p.H); bh = min(max(p.order[k / p.H], 0), p.B - 1) * p.H + k % p.H; }   // (clamped: a list that is no permutation must not leave the tensors)
   const int b = bh / p.H, h = bh % p.H;
   const int nkt = (p.Lk + 15) >> 4, nqt_all = (p.Lq + 15) >> 4;
@@ -337,14 +320,6 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, g = lane >> 4;
 
-  long long* dbg = (p.dbg && lane == 0 && (blockIdx.x % 131) == 0 && blockIdx.x / 131 < 8) ? p.dbg + ((blockIdx.x / 131) * 4 + wave) * 32 : nullptr;
-  int dbi = 0;
-#if SKF_MEASURE     // clock stamps of a few workgroups (tools/attn_timeline.py): measurement builds only
-#define SKF_STAMP() do { if (dbg && dbi < 32) dbg[dbi++] = clock64(); } while (0)
-#else
-#define SKF_STAMP() do { (void)dbg; (void)dbi; } while (0)
-#endif
-  SKF_STAMP();
   // Everything the prologue reads from global memory is requested before its first wait: the key fragments of the first pass,
   // this thread's mask byte and row statistics, then the Q / dO / O rows (four serialised round trips before: rows, mask scan,
   // statistics, fragments - 8.4k + 3.9k cycles of a ~40k-cycle workgroup at one or two waves per SIMD).
@@ -415,7 +390,7 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
       }
     }
   }
-  int* last_valid = reinterpret_cast<int*>(Tr + 4 * (SKF_ATTN_BWD_TRP ? SKF_ATTN_BWD_TRP : KTW) * 16 * TLD);   // [4]: per-wave index of the last un-padded key
+  int* last_valid = reinterpret_cast<int*>(Tr + 4 * KTW * 16 * TLD);   // [4]: per-wave index of the last un-padded key
   {
     int lv = -1;
     if (tid < p.Lk && !(km && mk0)) lv = tid;
@@ -433,7 +408,6 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
   // dQ of the dead query tiles: zeros (their tiles are never visited below)
   for (int e = nqt * 16 * DH + tid; e < p.Lq * DH; e += 256) p.dQ[(size_t)(b * p.Lq + e / DH) * p.lddq + h * DH + e % DH] = 0.f;
   __syncthreads();
-  SKF_STAMP();   // staging done
 
   // skipping fully look-ahead-masked tiles is exact only if key 0 is visible (see forward)
   const bool can_skip = CAUSAL && !(km && km[0]);      // CAUSAL == p.causal (dispatch)
@@ -442,7 +416,7 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
   const int nkt_eff = (lastk >= 0 && (!CAUSAL || can_skip)) ? (lastk >> 4) + 1 : nkt;
   const float inv_sqrt = 1.0f / sqrtf((float)DH);
   const float c2 = 1.44269504088896340736f / sqrtf((float)DH);
-  float* tr0 = Tr + wave * (SKF_ATTN_BWD_TRP ? SKF_ATTN_BWD_TRP : KTW) * 16 * TLD;
+  float* tr0 = Tr + wave * KTW * 16 * TLD;
   f32x4 dK_shared[NC], dV_shared[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) { dK_shared[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; dV_shared[c] = dK_shared[c]; }
@@ -474,11 +448,8 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
         dKt[j][c] = (f32x4){0.f, 0.f, 0.f, 0.f}; dVt[j][c] = dKt[j][c];
       }
     }
-
-    SKF_STAMP();   // K/V fragments loaded (issued)
     // every wave walks ALL query tiles in lock step (the trip count must be workgroup-uniform: one barrier per tile)
     for (int qt = 0; qt < nqt; ++qt) {
-      SKF_STAMP();
       const int q0 = qt * 16;
       float4 qa[NC], da[NC];
       float qT[NC][4], dT[NC][4];
@@ -544,8 +515,7 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
             dKt[j][c] = mfma16(qT[c][r], ds[r], dKt[j][c]);
           }
         // transpose dS through the wave-private scratch: write [q][k], read [q=i][k=4g..4g+3]
-        constexpr int TRP = SKF_ATTN_BWD_TRP ? SKF_ATTN_BWD_TRP : KTW;     // patches per wave
-        float* tr = tr0 + (j % TRP) * 16 * TLD;
+        float* tr = tr0 + (j % KTW) * 16 * TLD;     // one patch per key tile of the wave
 #pragma unroll
         for (int r = 0; r < 4; ++r) tr[(g * 4 + r) * TLD + i] = ds[r];
         // (no fence: the LDS executes one wave's instructions in order, and the patch is private to (wave, j))
@@ -602,9 +572,7 @@ __global__ __launch_bounds__(256, SKF_ATTN_BWD_WAVES) void attn_bwd_kernel(AttnP
   };
   kg_pass(0, std::true_type());
   for (int kg = 4 * KTW; kg < nkt; kg += 4 * KTW) kg_pass(kg, std::false_type());
-  SKF_STAMP();   // wave done
   __syncthreads();
-  SKF_STAMP();   // all waves done
   if (!CAUSAL && KTW > 1 && nkt == 4 * (KTW - 1) + 1) {
     // partial dK^T / dV^T of the shared key tile: Qs is free now, use it as [4 waves][2][DH][16] scratch
     float* sh = Qs + wave * 2 * DH * 16;
@@ -637,7 +605,7 @@ size_t fwd_smem(int DH, int Lk, bool split) {
 }
 size_t bwd_smem(int DH, int Lq) {
   const size_t QR = (size_t)(Lq + 15) / 16 * 16;
-  return (2 * QR * (DH + 4) + (size_t)2 * 4 * 16 * (DH + 1) + 3 * QR + (size_t)4 * (SKF_ATTN_BWD_TRP ? SKF_ATTN_BWD_TRP : 64 / DH) * 16 * 20 + 4) * sizeof(float);
+  return (2 * QR * (DH + 4) + (size_t)2 * 4 * 16 * (DH + 1) + 3 * QR + (size_t)4 * (64 / DH) * 16 * 20 + 4) * sizeof(float);
 }
 
 template <typename K>
@@ -647,14 +615,11 @@ int set_smem(K kfn, size_t bytes) {
 }
 
 inline bool mfma_head(int dh) { return dh == 16 || dh == 32 || dh == 64; }
-// S^T on the bf16 pipe follows the Dense arithmetic switch (SKF_ATTN_SPLIT=0 turns it off).  With padded 48-byte plane
+// S^T on the bf16 pipe follows the Dense arithmetic switch.  With padded 48-byte plane
 // rows it removed 26 % of the MFMA cycles and changed nothing (the forward is wait-bound: 45 % of the wave cycles parked,
 // and the planes cost the fourth resident workgroup per CU); with unpadded rows (four workgroups per CU again, 2-way bank
 // conflicts) it is 4-11 % faster than the fp32-MFMA tiles: 36.4 / 29.0 / 42.1 vs 39.2 / 30.2 / 47.2 us.
-bool fwd_split(int dh, int precision) {
-  static const bool split_off = skf_knob_is("SKF_ATTN_SPLIT", '0');
-  return dh == 16 && !split_off && precision != SKF_PREC_F32;
-}
+bool fwd_split(int dh, int precision) { return dh == 16 && precision != SKF_PREC_F32; }
 int check_common(const AttnParams& p, int dh) {
   SKF_CHECK_ARG(mfma_head(dh) || skf_attention_any_supported(dh, p.Lq, p.Lk), "head dim must be 16, 32, 64 (MFMA kernels) or any size <= 128 with sequences <= 1024 (fallback)");
   SKF_CHECK_ARG(p.B > 0 && p.H > 0 && p.Lq > 0 && p.Lk > 0, "empty problem");
@@ -693,10 +658,6 @@ extern "C" int skf_attention_fwd_ordered(const float* Q, int ldq, const float* K
   p.order = (B & 7) == 0 ? sample_order : nullptr;      // (the deal needs whole rounds of the 8 XCDs; results never depend on it)
   p.Q = Q; p.K = K; p.V = V; p.O = O; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.key_mask = key_mask; p.key_mask_ld = key_mask_ld; p.causal = causal; p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.stats = stats;
-  p.xcd_remap = !skf_knob_is("SKF_ATTN_XCD", '0');
-#if SKF_MEASURE
-  { const char* db = skf_knob("SKF_ATTN_DBG"); p.dbg = db ? (long long*)strtoull(db, nullptr, 0) : nullptr; }
-#endif
   int rc = check_common(p, dh);
   if (rc) return rc;
   SKF_CHECK_ARG(Q && K && V && O, "null operand");
@@ -759,11 +720,6 @@ extern "C" int skf_attention_bwd_ordered(const float* Q, int ldq, const float* K
   p.Q = Q; p.K = K; p.V = V; p.O = const_cast<float*>(O); p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.key_mask = key_mask; p.key_mask_ld = key_mask_ld; p.causal = causal; p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk;
   p.stats = const_cast<float*>(stats);
-  { const char* ab = skf_knob("SKF_ATTN_ABLATE"); p.ablate = ab ? atoi(ab) : 0; }
-  p.xcd_remap = !skf_knob_is("SKF_ATTN_XCD", '0');
-#if SKF_MEASURE
-  { const char* db = skf_knob("SKF_ATTN_DBG"); p.dbg = db ? (long long*)strtoull(db, nullptr, 0) : nullptr; }
-#endif
   p.dO = dO; p.lddo = lddo; p.dQ = dQ; p.dK = dK; p.dV = dV; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
   int rc = check_common(p, dh);
   if (rc) return rc;
@@ -771,25 +727,14 @@ extern "C" int skf_attention_bwd_ordered(const float* Q, int ldq, const float* K
   SKF_CHECK_ARG((lddo & 3) == 0 && (lddq & 3) == 0 && (lddk & 3) == 0 && (lddv & 3) == 0, "row strides must be multiples of 4");
   if (!mfma_head(dh)) return skf_attention_bwd_any(p, dh, (hipStream_t)stream);
   SKF_CHECK_ARG(Lk <= 512, "Lk > 512 not supported");      // (like the forward, whose statistics every kernel below needs)
-  // head size 16 / 32 in the split arithmetic modes: the two-pass kernel on the bf16 matrix cores (skf_attention_bwd2.hip);
-  // SKF_PREC_F32 keeps the fp32-MFMA kernel below (SKF_ATTN_BWD2=0 forces it)
-  // Head size 16: only the causal (decoder self-attention) calls take it - measured at the cfg-2 shape, the one-pass kernel
-  // below is faster without a look-ahead mask (encoder self 89 vs 95 us; cross 101 vs 124 us with every dO row live, and
-  // with the dead query tiles left out by q_live it also wins on padded batches); SKF_ATTN_BWD2=1 forces the two-pass kernel.
-  static const char* bwd2_env = skf_knob("SKF_ATTN_BWD2");       // measurement builds only
-  const bool bwd2_off = bwd2_env && bwd2_env[0] == '0', bwd2_all = (bwd2_env && bwd2_env[0] == '1') || two_pass;
-  // (round 3: with its prologue loads batched the one-pass kernel also wins the causal dh = 16 calls - 4.134 vs 4.149 ms/step padded,
-  //  4.777 vs 4.774 full-length at cfg 2 - so head size 16 takes the two-pass kernel only when forced; head size 32 keeps it:
-  //  15.9 vs 17.2 ms/step at cfg 3)
-  // round 5: head size 16, sequences up to 208, split modes: skf_attention_bwd3.hip (one workgroup per head stages every operand
-  // once, the dQ items and the dK / dV items of the two-pass scheme run side by side from one queue, per-score arithmetic folded
-  // into operands and accumulator seeds); SKF_ATTN_BWD3=0 (measurement builds) or SKF_ATTN_TWO_PASS keep the older kernels reachable
-  const char* bwd3_env = skf_knob("SKF_ATTN_BWD3");          // (per call: tools/attn_bwd3_ablate.py flips it inside one process)
-  if (skf_attention_bwd3_supported(dh, Lq, Lk) && precision != SKF_PREC_F32 && !bwd2_all && !bwd2_off && !(bwd3_env && bwd3_env[0] == '0'))
-    return skf_attention_bwd3_launch(p, (hipStream_t)stream);
-  const bool bwd2_shape = (dh == 16 && bwd2_all) || (dh == 32 && Lk <= 256 && Lq <= 256);
-  if (bwd2_shape && precision != SKF_PREC_F32 && !bwd2_off && Lk <= 512 && Lq <= 512)
-    return skf_attention_bwd2_launch(p, dh, (hipStream_t)stream);
+  const bool split_mode = precision != SKF_PREC_F32;      // SKF_PREC_F32 keeps the fp32-MFMA one-pass kernel below
+  // head size 16, sequences up to 208: both passes as independent workgroups of one launch (skf_attention_bwd3.hip);
+  // 3.772 against 3.868 ms/step at cfg 2.  SKF_ATTN_TWO_PASS keeps the older kernels reachable.
+  if (skf_attention_bwd3_supported(dh, Lq, Lk) && split_mode && !two_pass) return skf_attention_bwd3_launch(p, (hipStream_t)stream);
+  // the two-pass kernel on the bf16 matrix cores (skf_attention_bwd2.hip): head size 32 up to 256 rows (15.9 against 17.2 ms/step
+  // at cfg 3); head size 16 only on request - the one-pass kernel wins there (4.134 against 4.149 ms/step at cfg 2)
+  const bool bwd2_shape = (dh == 16 && two_pass) || (dh == 32 && Lk <= 256 && Lq <= 256);
+  if (bwd2_shape && split_mode && Lq <= 512) return skf_attention_bwd2_launch(p, dh, (hipStream_t)stream);
   const size_t smem = bwd_smem(dh, Lq);
   SKF_CHECK_ARG(smem <= kAttnLdsBytes, "Q/dO/dQ of one head do not fit in LDS");
   hipStream_t st = (hipStream_t)stream;

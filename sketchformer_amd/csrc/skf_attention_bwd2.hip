@@ -146,7 +146,7 @@ template <int NC, bool CAUSAL>
 __global__ __launch_bounds__(256, NC == 1 ? 4 : 2) void attn_bwd2_kernel(AttnParams p) {
   constexpr int RP = 32 * NC, DH = 16 * NC;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int bh = p.xcd_remap ? skf_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  int bh = skf_xcd_remap(blockIdx.x, gridDim.x);
   if (p.order) { const int k = skf_deal_rank(blockIdx.x, p.H); bh = min(max(p.order[k / p.H], 0), p.B - 1) * p.H + k % p.H; }   // (clamped: a list that is no permutation must not leave the tensors)
   const int b = bh / p.H, h = bh % p.H;
   const int nkt = (p.Lk + 15) >> 4, nqt = (p.Lq + 15) >> 4;
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 4 : 2) void attn_bwd2_kernel(AttnPar
       const bool live = __ballot(nz) != 0ull;
       if (live && lane == 0) atomicOr(reinterpret_cast<unsigned*>(&red[1]), 1u << qt);
       const DOps qo = d_ops<NC>(cur.q0, cur.q1, first, sel), go = d_ops<NC>(cur.g0, cur.g1, first, sel);
-      const int nt = (live && !(p.ablate & 1)) ? min(can_skip ? qt + 1 : nkt, nkt_eff) : 0;   // (ablate: diagnostics)
+      const int nt = min(can_skip ? qt + 1 : nkt, live ? nkt_eff : 0);      // a dead tile visits no key tile
       f32x4 dq[NC];
 #pragma unroll
       for (int c = 0; c < NC; ++c) dq[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 4 : 2) void attn_bwd2_kernel(AttnPar
       f32x4 dkt[NC], dvt[NC];
 #pragma unroll
       for (int c = 0; c < NC; ++c) { dkt[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; dvt[c] = dkt[c]; }
-      if (kt < nkt_eff && !(p.ablate & 2)) {
+      if (kt < nkt_eff) {
         if (!kok) { kc_.k0 = kc_.k1 = kc_.v0 = kc_.v1 = make_float4(0.f, 0.f, 0.f, 0.f); }
         const DOps ko = d_ops<NC>(kc_.k0, kc_.k1, first, sel), vo = d_ops<NC>(kc_.v0, kc_.v1, first, sel);
         const float kadd = kc_.kadd;

@@ -91,9 +91,6 @@ __device__ __forceinline__ int nt_lds_off(int row, int chunk) {       // byte of
 // readable one phase after the wait that retires it: the barrier in between publishes the other waves' pieces), and overwrites a
 // region whose last reader finished >= 2 phases earlier.  Order of the quadrants (0,0) (0,1) (1,1) (1,0) with BOTH n halves of B kept
 // in registers: phase 1 reads A(m half 0) + B(n half 0), phase 2 B(n half 1), phase 3 A(m half 1), phase 4 nothing.
-#ifndef SKF_PH8_ABLATE
-#define SKF_PH8_ABLATE 0      // timing experiments (results wrong): 1 no stagger, 2 no s_setprio, 4 no fragment reads, 8 no DMA, 16 no MFMA
-#endif
 template <bool EXTRA, bool DMA, int BK, bool BIG, bool TANH, bool PH8 = false>
 __global__ __launch_bounds__(BIG ? 512 : 256, 2) void gemm_bf16_nt_kernel(NtParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -239,18 +236,18 @@ __global__ __launch_bounds__(BIG ? 512 : 256, 2) void gemm_bf16_nt_kernel(NtPara
       if (s0 < n_stage) stage(s0 & 3, s0 >> 2);
     if (n_stage > 6) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (wm == 1 && !(SKF_PH8_ABLATE & 1)) __builtin_amdgcn_s_barrier();       // the second wave row runs one barrier behind
+    if (wm == 1) __builtin_amdgcn_s_barrier();       // the second wave row runs one barrier behind
     for (int kt = 0; kt < nk; ++kt) {
       const char* At = smem + (kt & 1) * TB2 + a_base;
       const char* Bt = smem + (kt & 1) * TB2 + b_base;
 #pragma unroll
       for (int ph = 0; ph < 4; ++ph) {
         const int mh = ph >> 1, nh = (ph == 1 || ph == 2) ? 1 : 0;
-        if ((ph == 0 || ph == 1) && !((SKF_PH8_ABLATE & 4) && kt > 0)) {
+        if (ph == 0 || ph == 1) {
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) bf[nh][ks] = *reinterpret_cast<const skf_bf16x8*>(Bt + nh * 32 * 128 + fo[ks]);
         }
-        if ((ph == 0 || ph == 2) && !((SKF_PH8_ABLATE & 4) && kt > 0)) {
+        if (ph == 0 || ph == 2) {
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int t = 0; t < 2; ++t)
@@ -258,25 +255,23 @@ __global__ __launch_bounds__(BIG ? 512 : 256, 2) void gemm_bf16_nt_kernel(NtPara
             for (int ks = 0; ks < 4; ++ks) af[t][ks] = *reinterpret_cast<const skf_bf16x8*>(At + (2 * mh + t) * 32 * 128 + fo[ks]);
         }
         const int sn = 4 * kt + ph + 6;               // the half-tile requested in this phase: kind (ph + 2) & 3 of K step kt + 1 (ph < 2) / kt + 2
-        if (sn < n_stage && !(SKF_PH8_ABLATE & 8)) { stage((ph + 2) & 3, kt + (ph < 2 ? 1 : 2)); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
+        if (sn < n_stage) { stage((ph + 2) & 3, kt + (ph < 2 ? 1 : 2)); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (!(SKF_PH8_ABLATE & 2)) __builtin_amdgcn_s_setprio(1);
-        if (!(SKF_PH8_ABLATE & 16)) {
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
           for (int t = 0; t < 2; ++t)
             acc[nh][2 * mh + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[nh][ks], af[t][ks], acc[nh][2 * mh + t], 0, 0, 0);
-        }
-        if (!(SKF_PH8_ABLATE & 2)) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
       }
     }
-    if (wm == 0 && !(SKF_PH8_ABLATE & 1)) __builtin_amdgcn_s_barrier();       // (the twin of the extra barrier in front of the loop)
+    if (wm == 0) __builtin_amdgcn_s_barrier();       // (the twin of the extra barrier in front of the loop)
     __syncthreads();                                  // the tile buffers are dead: the epilogue's images may overwrite them
   } else {
   if constexpr (DMA) {
@@ -743,9 +738,18 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_big_kernel(TnParams p) {
   }
 }
 
-__host__ inline bool tn_use_big(int P, int Q, int R) {
-  static const int tile_env = skf_knob("SKF_BF16_GEMM_TILE") ? atoi(skf_knob("SKF_BF16_GEMM_TILE")) : 0;
-  return tile_env != 128 && (R & 63) == 0 && P >= 256 && Q >= 256 && R >= 16384;
+__host__ inline bool tn_use_big(int P, int Q, int R) { return (R & 63) == 0 && P >= 256 && Q >= 256 && R >= 16384; }
+
+// Which K loop and tile gemm_bf16_nt_kernel runs for a problem: register-staged 128 x 128 tiles (K % 64 != 0), the same tiles filled
+// by DMA, the 256 x 256 tile (one workgroup per CU, so only where there are enough tiles to fill the chip), and for that tile the
+// phased K loop where there are at least two 64-deep steps.
+struct NtPlan { bool dma, big, ph8; };
+__host__ inline NtPlan nt_plan(int M, int N, int K, int act) {
+  NtPlan t;
+  t.dma = (K & 63) == 0;
+  t.big = t.dma && act != 2 && N >= 256 && (long)skf_cdiv(M, 256) * skf_cdiv(N, 256) >= 256;
+  t.ph8 = t.big && K >= 128;
+  return t;
 }
 
 template <typename K>
@@ -757,14 +761,7 @@ int set_smem(K kfn, size_t bytes) {
 }  // namespace
 
 // rows per output tile the launcher will use for this problem (a live-row block list must be built for that height)
-extern "C" int skf_gemm_bf16_tile_rows(int M, int N, int K, int act) {
-  static const bool dma_off = skf_knob_is("SKF_BF16_GEMM_DMA", '0');
-  static const int tile_env = skf_knob("SKF_BF16_GEMM_TILE") ? atoi(skf_knob("SKF_BF16_GEMM_TILE")) : 0;
-  const bool dma = (K & 63) == 0 && !dma_off;
-  // the 256 x 256 tile: one workgroup per CU, so only where there are enough tiles to fill the chip
-  const bool big = dma && tile_env != 128 && act != 2 && N >= 256 && ((long)skf_cdiv(M, 256) * skf_cdiv(N, 256) >= 256 || tile_env == 256);
-  return big ? 256 : 128;
-}
+extern "C" int skf_gemm_bf16_tile_rows(int M, int N, int K, int act) { return nt_plan(M, N, K, act).big ? 256 : 128; }
 
 extern "C" int skf_gemm_bf16(int M, int N, int K, const void* A, int lda, const void* B_nk, int ldb, void* C, int ldc,
                              const float* bias, int act, const void* relu_src, int ld_relu, int accumulate, float* C_f32,
@@ -807,10 +804,8 @@ extern "C" int skf_gemm_bf16_bits(int M, int N, int K, const void* A, int lda, c
   hipStream_t st = (hipStream_t)stream;
   p.bits_out = (unsigned char*)relu_bits_out; p.bits_in = (const unsigned char*)relu_bits_in; p.ld_bits = ld_bits;
   const bool extra = relu_src || accumulate || C_f32 || relu_bits_in;
-  // SKF_BF16_GEMM_DMA=0: register-staged tiles everywhere; SKF_BF16_GEMM_TILE=128: no 256 x 256 tiles (measurement knobs)
-  static const bool dma_off = skf_knob_is("SKF_BF16_GEMM_DMA", '0');
-  const bool dma = (K & 63) == 0 && !dma_off;
-  const bool big = skf_gemm_bf16_tile_rows(M, N, K, act) == 256;
+  const NtPlan plan = nt_plan(M, N, K, act);
+  const bool dma = plan.dma, big = plan.big, ph8 = plan.ph8;
   const int tile = big ? 256 : 128;
   p.tiles_m = skf_cdiv(M, tile); p.tiles_n = skf_cdiv(N, tile);
   p.row_blocks = row_list; p.zero_dead = zero_dead;
@@ -826,9 +821,6 @@ extern "C" int skf_gemm_bf16_bits(int M, int N, int K, const void* A, int lda, c
     if ((rc = set_smem(gemm_bf16_nt_kernel<EX, DM, 64, BG, TH>, smem))) return rc;                                           \
     hipLaunchKernelGGL((gemm_bf16_nt_kernel<EX, DM, 64, BG, TH>), dim3(p.tiles_m * p.tiles_n), dim3(BG ? 512 : 256), smem, st, p); \
   }
-  // the phased K loop (PH8) for the 256 x 256 tile with at least two 64-deep steps; SKF_BF16_GEMM_PH8=0 (measurement builds): the two-buffer loop
-  static const bool ph8_off = skf_knob_is("SKF_BF16_GEMM_PH8", '0');
-  const bool ph8 = big && K >= 128 && !ph8_off;
 #define SKF_NT_GO8(EX)                                                                                                       \
   {                                                                                                                          \
     if ((rc = set_smem(gemm_bf16_nt_kernel<EX, true, 64, true, false, true>, smem))) return rc;                              \

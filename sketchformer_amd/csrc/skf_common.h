@@ -11,21 +11,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define SKF_WAVE 64
 
-// The shipped library reads NO environment variable and keeps no configuration state (include/skf.h): the A/B, ablation and
-// timeline knobs of tools/ exist only in measurement builds (SKF_EXTRA_HIPCC_FLAGS=-DSKF_MEASURE=1 python -m
-// sketchformer_amd.build --force); in the default build skf_knob() is a constant null and every branch on it folds away.
-#ifndef SKF_MEASURE
-#define SKF_MEASURE 0
-#endif
-#if SKF_MEASURE
-#include <stdlib.h>
-static inline const char* skf_knob(const char* name) { return getenv(name); }
-#else
-static inline const char* skf_knob(const char*) { return nullptr; }
-#endif
-// the knob is set and its value starts with `c`
-static inline bool skf_knob_is(const char* name, char c) { const char* v = skf_knob(name); return v && v[0] == c; }
-
+// The shipped library reads NO environment variable and keeps no configuration state (include/skf.h).
 void skf_set_error(const char* fmt, ...);
 
 #define SKF_CHECK_ARG(cond, msg)                                   \
@@ -217,14 +203,9 @@ __device__ __forceinline__ void skf_split2(float x, float y, unsigned (&out)[P],
   for (int q = 0; q < P; ++q) {
     out[q] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, y), __builtin_bit_cast(unsigned, x), 0x07060302u);   // (y & 0xffff0000) | (x >> 16)
     if (q + 1 < P) {
-#ifdef SKF_SPLIT_NO_DOT2
-      x -= __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u);
-      y -= __builtin_bit_cast(float, __builtin_bit_cast(unsigned, y) & 0xffff0000u);
-#else
       const skf_bf16x2 pc = __builtin_bit_cast(skf_bf16x2, out[q]);
       x = __builtin_amdgcn_fdot2_f32_bf16(pc, __builtin_bit_cast(skf_bf16x2, sel.lo), x, false);
       y = __builtin_amdgcn_fdot2_f32_bf16(pc, __builtin_bit_cast(skf_bf16x2, sel.hi), y, false);
-#endif
     }
   }
 }

@@ -23,10 +23,7 @@ namespace {
 
 constexpr int NT = 512;   // threads per workgroup (8 waves)
 static_assert(NT == SKF_SAMPLE_NT && 4 * NT >= SKF_SAMPLE_SCRATCH_FLOATS, "skf_sample_row runs on this workgroup, in the `part` area");
-#ifndef SKF_DEC_UNROLL
-#define SKF_DEC_UNROLL 16
-#endif
-constexpr int UN = SKF_DEC_UNROLL;   // weight rows requested per thread before the first is used
+constexpr int UN = 16;   // weight rows requested per thread before the first is used
 
 __device__ __forceinline__ float block_sum(float v, float* red, int tid) {
   v = wave_sum(v);

@@ -47,19 +47,8 @@ constexpr int NKS = 4;                // 32-deep MFMA steps per 128-deep contrac
 constexpr int YPITCH = FD + 4;        // floats per row of the epilogue tile
 constexpr unsigned OOB = 0x7ffffff0u;
 
-// SKF_FFN_ABLATE (diagnostics builds, wrong results): bit 0 no MFMA (one VALU op keeps the operands live), 1 fragment reads only
-// once per sub-group, 2 no hidden-tensor / sign-bit stores, 3 no hidden-plane stores, 4 no stage-1 epilogue at all, 5 weight
-// fragments loaded once per launch, 6 no block barriers
-#ifndef SKF_FFN_ABLATE
-#define SKF_FFN_ABLATE 0
-#endif
 __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-#if SKF_FFN_ABLATE & 1
-  c[0] += __builtin_bit_cast(float, (a[0] ^ b[0]) & 0x3fffffu);
-  return c;
-#else
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-#endif
 }
 
 // descriptor over rows [row0, M) of a row-major fp32 matrix (byte counts are 32-bit: the launcher checks M * ld * 4 < 2^31)
@@ -133,10 +122,7 @@ int launch_images(const DenseImageDesc* descs, int n, int P, hipStream_t st) {
 // VGPR offset, everything else wave-uniform in the scalar offset.  (As global loads from per-lane 64-bit addresses the twelve
 // addresses of a rarely used image were spilled one by one: scratch reload + vmcnt(0) + load, twelve dependent round trips.)
 template <int P>
-__device__ __forceinline__ void load_frags(u32x4 (&w)[NKS][P], __amdgpu_buffer_rsrc_t img, unsigned lane16, int soff, bool first = false) {
-#if SKF_FFN_ABLATE & 32
-  if (!first) return;
-#endif
+__device__ __forceinline__ void load_frags(u32x4 (&w)[NKS][P], __amdgpu_buffer_rsrc_t img, unsigned lane16, int soff) {
 #pragma unroll
   for (int s = 0; s < NKS; ++s)
 #pragma unroll
@@ -149,10 +135,7 @@ __device__ __forceinline__ void load_frags(u32x4 (&w)[NKS][P], __amdgpu_buffer_r
 // first, its a0.b0 products last (two accumulator chains).
 template <int P> struct FfnFrags { u32x4 f[2][2][P]; };   // [half][step of the half][piece]
 template <int P>
-__device__ __forceinline__ void load_half(const char* rows, const unsigned (&a_off)[NKS], u32x4 (&f)[2][P], int half, bool first = false) {
-#if SKF_FFN_ABLATE & 2
-  if (!first) return;
-#endif
+__device__ __forceinline__ void load_half(const char* rows, const unsigned (&a_off)[NKS], u32x4 (&f)[2][P], int half) {
 #pragma unroll
   for (int sl = 0; sl < 2; ++sl)
 #pragma unroll
@@ -179,17 +162,6 @@ __device__ __forceinline__ void half_products(const u32x4 (&w)[NKS][P], const u3
     ++c;
   }
 }
-
-// SKF_FFN_STAMPS (diagnostics builds): s_memtime stamps of wave 0 / wave 7 of every 32nd workgroup (tools/ffn_timeline.py)
-#ifndef SKF_FFN_STAMPS
-#define SKF_FFN_STAMPS 0
-#endif
-#if SKF_FFN_STAMPS
-__device__ long long g_ffn_stamps[16 * 64];
-#define FFN_STAMP() do { if (dbg && dbi < 62) dbg[dbi++] = clock64(); } while (0)
-#else
-#define FFN_STAMP() do { } while (0)
-#endif
 
 // sum over the 32 lanes that share a row of the epilogue (lanes 0-31 / 32-63): a DPP all-reduce inside each 16-lane row, then
 // one exchange with the neighbouring row (five __shfl_xor steps are five dependent ds_bpermute round trips)
@@ -231,11 +203,6 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, g = lane >> 4;
-#if SKF_FFN_STAMPS
-  long long* dbg = (lane == 0 && (wave == 0 || wave == 7) && (blockIdx.x % 32) == 0 && blockIdx.x / 32 < 8) ? g_ffn_stamps + ((blockIdx.x / 32) * 2 + (wave == 7)) * 64 : nullptr;
-  int dbi = 0;
-#endif
-  FFN_STAMP();
   const int ntiles = (p.M + TR - 1) / TR;
   typedef const __attribute__((address_space(4))) int* const_i32p;
   const const_i32p blk = (const_i32p)p.row_blocks;
@@ -297,11 +264,7 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
 
   // ONE descriptor per tensor for the whole launch, the tile in the VGPR offset (rows behind M fall outside and are dropped / read
   // as zeros): a descriptor per (tile, block) was ~20 SALU instructions per tile and kept the kernel spilling SGPRs into VGPR lanes
-#if SKF_FFN_ABLATE & 4
-  const __amdgpu_buffer_rsrc_t r_H = __builtin_amdgcn_make_buffer_rsrc(p.H, 0, 0, 0x00020000);
-#else
   const __amdgpu_buffer_rsrc_t r_H = __builtin_amdgcn_make_buffer_rsrc(p.H, 0, p.M * (FF * 4), 0x00020000);
-#endif
   const __amdgpu_buffer_rsrc_t r_A = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(LNB ? p.ln_dout : p.A), 0, p.M * p.lda * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_Z = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(LNB ? p.ln_z : p.A), 0, LNB ? p.M * (FD * 4) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_S = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(LNB ? p.ln_stats : p.A), 0, LNB ? p.M * 8 : 0, 0x00020000);
@@ -327,10 +290,7 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
   const int img1_w = wave * (NKS * P * 1024);            // + b * 8 * NKS * P * 1024
   const int img2_w = wave * (16 * P * 1024);             // + b * NKS * P * 1024
   u32x4 w1[NKS][P], w2[NKS][P];
-  if (!NOFFN && nsub > 0) load_frags<P>(w1, r_img1, lane16, img1_w, true);
-#if SKF_FFN_ABLATE & 32
-  load_frags<P>(w2, r_img2, lane16, img2_w, true);
-#endif
+  if (!NOFFN && nsub > 0) load_frags<P>(w1, r_img1, lane16, img1_w);
 
   // A rows of a sub-group: thread -> float4 st_c of row st_row of every tile.  Requested one sub-group ahead (the first one here,
   // the next one under the current one's last hidden block).  In the forward they are also the residual of the epilogue, whose
@@ -405,9 +365,7 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
 #pragma unroll
       for (int q = 0; q < P; ++q) *reinterpret_cast<u32x2*>(Xp + q * PLANE + rt * TILE + st_off) = (u32x2){lo[q], hi[q]};
     }
-    FFN_STAMP();   // rows staged
     __syncthreads();
-    FFN_STAMP();   // behind the staging barrier
     FfnFrags<P> fr;
     // z = residual + dropout(y), out = LayerNorm(z) for this thread's float4 of row (tile rt, 2 wave + e_half), exactly as
     // ln_fwd_v4_kernel; optionally the planes of `out` for the next product stage (same thread map as the staging)
@@ -481,9 +439,6 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
     f32x4 y[NRT];
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt) y[rt] = bias2_r;
-#if SKF_FFN_ABLATE & 2
-    load_half<P>(Xp, a_off, fr.f[0], 0, true); load_half<P>(Xp, a_off, fr.f[1], 1, true);
-#endif
 
 #pragma unroll 1
     for (int b = 0; b < (NOFFN ? 0 : NBLK); ++b) {
@@ -495,9 +450,6 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
       }
       // the stage-1 epilogue of a tile: activation / mask, sign bits, the hidden rows to global memory and, split, to the LDS planes
       auto hidden_out = [&](int rt, const f32x4& acc0, const f32x4& acc1) {
-#if SKF_FFN_ABLATE & 16
-        if (p.M >= 0) { if (acc0[0] + acc1[0] == 1.2345f) Hb[0] = 1; return; }
-#endif
         f32x4 h = acc0 + acc1;
         const int tile = tl[rt];
         if constexpr (MODE == 0) {
@@ -531,9 +483,6 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
         skf_split2<P>(h[0], h[1], p01, sel);
         skf_split2<P>(h[2], h[3], p23, sel);
         char* hrow = Hb + rt * TILE;
-#if SKF_FFN_ABLATE & 8
-        if (p.M < 0)
-#endif
 #pragma unroll
         for (int q = 0; q < P; ++q) *reinterpret_cast<u32x2*>(hrow + q * PLANE + hw_off) = (u32x2){p01[q], p23[q]};
       };
@@ -567,11 +516,7 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
         if (t == nrt - 1) hidden_out(t, pacc0, pacc1);
       // the next first-stage operands (block 0 again behind the last block: the next sub-group starts with them)
       load_frags<P>(w1, r_img1, lane16, img1_w + ((b + 1) & (NBLK - 1)) * (8 * NKS * P * 1024));
-      FFN_STAMP();   // stage 1 issued
-#if !(SKF_FFN_ABLATE & 64)
       __syncthreads();
-#endif
-      FFN_STAMP();   // behind the block barrier
       // ---- stage 2: Y += Hblock . B2[block rows]
       load_half<P>(Hb, a_off, fr.f[0], 0);
 #pragma unroll
@@ -587,7 +532,6 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      FFN_STAMP();   // stage 2 issued
     }
 
     if constexpr (NOFFN) {                      // (no hidden block to hide them under: the next sub-group's rows are requested here)
@@ -651,23 +595,17 @@ __device__ __forceinline__ void ffn_fused_body(const FfnFusedParams& p) {
           }
         }
       };
-      FFN_STAMP();   // (POST) row epilogue done
       __syncthreads();                                   // the planes of `out` are complete
-      FFN_STAMP();   // (POST) behind the planes barrier
       if (nb2 > 1) load_frags<P>(w1, r_img3, lane16, img3_w + 1 * (8 * NKS * P * 1024));
       post_block(w2, 0);
-      FFN_STAMP();   // (POST) block 0
       if (nb2 > 1) {
         if (nb2 > 2) load_frags<P>(w2, r_img3, lane16, img3_w + 2 * (8 * NKS * P * 1024));
         post_block(w1, 1);
-        FFN_STAMP();   // (POST) block 1
         if (nb2 > 2) post_block(w2, 2);
-        FFN_STAMP();   // (POST) block 2
         if constexpr (!NOFFN) load_frags<P>(w1, r_img1, lane16, img1_w);        // the next sub-group's first operands again
       }
       __syncthreads();                                   // the next sub-group's staging overwrites the planes
     }
-    FFN_STAMP();   // epilogue done
     }
     // (the next sub-group's staging writes Xp, which nobody reads behind the last block's barrier; its first stage writes Hp
     //  buffer 0 = Yt behind the staging barrier, which every wave reaches after its epilogue reads)
@@ -954,10 +892,8 @@ int launch_ffn(const FfnFusedParams& p, hipStream_t st) {
   // per launch like skf_attention.hip's set_smem: the attribute belongs to the (function, device) pair and its failure must surface here
   SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_fused_kernel<P, MODE, LNB, POST, PRE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   // one profiler line for the family (the kernel template's forward / backward / LayerNorm-prologue / chained-projection variants,
-  // like the epilogue kinds of gemm_wsx); SKF_PROF_FINE=1 (measurement builds): one line per variant
-  static const bool fine = skf_knob_is("SKF_PROF_FINE", '1');
-  static const std::string tag = std::string("ffn_fused") + (!fine ? "" : MODE == 0 ? (PRE ? (POST ? "_fwd_pre_proj" : "_fwd_pre") : POST ? "_fwd_proj" : "_fwd") : LNB ? "_bwd_ln" : "_bwd") +
-                                 "<d128,dff512,bf16x" + std::to_string(P * (P + 1) / 2) + ">";
+  // like the epilogue kinds of gemm_wsx)
+  static const std::string tag = "ffn_fused<d128,dff512,bf16x" + std::to_string(P * (P + 1) / 2) + ">";
   const double live = skf_prof_list_fraction(p.row_blocks);
   const double flops = 2.0 * 2.0 * p.M * FD * FF + (POST ? 2.0 * p.M * FD * p.n2 : 0.0) + (PRE ? 2.0 * p.M * FD * FD : 0.0);
   const double bytes = 4.0 * ((double)p.M * FD * (MODE == 0 ? 4 : 3) + (double)p.M * FF + (POST ? (double)p.M * p.n2 : 0.0) + (PRE ? 4.0 * p.M * FD : 0.0)) + 2.0 * image_bytes(P) / 2;
@@ -997,11 +933,6 @@ int skf_ffn_fused_launch(const FfnFusedParams& p, int pieces, int direction, hip
   return direction == 0 ? launch_ffn<3, 0>(p, st) : launch_ffn<3, 1>(p, st);
 }
 
-#if SKF_FFN_STAMPS
-extern "C" int skf_ffn_debug_stamps(long long* out_host) {   // diagnostics builds only
-  return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_ffn_stamps), sizeof(long long) * 16 * 64) == hipSuccess ? 0 : 1;
-}
-#endif
 // ---------------------------------------------------------------- C ABI
 extern "C" int skf_ffn_fused_supported(int M, int d, int dff, int precision) {
   return (precision == SKF_PREC_BF16X6 || precision == SKF_PREC_BF16X3) && d == FD && dff == FF && M >= 1 && (double)M * FF * 4 < 2147483648.0;

@@ -173,13 +173,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     const bool more = kt + 1 < nk;
-    if (more && p.ablate != 3) {
+    if (more) {
       load_slab<BM, A_KC, VEC>(p.A, p.lda, m0, p.M, kb + (kt + 1) * BK, ke, ra);
       load_slab<BN, B_KC, VEC>(p.B, p.ldb, n0, p.N, kb + (kt + 1) * BK, ke, rb);
     }
     const float* Ac = As + cur * A_SZ;
     const float* Bc = Bs + cur * B_SZ;
-    if (p.ablate != 1)
 #pragma unroll
     for (int kp = 0; kp < BK / 2; ++kp) {
       const int k = 2 * kp + lhi;
@@ -235,7 +234,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
         const int row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
         if (row >= p.M) continue;
         float v = acc[i][j][r] + bv;
-        if (p.ablate == 2 && v != 12345.678f) continue;
         if (p.act == 1) v = fmaxf(v, 0.f);
         else if (p.act == 2) v = tanhf(v);
         if (p.relu_src && !(p.relu_src[(size_t)row * p.ld_relu + col] > 0.f)) v = 0.f;
@@ -344,8 +342,7 @@ extern "C" size_t skf_gemm_workspace_bytes(int M, int N, int K, int splits, int 
 extern "C" int skf_gemm_default_splits(int M, int N, int K) {
   const int tiles = skf_cdiv(M, 64) * skf_cdiv(N, 64);
   if (K <= 512) return 1;
-  static const int wgs = skf_knob("SKF_WGRAD_WGS") ? atoi(skf_knob("SKF_WGRAD_WGS")) : 256;
-  int splits = wgs / tiles;
+  int splits = 256 / tiles;      // ~one workgroup per CU
   const int max_splits = skf_cdiv(K, 8 * BK);   // at least 8 slabs per split
   if (splits > max_splits) splits = max_splits;
   return splits < 1 ? 1 : splits;
@@ -556,9 +553,6 @@ extern "C" int skf_gemm_ln_residual_f32(int M, int N, int K, const float* A, int
   p.a_vec = 1; p.b_vec = ((ldw & 3) == 0) && (((uintptr_t)W & 15) == 0);
   p.ln_x = x; p.ln_gamma = gamma; p.ln_beta = beta; p.ln_out = out; p.ln_stats = stats;
   p.ln_rate = rate; p.ln_site = site; p.ln_state = step_state;
-#if SKF_MEASURE
-  { const char* db = skf_knob("SKF_GEMM_DBG"); p.dbg = db ? (long long*)strtoull(db, nullptr, 0) : nullptr; }
-#endif
   return skf_gemm_wsx_launch(p, 0, precision == SKF_PREC_BF16X3 ? 2 : 3, (hipStream_t)stream);
 }
 
@@ -603,11 +597,6 @@ extern "C" int skf_gemm_f32_bits(int a_kcontig, int b_kcontig, int M, int N, int
   p.a_vec = ((lda & 3) == 0) && (((uintptr_t)A & 15) == 0);
   p.b_vec = ((ldb & 3) == 0) && (((uintptr_t)B & 15) == 0);
   p.tiles_m = skf_cdiv(M, 128); p.tiles_n = skf_cdiv(N, 128);
-  { const char* ab = skf_knob("SKF_GEMM_ABLATE"); p.ablate = ab ? atoi(ab) : 0; }
-  { const char* xr = skf_knob("SKF_WS_XCD"); p.xcd_remap = xr ? atoi(xr) : 0; }
-#if SKF_MEASURE
-  { const char* db = skf_knob("SKF_GEMM_DBG"); p.dbg = db ? (long long*)strtoull(db, nullptr, 0) : nullptr; }
-#endif
   SKF_CHECK_ARG(!bias_grad || !b_kcontig, "bias_grad needs B as [K][N]");
   {
     int handled = 0;
@@ -618,7 +607,10 @@ extern "C" int skf_gemm_f32_bits(int a_kcontig, int b_kcontig, int M, int N, int
     int handled = 0;
     int rc = skf_gemm_ws_dispatch(p, a_kcontig, b_kcontig, st, &handled);
     if (rc != SKF_OK || handled) return rc;
-    if (relu_bits_out || relu_bits_in) { skf_set_error("skf_gemm_f32_bits: the weight-stationary path is switched off"); return SKF_EUNSUPPORTED; }
+    if (relu_bits_out || relu_bits_in) {
+      skf_set_error("skf_gemm_f32_bits: the weight-stationary kernel declined the launch (relu_src needs 16-byte alignment and ld_relu %% 4 == 0)");
+      return SKF_EUNSUPPORTED;
+    }
     // 64-row tiles when 128-row tiles would leave most CUs idle
     if (p.tiles_m * p.tiles_n < 400 && M > 64) {
       p.tiles_m = skf_cdiv(M, 64);

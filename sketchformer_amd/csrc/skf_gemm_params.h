@@ -1,7 +1,6 @@
 // Shared between the generic tiled GEMM (skf_gemm.hip) and the weight-stationary one (skf_gemm_ws.hip).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <string>
 
 struct GemmParams {
@@ -19,8 +18,7 @@ struct GemmParams {
   float* slab;             // [splits][M][N] raw partial tiles (split-K only)
   float* colsum_slab;      // [splits][N] partial column sums of B (bias grad), or null
   int tiles_m, tiles_n;
-  long long* dbg;          // diagnostics only: per-phase s_memtime stamps of a few workgroups (-DSKF_MEASURE=1 builds only, env SKF_GEMM_DBG; always null in the shipped library)
-  int xcd_remap;           // ws kernel: XCD-contiguous logical ids (env SKF_WS_XCD, A/B knob)
+  int xcd_remap;           // split-arithmetic weight-stationary kernel: XCD-contiguous logical ids (launch_wsx decides from the shape)
   int precision;           // SKF_PREC_*: 0 fp32 MFMA, 6 / 3 = split fp32 operands on the bf16 matrix cores
   // Row-block list (skf_row_blocks_build): {n_live, n_blocks, live block ids ..., dead block ids ...} over blocks of
   // `row_block_rows` consecutive rows of the M (dgrad: output / A rows) or K (wgrad: contraction rows) dimension whose A
@@ -29,7 +27,6 @@ struct GemmParams {
   // tiles without a live 16-row block (dgrad form); every other kernel ignores it.
   const int* row_blocks;
   int row_block_rows;
-  int ablate;              // generic kernel, diagnostics only (env SKF_GEMM_ABLATE): 1 no MFMA, 2 no C store, 3 no global reload
   // ReLU sign bits (split-arithmetic weight-stationary kernels only; skf_gemm_relu_bits_bytes): a forward launch with
   // act = relu leaves one bit per output element ("> 0") in the layout of its own tiles - word [tile][column wave][r * NB + nb]
   // = ballot over the wave's lanes - and the input-gradient launch of the SAME (M, N, K) multiplies by them instead of

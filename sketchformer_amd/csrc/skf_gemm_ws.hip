@@ -106,23 +106,13 @@ __global__ __launch_bounds__(256, (K * NB <= 512 ? 2 : 1)) void gemm_ws_kernel(G
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, g = lane >> 4;
-  // the column groups of one worker read the same A tiles: consecutive logical ids -> same XCD / L2
-  const int logical = p.xcd_remap ? skf_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int group = logical % groups, worker = logical / groups;
+  // the column groups of one worker read the same A tiles and carry consecutive ids
+  const int group = (int)blockIdx.x % groups, worker = (int)blockIdx.x / groups;
   const int n_lane = group * 4 * CW + wave * CW + NB * i;   // first of this lane's NB columns
   const bool nok = n_lane < p.N;                            // N % NB == 0: all NB columns in or all out
   const int n_ld = nok ? n_lane : p.N - NB;                 // clamped: loads stay in bounds, stores are guarded
   const int ntiles = (p.M + TR - 1) / TR;
 
-  long long* dbg = (p.dbg && lane == 0 && wave == 0 && (blockIdx.x % 97) == 0 && blockIdx.x / 97 < 8) ? p.dbg + (blockIdx.x / 97) * 32 : nullptr;
-  int dbi = 0;
-#if SKF_WS_STAMPS   // per-phase s_memtime stamps (tools/ws_timeline.py); off by default: every conditional memory
-                    // operation in the tile loop makes the compiler's s_waitcnt vmcnt counts conservative
-#define SKF_STAMP() do { if (dbg && dbi < 32) dbg[dbi++] = clock64(); } while (0)
-#else
-#define SKF_STAMP() do { (void)dbg; (void)dbi; } while (0)
-#endif
-  SKF_STAMP();
   // per-lane byte offsets inside a tile (constant for the whole kernel)
   unsigned a_voff[NV], c_voff[4], h_voff[4];
 #pragma unroll
@@ -163,13 +153,9 @@ __global__ __launch_bounds__(256, (K * NB <= 512 ? 2 : 1)) void gemm_ws_kernel(G
   float bias_r[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) bias_r[nb] = p.bias ? p.bias[n_ld + nb] : 0.f;
-
-
-  SKF_STAMP();   // B loads issued
   ws_store_tile<K>(As, ra0);
   __syncthreads();
   ws_load_tile<K>(p.A, p.lda, p.M, tile + 2 * workers, a_voff, ra0);
-  SKF_STAMP();   // first A tile in LDS
 
   vecn cprev[4], hsrc[4], oacc[4];   // finished C fragment of the previous tile (+ its relu source / old C)
   // No branch around any memory operation of the tile loop: "nothing to do" cases use an empty descriptor
@@ -216,7 +202,6 @@ __global__ __launch_bounds__(256, (K * NB <= 512 ? 2 : 1)) void gemm_ws_kernel(G
     __builtin_amdgcn_sched_barrier(0);
     store_prev();
     __builtin_amdgcn_sched_barrier(0);
-    SKF_STAMP();   // previous C tile stored
     f32x4 acc[NB][NACC];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
@@ -259,7 +244,6 @@ __global__ __launch_bounds__(256, (K * NB <= 512 ? 2 : 1)) void gemm_ws_kernel(G
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    SKF_STAMP();   // MFMAs issued
     // lane (i,g) holds C[row 4g+r][n_lane + nb]; one wave-uniform activation switch per tile
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -282,7 +266,6 @@ __global__ __launch_bounds__(256, (K * NB <= 512 ? 2 : 1)) void gemm_ws_kernel(G
     }
     prev_tile = tile;
     if (!EARLY) __syncthreads();
-    SKF_STAMP();   // barrier
   };
   while (tile < ntiles) {
     do_tile(0, ra1, afA, afB);
@@ -299,7 +282,7 @@ int launch_ws(const GemmParams& p, int b_kc, hipStream_t st) {
   constexpr int CW = 16 * NB;
   const int groups = skf_cdiv(p.N, 4 * CW);
   // two workgroups per CU where the register budget allows it (K*NB <= 512), else one
-  static const int wg_target = skf_knob("SKF_WS_WGS") ? atoi(skf_knob("SKF_WS_WGS")) : (K * NB <= 512 ? 512 : 256);
+  constexpr int wg_target = K * NB <= 512 ? 512 : 256;
   int workers = wg_target / groups;
   if (workers < 1) workers = 1;
   const int ntiles = skf_cdiv(p.M, TR);

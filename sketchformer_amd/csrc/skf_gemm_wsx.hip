@@ -17,7 +17,6 @@
 // Small products go to their own accumulator (added to the a0.b0 sum at the end).
 #include "skf_common.h"
 #include "skf_gemm_params.h"
-#include <set>
 
 namespace {
 
@@ -30,18 +29,10 @@ __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
 }
 
 constexpr int TR = 16;   // rows per tile
-#ifndef SKF_WSX_EARLY3
-#define SKF_WSX_EARLY3 0   // 1: K = 128 keeps two full fragment sets also in the three-piece mode (register ring of 2)
-#endif
 
 // gfx950 hides about one VALU / LDS / VMEM instruction per v_mfma_f32_16x16x32_bf16 of the SAME wave and almost none
 // of another wave's (tools/micro/mfma_bf16_valu_overlap.hip), so the tile body is left to the scheduler as one region
-// (no fences between its phases) unless SKF_WSX_FENCES is defined.
-#ifdef SKF_WSX_FENCES
-#define SKF_WSX_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define SKF_WSX_SCHED_BARRIER() do { } while (0)
-#endif
+// (no fences between its phases).
 
 template <int N> struct VecOfX;
 template <> struct VecOfX<1> { typedef float type; typedef unsigned utype; };
@@ -77,9 +68,6 @@ template <int P> __device__ __forceinline__ void split2(float x, float y, unsign
 template <int K, int KS = 1>
 __device__ __forceinline__ void wsx_load_tile(const float* __restrict__ A, int lda, int M, int tile,
                                               const unsigned (&a_voff)[TR * K / (1024 * KS)], f32x4 (&ra)[TR * K / (1024 * KS)], int cut = 0) {
-#ifdef SKF_WSX_ABLATE_LOAD   // diagnostics: every A tile load hits the same (cached) rows
-  tile &= 7;
-#endif
   const __amdgpu_buffer_rsrc_t r = wsx_rows_rsrc(A, lda, M, tile * TR, cut);
 #pragma unroll
   for (int v = 0; v < TR * K / (1024 * KS); ++v)
@@ -132,7 +120,7 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
   static_assert(EXTRA == 0 || EXTRA == 2 || EXTRA == 3, "epilogue kinds: none, sign bits only, general");
   static_assert(KS == 1 || (KS == 2 && K >= 256 && !LNF), "contraction split: two halves, K >= 256");
   static_assert(!LNF || (K == 128 && NB == 2 && !EXTRA && !KMASK), "LayerNorm epilogue: K = 128, two columns per lane, plain launch");
-  constexpr bool EARLY = !LNF && K == 128 && (P == 2 || NB == 4 || SKF_WSX_EARLY3);   // every fragment of a tile in registers: barrier inside the MFMA stream
+  constexpr bool EARLY = !LNF && K == 128 && (P == 2 || NB == 4);   // every fragment of a tile in registers: barrier inside the MFMA stream
   constexpr int PF = EARLY ? NF : (NF < 6 ? NF : 6);
   constexpr int NCH = NB == 1 ? 2 : 1;   // accumulator chains per column block
   constexpr int PITCH = 2 * K + 32;      // bytes per LDS row.  ds_read_b128 is served in four groups of 16 lanes that MIX the lane
@@ -183,17 +171,6 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { ln_g[nb] = p.ln_gamma[n_ld + nb]; ln_b[nb] = p.ln_beta[n_ld + nb]; }
   }
-  long long* dbg = (p.dbg && lane == 0 && wave_all == 0 && (blockIdx.x % 64) == 0 && blockIdx.x / 64 < 8) ? p.dbg + (blockIdx.x / 64) * 32 : nullptr;   // same XCD: comparable clocks
-  int dbi = 0;
-#if SKF_WS_STAMPS   // per-phase s_memtime stamps (tools/ws_timeline.py); off by default
-#define SKF_STAMP() do { if (dbg && dbi < 30) dbg[dbi++] = clock64(); } while (0)
-#else
-#define SKF_STAMP() do { (void)dbg; (void)dbi; } while (0)
-#endif
-#if SKF_WS_STAMPS
-  const long long wall0 = wall_clock64(), cyc0 = clock64();   // 100 MHz constant clock vs shader clock
-#endif
-  SKF_STAMP();
   unsigned a_voff[NV], c_voff[4], h_voff[4];
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
@@ -254,11 +231,9 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
   for (int nb = 0; nb < NB; ++nb) bias_r[nb] = (p.bias && kh == 0) ? p.bias[n_ld + nb] : 0.f;
 
   const uint32_t ln_sk = (LNF && p.ln_rate > 0.f) ? skf_site_key(ln_key, p.ln_site) : 0u;
-  SKF_STAMP();   // weight slice loaded + split
   wsx_store_tile<K, P, PITCH, KS>(As, ra[0], sel);
   __syncthreads();
   wsx_load_tile<K, KS>(p.A, p.lda, p.M, phys(tile + R * workers), a_voff, ra[0], a_cut);
-  SKF_STAMP();   // first A tile in LDS
 
   vecn cprev[4], hsrc[4], oacc[4];
   vecn xresA[LNF ? 4 : 1], xresB[LNF ? 4 : 1];                    // LNF: residual rows of this tile and of the next one (requested a tile ahead:
@@ -321,9 +296,6 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
           for (int nb = 0; nb < NB; ++nb) reinterpret_cast<float*>(&v)[nb] += reinterpret_cast<const float*>(&oacc[r])[nb];
         }
       }
-#ifdef SKF_WSX_ABLATE_STORE   // diagnostics: only the first tile's stores reach memory
-      if (prev_tile < workers)
-#endif
       wsx_buf_store<NB>(v, rc, c_voff[r]);
     }
   };
@@ -346,10 +318,7 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
 #pragma unroll
       for (int f = 0; f < PF; ++f) af[f] = *reinterpret_cast<const u32x4*>(At + (f % P) * TR * PITCH + 64 * (f / P));
     }
-    SKF_WSX_SCHED_BARRIER();
     store_prev();
-    SKF_WSX_SCHED_BARRIER();
-    SKF_STAMP();   // previous C tile stored
     // One accumulator chain per column block (two for NB = 1: a dependent MFMA straight behind its producer stalls):
     // the small products first, the a0.b0 products last - small-to-large summation, no separate add.
     f32x4 acc[NB][NCH];
@@ -382,26 +351,15 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
         for (int qa = 0; qa <= d; ++qa) {
           const int qb = d - qa;
 #pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
-#ifdef SKF_WSX_ABLATE_MFMA   // diagnostics: wrong results; keeps every operand live with one VALU op per 4 MFMAs
-            if ((c & 3) == 0 && nb == 0) acc[nb][c % NCH][0] += __builtin_bit_cast(float, a[qa][0] ^ bq[nb][s][qb][0]);
-#else
-            acc[nb][c % NCH] = mfma_bf16(a[qa], bq[nb][s][qb], acc[nb][c % NCH]);
-#endif
-          }
+          for (int nb = 0; nb < NB; ++nb) acc[nb][c % NCH] = mfma_bf16(a[qa], bq[nb][s][qb], acc[nb][c % NCH]);
           ++c;
         }
       if (!TWO_PHASE) {
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-#ifndef SKF_WSX_ABLATE_MFMA
-          acc[nb][c % NCH] = mfma_bf16(a[0], bq[nb][s][0], acc[nb][c % NCH]);
-#endif
-        }
+        for (int nb = 0; nb < NB; ++nb) acc[nb][c % NCH] = mfma_bf16(a[0], bq[nb][s][0], acc[nb][c % NCH]);
         ++c;
       }
       if (s == NKS / 2 - 1) {
-        SKF_WSX_SCHED_BARRIER();
         wsx_store_tile<K, P, PITCH, KS>(As + (cur ^ 1) * TILE_B, rn, sel);
         wsx_load_tile<K, KS>(p.A, p.lda, p.M, phys(tile + (R + 1) * workers), a_voff, rn, a_cut);
         if constexpr (LNF) {
@@ -432,7 +390,6 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
           for (int j = 0; j < 4 * NB; ++j) mbits[j] = wp[j];
           }
         }
-        SKF_WSX_SCHED_BARRIER();
       }
       if (EARLY && s == (3 * NKS) / 4 - 1) {
         __builtin_amdgcn_sched_barrier(0);
@@ -447,15 +404,10 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
 #pragma unroll
       for (int s = 0; s < NKS; ++s) {        // the a0.b0 products
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-#ifndef SKF_WSX_ABLATE_MFMA
-          acc[nb][c % NCH] = mfma_bf16(a0keep[s], bq[nb][s][0], acc[nb][c % NCH]);
-#endif
-        }
+        for (int nb = 0; nb < NB; ++nb) acc[nb][c % NCH] = mfma_bf16(a0keep[s], bq[nb][s][0], acc[nb][c % NCH]);
         ++c;
       }
     }
-    SKF_STAMP();   // MFMAs issued
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -529,7 +481,6 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
     }
     prev_tile = phys(tile);
     if (!EARLY) __syncthreads();
-    SKF_STAMP();   // tile done
   };
   constexpr int U = (R & 1) ? 2 * R : R;   // unroll: LDS buffer parity x ring position (written out: a `for` with
                                            // a break is not unrolled and would index the ring dynamically)
@@ -557,18 +508,13 @@ __global__ __launch_bounds__(256 * KS, (KS == 2 || (K <= 256 && NB <= 2) ? 2 : 1
       for (int r = 0; r < 4; ++r) wsx_buf_store<NB>(zero, rz, c_voff[r]);
     }
   }
-  SKF_STAMP();
-#if SKF_WS_STAMPS
-  if (dbg) { dbg[30] = wall_clock64() - wall0; dbg[31] = clock64() - cyc0; }
-#endif
-#undef SKF_STAMP
 }
 
 template <int K, int NB, int P, int KS = 1>
 int launch_wsx(const GemmParams& p, int b_kc, hipStream_t st) {
   constexpr int CW = 16 * NB;
   const int groups = skf_cdiv(p.N, 4 * CW);
-  static const int wg_target = skf_knob("SKF_WS_WGS") ? atoi(skf_knob("SKF_WS_WGS")) : (KS == 1 && K <= 256 && NB <= 2 ? 512 : 256);
+  constexpr int wg_target = KS == 1 && K <= 256 && NB <= 2 ? 512 : 256;
   int workers = wg_target / groups;
   if (workers < 1) workers = 1;
   const int ntiles = skf_cdiv(p.M, TR);
@@ -593,22 +539,15 @@ int launch_wsx(const GemmParams& p, int b_kc, hipStream_t st) {
   const double live = skf_prof_list_fraction(q.row_blocks);
   const double a_c = (double)p.M * p.K + (double)p.M * p.N * ((p.accumulate ? 1 : 0) + (p.relu_src && !p.relu_bits_in ? 1 : 0));
   const double ln_c = p.ln_out ? 2.0 * p.M * p.N : 0.0;
-  // SKF_PROF_FINE=1 (analysis only): one table line per output width and epilogue
-  static const bool fine = skf_knob_is("SKF_PROF_FINE", '1');
-  static std::set<std::string> fine_tags;           // the profiler keeps the pointer: interned
-  const char* ftag = nullptr;
-  if (fine) ftag = fine_tags.insert(tag + "[N" + std::to_string(p.N) + (b_kc ? ",dgrad" : "") + (p.relu_bits_in ? ",bits" : "") + (p.relu_src ? ",relu_src" : "") +
-                   (p.accumulate ? ",acc" : "") + (q.row_blocks ? ",list" : "") + (p.act ? ",act" : "") + (p.ln_out ? ",ln" : "") + "]").first->c_str();
   // (the launches with the LayerNorm epilogue stay in their family's line - same kernel template, same product - as the rocprofv3
   //  kernel names that bench.py matches against do; their residual / LayerNorm bytes are counted)
-  SkfProfScope ps(st, fine ? ftag : tag.c_str(), 2.0 * p.M * p.N * p.K, 4.0 * (a_c + ln_c + (double)p.K * p.N + (double)p.M * p.N));
+  SkfProfScope ps(st, tag.c_str(), 2.0 * p.M * p.N * p.K, 4.0 * (a_c + ln_c + (double)p.K * p.N + (double)p.M * p.N));
   ps.done(2.0 * p.M * p.N * p.K * live, 4.0 * (a_c * live + ln_c + (double)p.K * p.N + (double)p.M * p.N));
   // K >= 384 (N = 128): the two column groups of a worker read the same A tiles - XCD-contiguous ids keep the second read
   // in the L2 (PMC: 132 -> ~80 MB per launch); with one or two groups of short tiles (K <= 256) the remap only costs
   // K = 128 with three or more column groups (N = 384 / 512 / 1004): round-robin ids put the group-mates of a worker on
   // different XCDs, i.e. every A tile is fetched into `groups` L2s (PMC, round 1: 1.55x the algorithmic bytes)
-  static const char* xcd_env = skf_knob("SKF_WS_XCD");     // "0" / "1" force it (measurement)
-  q.xcd_remap = xcd_env ? xcd_env[0] == '1' : (groups > 1 && (K >= 384 || groups >= 3));
+  q.xcd_remap = groups > 1 && (K >= 384 || groups >= 3);
   // tail audit (all four sites of launch_wsx): parked by run_backward around dense_dgrad / ln_oproj_bwd, whose last call is one skf_gemm_f32*.
   // launch_wsx is ONE launch and the last thing its entry points do (skf_gemm_ws_dispatch: single launch, or a chain that defers the event to its
   // last slice; skf_gemm_ln_residual_f32: single launch, nobody parks)
@@ -669,25 +608,18 @@ int launch_wsx_k(const GemmParams& p, int b_kc, hipStream_t st) {
     // (four columns per lane = 64 per wave, one workgroup per CU, was measured for N >= 256: 30.8 vs 28.7 us at N = 512 -
     //  one wave per SIMD loses more to exposed waits than the doubled MFMA : overhead ratio wins)
     case 128: return launch_wsx<128, 2, P>(p, b_kc, st);
-    case 256: {
-      // K = 256: only for N <= 128 (one or two column groups, 256 workgroups either way); with more column groups the 512-thread form
-      // was 4 % slower at cfg 3 (N = 256 ... 1024).  SKF_WSX_KSPLIT256=1 forces it for every N, =0 turns it off (measurement)
-      static const char* ks2 = skf_knob("SKF_WSX_KSPLIT256");
-      const bool ks_on2 = ks2 ? ks2[0] == '1' : (p.N <= 128 && !skf_knob_is("SKF_WSX_KSPLIT", '0'));
-      if (ks_on2 && p.act == 0) return launch_wsx<256, 1, P, 2>(p, b_kc, st);
+    // K >= 256 without an activation: the contraction split between wave pairs (two waves per SIMD)
+    case 256:
+      // only for N <= 128 (one or two column groups, 256 workgroups either way); with more column groups the 512-thread form
+      // was 4 % slower at cfg 3 (N = 256 ... 1024)
+      if (p.N <= 128 && p.act == 0) return launch_wsx<256, 1, P, 2>(p, b_kc, st);
       return launch_wsx<256, 1, P>(p, b_kc, st);
-    }
-    case 384: {
-      static const bool ks_off3 = skf_knob_is("SKF_WSX_KSPLIT", '0') || skf_knob_is("SKF_WSX_KSPLIT384", '0');
-      if (!ks_off3 && p.act == 0) return launch_wsx<384, 1, P, 2>(p, b_kc, st);
+    case 384:
+      if (p.act == 0) return launch_wsx<384, 1, P, 2>(p, b_kc, st);
       return launch_wsx<384, 1, P>(p, b_kc, st);
-    }
-    default: {
-      // K = 512 without an activation: the contraction split between wave pairs (two waves per SIMD); SKF_WSX_KSPLIT=0: A/B knob
-      static const bool ks_off = skf_knob_is("SKF_WSX_KSPLIT", '0');
-      if (!ks_off && p.act == 0) return launch_wsx<512, 1, P, 2>(p, b_kc, st);
+    default:
+      if (p.act == 0) return launch_wsx<512, 1, P, 2>(p, b_kc, st);
       return launch_wsx<512, 1, P>(p, b_kc, st);
-    }
   }
 }
 

@@ -20,23 +20,13 @@ __device__ __forceinline__ float2 skf_ld2(const skf_bf16* p, size_t i) {
   return r;
 }
 
-#ifndef SKF_LN_FWD_GRID
-#define SKF_LN_FWD_GRID 2048
-#endif
-#ifndef SKF_LN_BWD_GRID
-#define SKF_LN_BWD_GRID 640    // more workgroups shorten the kernel (15.4 -> 14.7 us) but lengthen the batched reduction of their partials
-#endif
-#ifndef SKF_LN_UR
-#define SKF_LN_UR 1            // row groups in flight per wave iteration (2 measured 0.3-0.5 us slower per launch in the step)
-#endif
-#ifndef SKF_LN_BWD_THREADS
-#define SKF_LN_BWD_THREADS 256 // threads per workgroup of the LayerNorm backward: more waves per workgroup = more bytes in flight per CU
-#endif                         // at the same number of dgamma / dbeta partial rows (one per workgroup)
-#ifndef SKF_LN_BWD_UR
-#define SKF_LN_BWD_UR SKF_LN_UR
-#endif
-constexpr int kMaxGrid = SKF_LN_FWD_GRID;
-constexpr int kLnBwdGrid = SKF_LN_BWD_GRID;    // workgroups of the LayerNorm backward (each leaves one [2][d] partial for the column sums)
+constexpr int kMaxGrid = 2048;       // (4096: 4.65 against 4.64 ms/step, profiles/r03f_flag_sweep_ln_bwd.txt)
+constexpr int kLnBwdGrid = 640;      // workgroups of the LayerNorm backward (each leaves one [2][d] partial for the column sums): more
+                                     // shorten the kernel (15.4 -> 14.7 us) but lengthen the batched reduction of their partials
+constexpr int kLnUr = 1;             // row groups in flight per wave iteration (2 measured 0.3-0.5 us slower per launch in the step)
+constexpr int kLnBwdUr = kLnUr;
+constexpr int kLnBwdThreads = 256;   // threads per workgroup of the LayerNorm backward: more waves per workgroup = more bytes in flight per
+                                     // CU at the same number of dgamma / dbeta partial rows (one per workgroup)
 
 __global__ void padding_mask_kernel(const long long* __restrict__ tok, int tok_ld, int B, int L,
                                     unsigned char* __restrict__ out) {
@@ -418,7 +408,7 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(const float* __restrict_
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         float* __restrict__ out, float* __restrict__ stats, int rows,
                                                         float rate, uint32_t site, const SkfStepState* st) {
-  constexpr int D = 4 * LPR, RPW = 64 / LPR, UR = SKF_LN_UR;
+  constexpr int D = 4 * LPR, RPW = 64 / LPR, UR = kLnUr;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane % LPR, rsel = lane / LPR;
   const uint32_t thresh = skf_drop_thresh(rate);
@@ -534,14 +524,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
   }
 }
 
-// Same, D = 4*LPR <= 256: 16-byte loads, 64/LPR rows per wave instruction, SKF_LN_UR groups in flight (see ln_fwd_v4_kernel).
+// Same, D = 4*LPR <= 256: 16-byte loads, 64/LPR rows per wave instruction, kLnUr groups in flight (see ln_fwd_v4_kernel).
 template <int LPR>
-__global__ __launch_bounds__(SKF_LN_BWD_THREADS) void ln_bwd_v4_kernel(const float* __restrict__ dout, const float* __restrict__ z,
+__global__ __launch_bounds__(kLnBwdThreads) void ln_bwd_v4_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                         const float* __restrict__ stats, const float* __restrict__ gamma,
                                                         float* __restrict__ dz, float* __restrict__ dy,
                                                         float* __restrict__ part, int rows, float rate, uint32_t site,
                                                         const SkfStepState* st, const int* __restrict__ live_len, int rps) {
-  constexpr int D = 4 * LPR, RPW = 64 / LPR, UR = SKF_LN_BWD_UR, NWV = SKF_LN_BWD_THREADS / 64;
+  constexpr int D = 4 * LPR, RPW = 64 / LPR, UR = kLnBwdUr, NWV = kLnBwdThreads / 64;
   __shared__ float red[NWV][2][D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane % LPR, rsel = lane / LPR;
@@ -640,7 +630,7 @@ __global__ __launch_bounds__(SKF_LN_BWD_THREADS) void ln_bwd_v4_kernel(const flo
     *reinterpret_cast<f32x4*>(&red[wave][1][4 * sub]) = db;
   }
   __syncthreads();
-  for (int e = threadIdx.x; e < 2 * D; e += SKF_LN_BWD_THREADS) {
+  for (int e = threadIdx.x; e < 2 * D; e += kLnBwdThreads) {
     const int w = e / D, c = e % D;
     float t = red[0][w][c];
 #pragma unroll
@@ -1303,7 +1293,7 @@ extern "C" int skf_layernorm_residual_fwd(const float* x, float* y_inout_z, cons
   SkfProfScope ps(s, "ln_fwd", 0.0, 16.0 * rows * d);
   const bool al = ((((uintptr_t)x | (uintptr_t)y_inout_z | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0);
   if (al && (d == 64 || d == 128 || d == 256)) {
-    const int rpi = (64 / (d / 4)) * SKF_LN_UR * 4;               // rows per workgroup iteration
+    const int rpi = (64 / (d / 4)) * kLnUr * 4;               // rows per workgroup iteration
     int g = skf_cdiv(rows, rpi); if (g > kMaxGrid) g = kMaxGrid;
     if (d == 64) hipLaunchKernelGGL(ln_fwd_v4_kernel<16>, dim3(g), block, 0, s, x, y_inout_z, gamma, beta, out, stats, rows, rate, site, st);
     else if (d == 128) hipLaunchKernelGGL(ln_fwd_v4_kernel<32>, dim3(g), block, 0, s, x, y_inout_z, gamma, beta, out, stats, rows, rate, site, st);
@@ -1353,7 +1343,7 @@ extern "C" int skf_layernorm_residual_bwd_rows(const float* dout, const float* z
   SkfProfScope ps(s, "ln_bwd", 0.0, (rate > 0.f ? 16.0 : 12.0) * rows * d);
   const bool al = ((((uintptr_t)dout | (uintptr_t)z | (uintptr_t)dz | (uintptr_t)dyp | (uintptr_t)gamma) & 15) == 0) &&
                   (double)rows * d * 4 < 2147483648.0;             // (the v4 kernel stores through 32-bit buffer offsets)
-  const dim3 block4(SKF_LN_BWD_THREADS);
+  const dim3 block4(kLnBwdThreads);
   if (al && d == 64) hipLaunchKernelGGL(ln_bwd_v4_kernel<16>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
   else if (al && d == 128) hipLaunchKernelGGL(ln_bwd_v4_kernel<32>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);
   else if (al && d == 256) hipLaunchKernelGGL(ln_bwd_v4_kernel<64>, grid, block4, 0, s, dout, z, stats, gamma, dz, dyp, part, rows, rate, site, st, live_len, rows_per_sample);

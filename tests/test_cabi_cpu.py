@@ -108,26 +108,41 @@ def test_config_struct_size_guard(lib):
 
 
 def test_shipped_library_reads_no_environment():
-    """include/skf.h: 'no global state'.  The default build must not call getenv at all (A/B and ablation knobs live behind
-    -DSKF_MEASURE=1, skf_common.h: skf_knob), and no source may turn an environment string into a device pointer outside it."""
+    """include/skf.h: 'no global state'.  No source of the library calls getenv, turns a string into a device pointer or names the
+    knob reader / measurement build that once did (there is one build of the library), and the library does not import getenv."""
     import glob
     import subprocess
     csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
-    for path in glob.glob(os.path.join(csrc, "*")):
-        text = open(path).read()
-        if path.endswith("skf_common.h"):
-            assert text.count("getenv(") == 1          # the one inside `#if SKF_MEASURE`
-            continue
-        assert "getenv(" not in text, path
-        for m in re.finditer(r"strtoull\(", text):
-            before = text[:m.start()]
-            assert before.rfind("#if SKF_MEASURE") > before.rfind("#endif"), "%s: strtoull outside an SKF_MEASURE block" % path
-    from sketchformer_amd import build
-    if "-DSKF_MEASURE=1" in build.FLAGS:
-        pytest.skip("measurement build")
+    paths = glob.glob(os.path.join(csrc, "*"))
+    assert len(paths) > 30
+    for path in paths:
+        text = open(path, encoding="utf-8").read()
+        for gone in ("getenv(", "strtoull(", "skf_knob", "SKF_MEASURE"):
+            assert gone not in text, "%s: %s" % (path, gone)
     syms = subprocess.run(["nm", "-D", "--undefined-only", os.path.join(ROOT, "sketchformer_amd", "libskf.so")],
                           capture_output=True, text=True, check=True).stdout
     assert not re.search(r"\bU (secure_)?getenv\b", syms), "libskf.so imports getenv"
+
+
+def test_kernel_parameter_blocks_have_no_diagnostic_members():
+    """AttnParams / GemmParams carry operands and shapes only: no `ablate` / `dbg` member for a shipped kernel to branch on."""
+    csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
+    for name in ("skf_attention_params.h", "skf_gemm_params.h"):
+        text = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, name), encoding="utf-8").read())
+        assert re.search(r"struct (AttnParams|GemmParams) \{", text), name
+        m = re.search(r"\b(ablate|dbg)\b\s*[;,=\[]", text)
+        assert m is None, "%s declares %s" % (name, m.group(1))
+
+
+def test_library_sources_have_no_build_time_switch():
+    """No #if / #ifdef / #ifndef / #elif on an SKF_ name in csrc/ (the headers use #pragma once): one build, no -D experiments."""
+    import glob
+    csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
+    paths = glob.glob(os.path.join(csrc, "*"))
+    assert len(paths) > 30
+    for path in paths:
+        for ln in open(path, encoding="utf-8").read().splitlines():
+            assert not re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b.*\bSKF_", ln), "%s: %s" % (path, ln.strip())
 
 
 _RETIRED_KNOBS = (
@@ -138,6 +153,15 @@ _RETIRED_KNOBS = (
     "SKF_TAIL_WGRAD_SIDE", "SKF_MID_FLUSH", "SKF_DECODE_GRAPH", "SKF_NO_STAGE_KERNEL", "SKF_NO_STAGED_MASKS",
     "SKF_NO_SIDE_STREAM", "SKF_NO_SIDE_PREAMBLE",
     "SKF_GEMM_NO_SMALL", "SKF_GEMM_NO_WGRAD", "SKF_NO_WGRAD_GROUP", "SKF_GEMM_NO_WS", "SKF_NO_MASKED_CHAIN", "SKF_LN_V4",
+    # the kernels' and launchers' environment knobs ...
+    "SKF_ATTN_XCD", "SKF_ATTN_ABLATE", "SKF_ATTN_DBG", "SKF_ATTN_BWD2", "SKF_ATTN_BWD3", "SKF_ATTN_SPLIT", "SKF_GEMM_DBG", "SKF_GEMM_ABLATE",
+    "SKF_WS_XCD", "SKF_WS_WGS", "SKF_WGRAD_WGS", "SKF_PROF_FINE", "SKF_WSX_KSPLIT", "SKF_WSX_KSPLIT256", "SKF_WSX_KSPLIT384",
+    "SKF_BF16_GEMM_TILE", "SKF_BF16_GEMM_DMA", "SKF_BF16_GEMM_PH8",
+    # ... and their -D names and stamp macros
+    "SKF_MEASURE", "SKF_WGRAD_PIPE", "SKF_WGRAD_OCC", "SKF_WG_ABLATE_SPLIT", "SKF_WG_ABLATE_LOAD", "SKF_WSX_ABLATE_LOAD", "SKF_WSX_ABLATE_STORE",
+    "SKF_WSX_ABLATE_MFMA", "SKF_WSX_FENCES", "SKF_WSX_EARLY3", "SKF_WS_STAMPS", "SKF_FFN_ABLATE", "SKF_FFN_STAMPS", "SKF_PH8_ABLATE",
+    "SKF_SPLIT_NO_DOT2", "SKF_ATTN_BWD_WAVES", "SKF_ATTN_BWD_TRP", "SKF_LN_FWD_GRID", "SKF_LN_BWD_GRID", "SKF_LN_UR", "SKF_LN_BWD_THREADS",
+    "SKF_LN_BWD_UR", "SKF_DEC_UNROLL", "SKF_STAMP", "SKF_STAMP3", "SKF_FSTAMP", "FFN_STAMP",
 )
 
 
@@ -147,9 +171,11 @@ _MODEL_UNITS = ("skf_model", "skf_model_prof", "skf_model_layout", "skf_model_sc
 
 
 def test_train_step_schedule_has_no_knobs():
-    """The train step's stream / event schedule and the Dense / LayerNorm routing are fixed: the A/B knobs that once switched
-    them (even in measurement builds) are gone, the step's orchestrator reads no knob at all, and the integration guide and the
-    knob table of tools/ do not name the retired ones."""
+    """The train step's stream / event schedule, the Dense / LayerNorm routing and the kernels' dispatch are fixed: the A/B knobs
+    that once switched them are gone, and neither the library's sources and public header, the integration guide, the knob table of
+    tools/ nor a tool (a script that still sets a dead variable or passes a dead -D) names a retired one.  The names are matched as
+    whole words, also straight behind `-D`: no live identifier is one of them (SKF_ATTN_TWO_PASS, SKF_EXTRA_HIPCC_FLAGS, the
+    SKF_MODEL_* flags and SKF_PREC_* stay)."""
     import glob
     csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
     units = sorted(os.path.basename(p) for p in glob.glob(os.path.join(csrc, "skf_model*")))
@@ -158,9 +184,12 @@ def test_train_step_schedule_has_no_knobs():
     assert "skf_model_internal.h" in units
     for name in units:
         assert "skf_knob(" not in open(os.path.join(csrc, name)).read(), name
-    pattern = re.compile(r"\b(%s)\b" % "|".join(_RETIRED_KNOBS))
-    docs = [os.path.join(ROOT, "INTEGRATION.md"), os.path.join(ROOT, "tools", "README.md")]
-    for path in glob.glob(os.path.join(csrc, "*")) + docs:
+    pattern = re.compile(r"(?:\b|(?<=-D))(%s)\b" % "|".join(_RETIRED_KNOBS))
+    assert pattern.search("hipcc -DSKF_MEASURE=1") and pattern.search("SKF_WS_XCD=0") and not pattern.search("SKF_ATTN_TWO_PASS SKF_EXTRA_HIPCC_FLAGS")
+    docs = [os.path.join(ROOT, "INTEGRATION.md"), os.path.join(ROOT, "tools", "README.md"), os.path.join(ROOT, "include", "skf.h")]
+    tools = [p for p in glob.glob(os.path.join(ROOT, "tools", "*")) if os.path.splitext(p)[1] in (".py", ".sh")]
+    assert len(tools) > 40, tools
+    for path in glob.glob(os.path.join(csrc, "*")) + docs + tools:
         m = pattern.search(open(path, encoding="utf-8").read())
         assert m is None, "%s names the retired knob %s" % (path, m.group(1))
 

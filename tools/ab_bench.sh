@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (on the GPU box): tools/ab_bench.sh <tag> "<ENV=1 for variant B>" [rounds]  - interleaved A/B of the headline step time
+# usage (on the GPU box): tools/ab_bench.sh <tag> "<VAR=value for variant B>" [rounds]  - interleaved A/B of the headline step time (Python-layer variables: the library reads none)
 tag=$1; envb=$2; rounds=${3:-3}
 for r in $(seq 1 $rounds); do
   for v in A B; do

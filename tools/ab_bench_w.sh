@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (on the GPU box): tools/ab_bench_w.sh <tag> <workload> "<ENV=1 for variant B>" [rounds] [steps] - interleaved A/B of one workload's step time
+# usage (on the GPU box): tools/ab_bench_w.sh <tag> <workload> "<VAR=value for variant B>" [rounds] [steps] - interleaved A/B of one workload's step time
 tag=$1; wl=$2; envb=$3; rounds=${4:-2}; steps=${5:-30}
 for r in $(seq 1 $rounds); do
   for v in A B; do

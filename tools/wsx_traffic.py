@@ -55,7 +55,6 @@ def pmc_mode(out):
                        "algorithmic_bytes": alg, "ratio": meas / alg, "fetch_over_algorithmic_reads": 2048.0 * vals["FETCH_SIZE"] / (4.0 * (M * K + K * N))}
         print(N, res[str(N)])
     res["what"] = "gemm_wsx<K128> M=25600, per-launch HBM bytes (rocprofv3 --pmc, separate FETCH_SIZE / WRITE_SIZE passes) vs algorithmic"
-    res["xcd_env"] = os.environ.get("SKF_WS_XCD", "rule")
     json.dump(res, open(out, "w"), indent=1)
 
 
