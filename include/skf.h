@@ -862,6 +862,45 @@ int skf_kmeans_step_f32(const float* points, int ldp, long long N, int d, float*
 int skf_interpolate_f32(const float* a, int lda, const float* b, int ldb, int P, int d, const float* t, int T, int mode,
                         float* out, int ldo, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Embedding map (exact t-SNE)
+ * The t-SNE map of the evaluation (metrics/visualisation.py of the reference asks sklearn.manifold.TSNE for it): the exact O(N^2)
+ * algorithm of van der Maaten & Hinton (2008) with the semantics of scikit-learn's method='exact', no Barnes-Hut.  Nothing here
+ * allocates or synchronises with the host; every sum has a fixed order (no floating-point atomic), so two calls on the same
+ * inputs agree bit for bit.  workspace: skf_tsne_workspace_bytes(N) bytes (0 = bad N), 16-byte aligned; its contents carry nothing
+ * from one call to the next.
+ * skf_tsne_affinities_f32: x (N, d) fp32 -> the joint probabilities P (N, N) fp32 and, when beta != NULL, the N precisions (fp64).
+ *   The distance of a pair is DEFINED as D_ij = sum_k (x_ik - x_jk)^2 in fp32, acc = fmaf(diff, diff, acc) over k ascending from
+ *   acc = 0: direct differences, so D_ii == 0 and D_ij == D_ji bit for bit.  Row i is searched over j != i with
+ *   e_j = (double)D_ij - (double)min_{j != i} D_ij, p_j = exp(-beta e_j), S = sum p_j, H = log S + beta sum e_j p_j / S, all fp64:
+ *   beta starts at 1 with bounds (0, inf); 64 evaluations, none skipped; after each, H > log(perplexity) makes beta the lower bound
+ *   and doubles it while no upper bound exists, else moves it to the middle of the bounds; otherwise beta becomes the upper bound
+ *   and moves to the middle.  beta_i and S_i are those of the 64th evaluation.  Entries with D_ij == 0 (duplicates of row i) are
+ *   counted into S as exact ones instead of being added in place, so identical rows of x get identical beta and S.  The sign of
+ *   H - log(perplexity) is taken from that expression while S <= 0.75 n (n = N - 1), and above it - a row near uniformity, where
+ *   log S and beta sum e p / S cancel - from the identical log(n / perplexity) - (1 / n) sum_j f(x_j), f(x) = (1 + x) log(1 + x) - x,
+ *   x_j = n p_j / S - 1 = (expm1(-beta e_j) - m) / (1 + m), m = mean_j expm1(-beta e_j): every term is non-negative, so the sign
+ *   is exact down to beta = 2^-63 (perplexity = N - 1 ends there) instead of following rounding noise.  The conditional
+ *   is p_{j|i} = exp(-beta_i e_j) / S_i in fp64 and P_ij = (float)((p_{j|i} + p_{i|j}) / (2 N)): P_ii == 0, P_ij == P_ji bit for bit.
+ *   Limits (SKF_EINVAL): 3 <= N <= 8192, 4 <= d <= 1024, d % 4 == 0, 1 <= perplexity <= N - 1, rows of x and P 16-byte aligned
+ *   (base pointers, ldx % 4 == 0, ldp % 4 == 0, ldx >= d, ldp >= N).  Columns >= N of P are left alone.  Inputs must be finite.
+ * skf_tsne_step_f32: one gradient-descent iteration, two launches, in place on Y, U (velocity) and gains, contiguous (N, 2) fp32.
+ *   Pair pass: q_ij is DEFINED as dx = y_i0 - y_j0; dy = y_i1 - y_j1; q = rcp(1 + fmaf(dy, dy, dx * dx)) in fp32 (rcp: the
+ *   hardware reciprocal, 1 ulp); per row, in fp32, z_i = sum_{j != i} q_ij, a_i = sum_j P_ij q_ij (y_i - y_j),
+ *   r_i = sum_j q_ij^2 (y_i - y_j).  Update: Z = sum_i z_i in fp64 (no second pass over the pairs) and
+ *   g = (float)(4 (exaggeration a_i - r_i / Z)) in fp64 from the fp32 row sums; grad (N, 2), if not NULL, receives g.  Then, every
+ *   operation rounded to fp32 on its own (no fused multiply-add): gain' = (U * g < 0) ? gain + 0.2f : gain * 0.8f;
+ *   gain' = max(gain', 0.01f); U' = momentum * U - learning_rate * (gain' * g); Y' = Y + U'.  No recentring.
+ * skf_tsne_kl_f32: *kl_out (a device double) = sum over P_ij > 0 of P_ij log(P_ij / Q_ij), Q_ij = q_ij / Z, with q and z_i as
+ *   above (fp32) and everything else in fp64, as sum_ij P_ij log(P_ij / q_ij) + log Z sum_ij P_ij.
+ *   Limits of both (SKF_EINVAL): 3 <= N <= 8192, rows of P 16-byte aligned, the (N, 2) arrays 8-byte aligned. */
+size_t skf_tsne_workspace_bytes(int N);
+int skf_tsne_affinities_f32(const float* x, int ldx, int N, int d, double perplexity, float* P, int ldp, double* beta,
+                            void* workspace, size_t workspace_bytes, skf_stream_t stream);
+int skf_tsne_step_f32(const float* P, int ldp, int N, float* Y, float* U, float* gains, float* grad, float exaggeration,
+                      float momentum, float learning_rate, void* workspace, size_t workspace_bytes, skf_stream_t stream);
+int skf_tsne_kl_f32(const float* P, int ldp, int N, const float* Y, double* kl_out, void* workspace, size_t workspace_bytes,
+                    skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

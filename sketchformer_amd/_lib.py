@@ -271,6 +271,10 @@ SIGNATURES = {
     "skf_kmeans_assign_f32": (_I, [_P, _I, _L, _I, _P, _I, _I, _P, _P, _P]),
     "skf_kmeans_step_f32": (_I, [_P, _I, _L, _I, _P, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
     "skf_interpolate_f32": (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
+    "skf_tsne_workspace_bytes": (_Z, [_I]),
+    "skf_tsne_affinities_f32": (_I, [_P, _I, _I, _I, _D, _P, _I, _P, _P, _Z, _P]),
+    "skf_tsne_step_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _F, _F, _F, _P, _Z, _P]),
+    "skf_tsne_kl_f32": (_I, [_P, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 """QuickMetric: per-step history of one scalar (core/metrics.py:7-52 of the reference).
-The threaded SlowMetric family (plots, t-SNE, sklearn) is outside the accelerated path."""
+The threaded SlowMetric family runs in worker threads beside training; of its members the t-SNE maps run on the device
+(sketchformer_amd/projection.py over skf_tsne.hip), PCA and the plots on the host."""
 
 
 class QuickMetric(object):

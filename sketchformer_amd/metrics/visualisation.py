@@ -1,7 +1,9 @@
 """tsne / tsne-predicted / pca projections of the embeddings (metrics/visualisation.py of the reference): up to 1000
-samples of the first 10 classes met in a seeded permutation; rows of the result = (x, y, label)."""
+samples of the first 10 classes met in a seeded permutation; rows of the result = (x, y, label).  The maps come from
+sketchformer_amd.projection: exact t-SNE on the device, PCA in numpy."""
 import numpy as np
 
+from .. import projection
 from ..core.metrics import ProjectionMetric
 
 
@@ -23,8 +25,9 @@ def _select(y, pred_z, shown_labels):
 
 
 def _tsne(feats):
-    from sklearn.manifold import TSNE
-    return TSNE(n_components=2, verbose=0, perplexity=min(30, max(2, len(feats) // 4)), random_state=14).fit_transform(feats)
+    if len(feats) < 3:                                       # nothing to lay out: the map needs three points
+        return np.zeros((len(feats), 2))
+    return projection.tsne(feats, perplexity=min(30, max(2, len(feats) // 4)), seed=14).astype(np.float64)
 
 
 class TSNEProjection(ProjectionMetric):
@@ -52,7 +55,7 @@ class PCAProjection(ProjectionMetric):
     input_type = 'predictions_on_validation_set'
 
     def compute(self, input_data):
-        from sklearn.decomposition import PCA
         x, y, pred_x, pred_y, pred_z, tokenizer, plot_filepath, tmp_filepath, _ = input_data
         feats, labels = _select(y, pred_z, y)
-        return np.concatenate((PCA(n_components=2).fit_transform(feats), labels[:, None]), axis=1)
+        xy = projection.pca(feats, 2) if len(feats) >= 3 else np.zeros((len(feats), 2))
+        return np.concatenate((xy, labels[:, None]), axis=1)

@@ -776,3 +776,80 @@ def kmeans_step(points, centers, state, scale_exp, tol_abs=-1.0, labels=None, co
     _lib.call("skf_kmeans_step_f32", _p(points), points.stride(0), N, d, _p(centers), centers.stride(0), K, int(scale_exp),
               float(tol_abs), _p(labels), _p(counts), _p(state), _p(ws), ws.numel(), _stream())
     return labels, counts
+
+
+TSNE_MAX_N = 8192
+
+
+def _tsne_ws(N, device, workspace):
+    if workspace is not None:
+        return workspace
+    return _ws(_lib.load().skf_tsne_workspace_bytes(N) if 3 <= N <= TSNE_MAX_N else 0, device)
+
+
+def _tsne_matrix(P, name="P"):
+    _f32(P, name)
+    if P.dim() != 2 or P.shape[0] != P.shape[1]:
+        raise ValueError("%s must be (N, N)" % name)
+    _p(P)                                                        # CPU tensors: SkfError before anything is allocated
+    return P.shape[0]
+
+
+def _tsne_points(t, name, N, device):
+    _f32(t, name)
+    if tuple(t.shape) != (N, 2) or not t.is_contiguous() or t.device != device:
+        raise ValueError("%s must be a contiguous (N, 2) float32 tensor on the device of P" % name)
+    return t
+
+
+def tsne_new_affinities(N, device):
+    """An (N, N) float32 view whose rows are 16-byte aligned (the row pitch is N rounded up to a multiple of 4)."""
+    return torch.empty(N, (N + 3) // 4 * 4, dtype=torch.float32, device=device)[:, :N]
+
+
+def tsne_affinities(x, perplexity, return_beta=False, out=None, workspace=None):
+    """Joint probabilities of exact t-SNE (skf_tsne_affinities_f32): x (N, d) float32 -> P (N, N) float32, symmetric bit for bit,
+    zero diagonal, summing to 1; with return_beta also the N precisions (float64) of the rows' Gaussians after the 64-step
+    bisection to `perplexity`.  x may be a row view of a wider buffer.  out: an (N, N) view to write instead of a new tensor
+    (tsne_new_affinities gives one; its row pitch must be a multiple of 4).  The result is a view with such a pitch."""
+    _f32(x, "x")
+    if x.dim() != 2:
+        raise ValueError("x must be (N, d)")
+    _p(x)                                                        # CPU tensors: SkfError before anything is allocated
+    N, d = x.shape
+    if out is None:
+        out = tsne_new_affinities(N if 3 <= N <= TSNE_MAX_N else 4, x.device)    # the library refuses such an N before it looks at P
+    else:
+        if _tsne_matrix(out, "out") != N or out.device != x.device:
+            raise ValueError("out must be an (N, N) float32 tensor on the device of x")
+    beta = torch.empty(max(N, 1), dtype=torch.float64, device=x.device) if return_beta else None
+    ws = _tsne_ws(N, x.device, workspace)
+    _lib.call("skf_tsne_affinities_f32", _p(x), x.stride(0), N, d, float(perplexity), _p(out), out.stride(0), _p(beta),
+              _p(ws), ws.numel(), _stream())
+    return (out, beta) if return_beta else out
+
+
+def tsne_step(P, Y, U, gains, exaggeration, momentum, learning_rate, return_grad=False, workspace=None):
+    """One gradient-descent iteration of exact t-SNE (skf_tsne_step_f32), enqueued on the current stream, IN PLACE on Y, U
+    (velocity) and gains, contiguous (N, 2) float32: the gradient 4 (exaggeration sum_j P_ij q_ij (y_i - y_j) - sum_j q_ij^2
+    (y_i - y_j) / Z) from one pass over the pairs, then scikit-learn's gains / momentum update, each operation rounded to float32
+    on its own.  P (N, N) float32 may be a row view with a pitch that is a multiple of 4.  return_grad: -> the gradient (N, 2)."""
+    N = _tsne_matrix(P)
+    for t, name in ((Y, "Y"), (U, "U"), (gains, "gains")):
+        _tsne_points(t, name, N, P.device)
+    grad = torch.empty(N, 2, dtype=torch.float32, device=P.device) if return_grad else None
+    ws = _tsne_ws(N, P.device, workspace)
+    _lib.call("skf_tsne_step_f32", _p(P), P.stride(0), N, _p(Y), _p(U), _p(gains), _p(grad), float(exaggeration), float(momentum),
+              float(learning_rate), _p(ws), ws.numel(), _stream())
+    return grad
+
+
+def tsne_kl(P, Y, workspace=None):
+    """KL(P || Q) of the embedding Y (skf_tsne_kl_f32): P (N, N), Y (N, 2) float32 -> a float64 tensor of one element on the
+    device (no host sync), the sum over P_ij > 0 of P_ij log(P_ij / Q_ij), accumulated in float64."""
+    N = _tsne_matrix(P)
+    _tsne_points(Y, "Y", N, P.device)
+    out = torch.empty(1, dtype=torch.float64, device=P.device)
+    ws = _tsne_ws(N, P.device, workspace)
+    _lib.call("skf_tsne_kl_f32", _p(P), P.stride(0), N, _p(Y), _p(out), _p(ws), ws.numel(), _stream())
+    return out
