@@ -901,6 +901,55 @@ int skf_tsne_step_f32(const float* P, int ldp, int N, float* Y, float* U, float*
 int skf_tsne_kl_f32(const float* P, int ldp, int N, const float* Y, double* kl_out, void* workspace, size_t workspace_bytes,
                     skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Sketches as images (rasterizer, overlap score)
+ * The reference draws sketches through utils/sketch.py (svgwrite -> svglib); here a sketch becomes a coverage image on the device,
+ * so that a reconstruction can be laid over its original and scored.  Nothing here allocates, synchronises with the host or uses
+ * an atomic; two calls on the same inputs agree bit for bit and a sketch's results do not depend on the rest of the batch.
+ * skf_sketch_points: B sketches of at most T positions -> drawable points.  kind selects the encoding of `data`; the project's
+ *   host decoders are the specification:
+ *     SKF_SKETCH_STROKE3: fp32 rows (dx, dy, pen), ld floats from sketch to sketch (>= 3 T); lengths[b] rows are used (clamped to
+ *       [0, T]); every row is a point, its pen is lifted where pen == 1.
+ *     SKF_SKETCH_STROKE5: fp32 rows (dx, dy, p_down, p_up, p_end), ld >= 5 T; a = argmax(row[2:5]), ties to the first index: the
+ *       sketch ends before the first row with a == 2, the pen is lifted where a == 1 (metrics/samples.py: stroke5_to_stroke3).
+ *     SKF_SKETCH_DICT_TOKENS: int64 ids, ld ids from sketch to sketch (>= T, the first T are read), centers (K, 2) fp32, contiguous;
+ *       PAD = 0, SEP = K + 1, SOS = K + 2, EOS = K + 3 (utils/tokenizer.py: Tokenizer.decode_single): id 1 .. K appends the offset
+ *       centers[id - 1], SEP lifts the pen on the previous point if there is one, EOS ends the sketch, SOS and PAD are skipped.
+ *     SKF_SKETCH_GRID_TOKENS: int64 ids, K = the grid resolution R (even), n = R^2 ids with SEP = n + 1, SOS = n + 2, EOS = n + 3
+ *       (GridTokenizer.decode_single): id 1 .. n is the ABSOLUTE position of its cell centre,
+ *       (float)((double)((id - 1) % R) / (R / 2) - 1 + 1 / R) and the same of (id - 1) / R; SEP closes a line that has a point,
+ *       EOS ends the sketch, and the last point's pen is lifted like the last line of the host decoder.
+ *   Output: xy (B, T, 2) fp32 ABSOLUTE positions (for offsets the running sum from the origin, which is itself no point; summed as
+ *   a shuffle scan per 64 positions plus a carry: exact whenever every partial sum is representable, otherwise within a few
+ *   roundings per 64 positions), pen (B, T) bytes (1 = the pen lifts after this point), n_points (B), bounds (B, 4) fp32 =
+ *   (min x, min y, max x, max y) over the points (zeros for an empty sketch).  Rows n_points[b] .. T - 1 of xy and pen are zeroed.
+ *   Two deliberate differences from the host decoders: an empty sketch gives n_points = 0 (the host returns one dummy row), and
+ *   a token id outside the vocabulary (negative, or above EOS) is skipped and never used as an index (the host raises).
+ *   Limits (SKF_EINVAL): kind one of the four, B >= 1, 1 <= T < 2^31 / 5, ld as above, data aligned to its element, lengths for
+ *   stroke-3, centers and K >= 1 for dictionary tokens, R even in [2, 32768] for grid tokens.  Offsets must be finite.
+ * skf_rasterize_f32: points -> anti-aliased coverage images out (B, H, W) fp32, contiguous, ink = 1, paper = 0.  xy, pen, n_points
+ *   as written above (n_points is clamped to [0, T]); frames (B, 4) = the box (x0, y0, x1, y1) each sketch is fitted into: with
+ *   w = x1 - x0, h = y1 - y0 and the margin m in pixels, s = min((W - 2 m) / w, (H - 2 m) / h), a side below 1e-6 is left out of
+ *   the min and s = 0 when both are; the pixel position of p is q = (W / 2, H / 2) + s (p - box centre), y grows downwards, row v
+ *   of the image is pixel y = v.  Point i contributes the segment q[i-1] -> q[i] if i > 0 and pen[i-1] == 0, else the dot q[i].
+ *   The coverage of pixel (u, v) is clamp(0.5 + line_width / 2 - d, 0, 1), d = the smallest Euclidean distance from its centre
+ *   (u + 0.5, v + 0.5) to any primitive, all in fp32: points and pixel centres are both taken relative to (W / 2, H / 2) (the same
+ *   distances from coordinates half as large), the foot point is t = clamp(((c - a) . (b - a)) / |b - a|^2, 0, 1) and
+ *   c - a - t (b - a) is one fused multiply-add per coordinate.  n_points = 0 gives a blank image.  A primitive whose bounding box misses
+ *   a 32 x 32 pixel tile grown by line_width / 2 + 0.5 is skipped for that tile (it cannot cover any of its pixels).
+ *   Limits (SKF_EINVAL): H, W in [1, 16384], 0 < line_width <= 1024, margin >= 0, 2 margin < min(H, W), B, T >= 1.
+ * skf_raster_overlap_f32: a, b (B, N) fp32 rows (N = H W) -> out (B, 2) = (sum min(a, b), sum max(a, b)) per pair, fp32, summed
+ *   in a fixed order (a[i], b[i] with themselves give two identical sums).  Limits (SKF_EINVAL): B, N >= 1, lda, ldb >= N. */
+#define SKF_SKETCH_STROKE3 0
+#define SKF_SKETCH_STROKE5 1
+#define SKF_SKETCH_DICT_TOKENS 2
+#define SKF_SKETCH_GRID_TOKENS 3
+int skf_sketch_points(int kind, const void* data, long long ld, const int* lengths, const float* centers, int K, int B, int T,
+                      float* xy, unsigned char* pen, int* n_points, float* bounds, skf_stream_t stream);
+int skf_rasterize_f32(const float* xy, const unsigned char* pen, const int* n_points, const float* frames, int B, int T, int H,
+                      int W, float line_width, float margin, float* out, skf_stream_t stream);
+int skf_raster_overlap_f32(const float* a, long long lda, const float* b, long long ldb, int B, long long N, float* out,
+                           skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -275,6 +275,9 @@ SIGNATURES = {
     "skf_tsne_affinities_f32": (_I, [_P, _I, _I, _I, _D, _P, _I, _P, _P, _Z, _P]),
     "skf_tsne_step_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _F, _F, _F, _P, _Z, _P]),
     "skf_tsne_kl_f32": (_I, [_P, _I, _I, _P, _P, _P, _Z, _P]),
+    "skf_sketch_points": (_I, [_I, _P, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "skf_rasterize_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P]),
+    "skf_raster_overlap_f32": (_I, [_P, _L, _P, _L, _I, _L, _P, _P]),
 }
 
 _lib = None

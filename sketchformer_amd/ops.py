@@ -853,3 +853,103 @@ def tsne_kl(P, Y, workspace=None):
     ws = _tsne_ws(N, P.device, workspace)
     _lib.call("skf_tsne_kl_f32", _p(P), P.stride(0), N, _p(Y), _p(out), _p(ws), ws.numel(), _stream())
     return out
+
+
+SKETCH_KINDS = {'stroke3': 0, 'stroke5': 1, 'dict_tokens': 2, 'grid_tokens': 3}       # SKF_SKETCH_* of include/skf.h
+
+
+def sketch_points(data, kind, lengths=None, centers=None, resolution=None, T=None):
+    """Any sketch encoding -> drawable points (skf_sketch_points).  kind 'stroke3': data (B, T, 3) float32 offsets + lengths
+    int32 (B,); 'stroke5': data (B, T, 5) float32; 'dict_tokens': data (B, ld) int64 ids + centers (K, 2) float32;
+    'grid_tokens': data (B, ld) int64 ids + the grid resolution.  T: positions read per sketch (tokens only; default ld).
+    Returns (xy (B, T, 2) float32 absolute positions, pen (B, T) uint8, n_points (B,) int32, bounds (B, 4) float32 =
+    (min x, min y, max x, max y)); rows behind n_points are zero.  An empty sketch has n_points = 0; an id outside the vocabulary
+    is skipped."""
+    if kind not in SKETCH_KINDS:
+        raise ValueError("kind must be one of %s (got %r)" % (sorted(SKETCH_KINDS), kind))
+    _p(data)                                                     # CPU tensors: SkfError before anything is allocated
+    K = 0
+    if kind in ('stroke3', 'stroke5'):
+        width = 3 if kind == 'stroke3' else 5
+        if data.dtype != torch.float32 or data.dim() != 3 or data.shape[2] != width or not data.is_contiguous():
+            raise TypeError("%s data must be a contiguous float32 tensor of shape (B, T, %d)" % (kind, width))
+        B, ld = data.shape[0], data.shape[1] * width
+        if T is not None and int(T) != data.shape[1]:
+            raise ValueError("T of stroke data is its second dimension")
+        T = data.shape[1]
+        if kind == 'stroke3':
+            if lengths is None or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or not lengths.is_contiguous() \
+                    or lengths.device != data.device:
+                raise TypeError("stroke3 needs lengths: a contiguous int32 tensor of shape (B,) on the device of data")
+        else:
+            lengths = None
+        centers = None
+    else:
+        if data.dtype != torch.int64 or data.dim() != 2 or data.stride(1) != 1:
+            raise TypeError("token data must be an int64 tensor of shape (B, ld) with a unit innermost stride")
+        B, ld = data.shape[0], data.stride(0)
+        T = data.shape[1] if T is None else int(T)
+        if T < 1 or T > data.shape[1]:
+            raise ValueError("T must be in [1, %d]" % data.shape[1])
+        lengths = None
+        if kind == 'dict_tokens':
+            if centers is None or centers.dtype != torch.float32 or centers.dim() != 2 or centers.shape[1] != 2 \
+                    or not centers.is_contiguous() or centers.device != data.device:
+                raise TypeError("dict_tokens needs centers: a contiguous float32 tensor of shape (K, 2) on the device of data")
+            K = centers.shape[0]
+        else:
+            if resolution is None:
+                raise ValueError("grid_tokens needs the grid resolution")
+            K, centers = int(resolution), None
+    if B < 1 or T < 1:
+        raise ValueError("sketch_points needs at least one sketch and one position")
+    dev = data.device
+    xy = torch.empty(B, T, 2, dtype=torch.float32, device=dev)
+    pen = torch.empty(B, T, dtype=torch.uint8, device=dev)
+    n = torch.empty(B, dtype=torch.int32, device=dev)
+    bounds = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    _lib.call("skf_sketch_points", SKETCH_KINDS[kind], _p(data), ld, _p(lengths), _p(centers), K, B, T, _p(xy), _p(pen), _p(n),
+              _p(bounds), _stream())
+    return xy, pen, n, bounds
+
+
+def rasterize(xy, pen, n_points, frames, size, line_width=1.5, margin=2.0, out=None):
+    """Points -> anti-aliased coverage images (skf_rasterize_f32): xy (B, T, 2) float32, pen (B, T) uint8, n_points (B,) int32 as
+    sketch_points returns them, frames (B, 4) float32 = the box (x0, y0, x1, y1) every sketch is fitted into, size = (H, W) ->
+    (B, H, W) float32, ink 1, paper 0: coverage = clamp(0.5 + line_width / 2 - distance to the nearest stroke, 0, 1) at every
+    pixel centre.  include/skf.h has the frame rule."""
+    H, W = (int(v) for v in size)
+    _p(xy)
+    if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[2] != 2 or not xy.is_contiguous():
+        raise TypeError("xy must be a contiguous float32 tensor of shape (B, T, 2)")
+    B, T = xy.shape[0], xy.shape[1]
+    dev = xy.device
+    if pen.dtype != torch.uint8 or tuple(pen.shape) != (B, T) or not pen.is_contiguous() or pen.device != dev:
+        raise TypeError("pen must be a contiguous uint8 tensor of shape (B, T) on the device of xy")
+    if n_points.dtype != torch.int32 or tuple(n_points.shape) != (B,) or not n_points.is_contiguous() or n_points.device != dev:
+        raise TypeError("n_points must be a contiguous int32 tensor of shape (B,) on the device of xy")
+    if frames.dtype != torch.float32 or tuple(frames.shape) != (B, 4) or not frames.is_contiguous() or frames.device != dev:
+        raise TypeError("frames must be a contiguous float32 tensor of shape (B, 4) on the device of xy")
+    if out is None:
+        out = torch.empty(B, max(H, 0), max(W, 0), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H, W) or not out.is_contiguous() or out.device != dev:
+        raise TypeError("out must be a contiguous float32 tensor of shape (B, H, W) on the device of xy")
+    _lib.call("skf_rasterize_f32", _p(xy), _p(pen), _p(n_points), _p(frames), B, T, H, W, float(line_width), float(margin), _p(out),
+              _stream())
+    return out
+
+
+def raster_overlap(a, b):
+    """(sum min(a, b), sum max(a, b)) of every pair of images (skf_raster_overlap_f32): a, b (B, ...) float32 of one shape ->
+    (B, 2) float32, summed in a fixed order (bit-reproducible; an image with itself gives two equal sums)."""
+    _f32(a, "a"); _f32(b, "b")
+    _p(a); _p(b)
+    if a.dim() < 2 or a.shape != b.shape or a.device != b.device:
+        raise ValueError("a and b must be two (B, ...) tensors of one shape on one device")
+    B = a.shape[0]
+    a2, b2 = a.reshape(B, -1), b.reshape(B, -1)
+    if a2.stride(1) != 1 or b2.stride(1) != 1:
+        raise ValueError("the images of a and b must be contiguous")
+    out = torch.empty(B, 2, dtype=torch.float32, device=a.device)
+    _lib.call("skf_raster_overlap_f32", _p(a2), a2.stride(0), _p(b2), b2.stride(0), B, a2.shape[1], _p(out), _stream())
+    return out
