@@ -950,6 +950,53 @@ int skf_rasterize_f32(const float* xy, const unsigned char* pen, const int* n_po
 int skf_raster_overlap_f32(const float* a, long long lda, const float* b, long long ldb, int B, long long N, float* out,
                            skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Sketch encoding (raw stroke-3 -> model input)
+ * The direction a user meets first: raw stroke-3 sketches -> the (N, L) token rows / (N, L, 5) stroke-5 rows the model reads.  The
+ * specification is the project's own host code - DistributedStroke3DataLoader.preprocess_per_sketch_from, Tokenizer.encode with a
+ * .npz dictionary (float64 nearest_center, first minimum wins) and GridTokenizer.encode - and the results are BIT-EQUAL to it, not
+ * close.  Two things decide that:
+ *   - Summation order is part of the definition.  The bounds are a float64 running sum and the grid positions an fp32 running sum,
+ *     one add per point in sequence; the fp32 sum is not order-free (a 64-wide shuffle scan plus carry put 88 of 800 coordinate
+ *     rows of integer sketches into at least one other cell).  The scans are therefore sequential per sketch: one lane owns one
+ *     sketch, the per-point work (nearest centre, scatter into the rows) runs point-parallel in launches of its own.
+ *   - No contraction, no approximate division: every operation named below is rounded on its own (no fused multiply-add), and the
+ *     divisions are correctly rounded fp32 divisions.
+ * Nothing here allocates, synchronises with the host or uses an atomic; two calls on the same inputs agree bit for bit.
+ * skf_nearest_center_f64: points (P, 2) fp32, ldp floats from row to row; centers (K, 2) fp64, contiguous; labels[i] (P int32) = the
+ *   nearest centre of point i.  Per pair dx = (double)x - cx; dy = (double)y - cy; d = dx * dx + dy * dy, each of the operations
+ *   rounded to fp64 on its own; among equal minima the lowest index wins.  (skf_kmeans_assign_f32 defines its distance as fp32 fmaf:
+ *   the two can disagree, and the tokenizer's rule is this one.)  Limits (SKF_EINVAL): 1 <= K <= 4096, 1 <= P < 2^31, ldp >= 2.
+ *   sklearn's own KMeans.predict may differ from this rule on exact near-ties.
+ * skf_sketch_encode: flat (P, 3) fp32 rows (dx, dy, pen) of N sketches back to back, offsets (N + 1 int64, on the device,
+ *   non-decreasing from 0 to P: sketch s owns rows offsets[s] .. offsets[s + 1] - 1; the caller checks that, the kernels only
+ *   clamp what they read so that they stay in bounds).  flags & SKF_ENCODE_CLAMP: all three columns are clamped to +-1000 first
+ *   (np.clip).  Per sketch, in this order and precision:
+ *     bounds: running sums of (double)x and (double)y in sequence; min and max include the origin;
+ *       div = (float)max(max_x - min_x, max_y - min_y, 1.0); X = x / div, Y = y / div in fp32.  scale (N fp32, NULL = not wanted)
+ *       receives div.
+ *     SKF_ENCODE_DICT: out (N, L) int64; id = nearest centre of (X, Y) by the rule above + 1; the row is SOS, every id followed by
+ *       SEP where pen == 1, EOS; truncated to L, padded with PAD = 0; SEP = K + 1, SOS = K + 2, EOS = K + 3.
+ *     SKF_ENCODE_GRID: out (N, L) int64; K is the resolution R (even); c = the sequential fp32 running sum of X (likewise Y),
+ *       cell = (int)((c + 1.0f) * (float)(R / 2)) truncated toward zero, cell R -> R - 1, id = cell_x + cell_y * R + 1; SEP = R^2 + 1,
+ *       SOS = R^2 + 2, EOS = R^2 + 3.  Points behind the last pen lift are dropped, unless the sketch has no lift: then all points
+ *       and one SEP.  Truncation as for DICT.
+ *     SKF_ENCODE_STROKE5: out (N, L, 5) fp32; rows (X, Y, 1 - pen, pen, 0) for the first min(n, L) points, (0, 0, 0, 0, 1) behind
+ *       them, and column 4 of row L - 1 is always 1.
+ *   An empty sketch gives an all-PAD row / all (0, 0, 0, 0, 1) rows and scale 1 (the host raises IndexError; the Python layers do
+ *   so too, before the call).  Limits (SKF_EINVAL): N >= 1, 1 <= P < 2^31, L >= 2, 1 <= K <= 4096 (DICT), R even in [2, 32768]
+ *   (GRID), unknown flag bits.  Inputs must be finite.  workspace: skf_sketch_encode_workspace_bytes(P, N) bytes (0 = bad sizes),
+ *   16-byte aligned; its contents carry nothing from one call to the next. */
+#define SKF_ENCODE_DICT 0
+#define SKF_ENCODE_GRID 1
+#define SKF_ENCODE_STROKE5 2
+#define SKF_ENCODE_CLAMP 1u
+int skf_nearest_center_f64(const float* points, int ldp, long long P, const double* centers, int K, int* labels,
+                           skf_stream_t stream);
+size_t skf_sketch_encode_workspace_bytes(long long P, int N);
+int skf_sketch_encode(const float* flat, long long P, const long long* offsets, int N, int mode, const double* centers, int K,
+                      int L, unsigned flags, void* out, float* scale, void* workspace, size_t workspace_bytes,
+                      skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

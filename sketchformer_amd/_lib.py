@@ -278,6 +278,9 @@ SIGNATURES = {
     "skf_sketch_points": (_I, [_I, _P, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "skf_rasterize_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P]),
     "skf_raster_overlap_f32": (_I, [_P, _L, _P, _L, _I, _L, _P, _P]),
+    "skf_nearest_center_f64": (_I, [_P, _I, _L, _P, _I, _P, _P]),
+    "skf_sketch_encode_workspace_bytes": (_Z, [_L, _I]),
+    "skf_sketch_encode": (_I, [_P, _L, _P, _I, _I, _P, _I, _I, _U, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """Data-loader registry (dataloaders/__init__.py:9-17 of the reference): every BaseDataLoader subclass
 with a ``name`` attribute is discoverable by that name."""
 from ..core.data import BaseDataLoader
-from . import distributed_stroke3, synthetic_stroke3  # noqa: F401
+from . import device_stroke3, distributed_stroke3, synthetic_stroke3  # noqa: F401
 
 
 def _all():

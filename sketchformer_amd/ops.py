@@ -953,3 +953,71 @@ def raster_overlap(a, b):
     out = torch.empty(B, 2, dtype=torch.float32, device=a.device)
     _lib.call("skf_raster_overlap_f32", _p(a2), a2.stride(0), _p(b2), b2.stride(0), B, a2.shape[1], _p(out), _stream())
     return out
+
+
+def nearest_center(points, centers):
+    """Nearest dictionary centre of every point by the tokenizer's float64 rule (skf_nearest_center_f64): points (P, 2) float32,
+    centers (K, 2) float64 -> labels int32 (P,).  d = (x - cx)^2 + (y - cy)^2 with every operation rounded to float64 on its own
+    (no fused multiply-add); among equal minima the lowest index wins - Tokenizer.nearest_center's numpy path, bit for bit."""
+    _p(points); _p(centers)                                      # CPU tensors: SkfError before anything is allocated
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 2 or points.stride(1) != 1:
+        raise TypeError("points must be a float32 tensor of shape (P, 2) with a unit innermost stride")
+    if centers.dtype != torch.float64 or centers.dim() != 2 or centers.shape[1] != 2 or not centers.is_contiguous():
+        raise TypeError("centers must be a contiguous float64 tensor of shape (K, 2)")
+    if centers.device != points.device:
+        raise ValueError("points and centers must be on one device")
+    P, K = points.shape[0], centers.shape[0]
+    if P < 1 or not 1 <= K <= 4096:
+        raise ValueError("nearest_center needs at least one point and 1 <= K <= 4096 centres")
+    labels = torch.empty(P, dtype=torch.int32, device=points.device)
+    _lib.call("skf_nearest_center_f64", _p(points), points.stride(0), P, _p(centers), K, _p(labels), _stream())
+    return labels
+
+
+ENCODE_MODES = {'dict': 0, 'grid': 1, 'stroke5': 2}               # SKF_ENCODE_* of include/skf.h
+
+
+def sketch_encode(flat, offsets, mode, max_seq_len, centers=None, resolution=None, clamp=True, return_scale=False):
+    """Raw stroke-3 sketches -> model input (skf_sketch_encode), bit-equal to the loader's per-sketch host pipeline.  flat (P, 3)
+    float32 rows (dx, dy, pen) of N sketches back to back, offsets (N + 1) int64 on the same device, non-decreasing from 0 to P
+    (the caller builds them on the host and checks that there: preprocess.pack_ragged).  mode 'dict': centers (K, 2) float64 ->
+    (N, L) int64; 'grid': the even resolution -> (N, L) int64; 'stroke5' -> (N, L, 5) float32.  clamp: all three columns to +-1000
+    first.  With return_scale also the divisor of every sketch, float32 (N,).  include/skf.h has the definition."""
+    if mode not in ENCODE_MODES:
+        raise ValueError("mode must be one of %s (got %r)" % (sorted(ENCODE_MODES), mode))
+    _p(flat); _p(offsets)                                        # CPU tensors: SkfError before anything is allocated
+    if flat.dtype != torch.float32 or flat.dim() != 2 or flat.shape[1] != 3 or not flat.is_contiguous():
+        raise TypeError("flat must be a contiguous float32 tensor of shape (P, 3)")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.device != flat.device:
+        raise TypeError("offsets must be a contiguous int64 tensor of shape (N + 1,) on the device of flat")
+    P, N, L, K = flat.shape[0], offsets.shape[0] - 1, int(max_seq_len), 0
+    if N < 1 or P < 1:
+        raise ValueError("sketch_encode needs at least one sketch and one point")
+    if L < 2:
+        raise ValueError("max_seq_len must be at least 2")
+    if mode == 'dict':
+        if centers is None:
+            raise ValueError("mode 'dict' needs centers")
+        _p(centers)
+        if centers.dtype != torch.float64 or centers.dim() != 2 or centers.shape[1] != 2 or not centers.is_contiguous() \
+                or centers.device != flat.device:
+            raise TypeError("centers must be a contiguous float64 tensor of shape (K, 2) on the device of flat")
+        K = centers.shape[0]
+        if not 1 <= K <= 4096:
+            raise ValueError("the dictionary must hold 1 <= K <= 4096 centres")
+    else:
+        centers = None
+        if mode == 'grid':
+            if resolution is None:
+                raise ValueError("mode 'grid' needs the grid resolution")
+            K = int(resolution)
+            if K < 2 or K > 32768 or K % 2:
+                raise ValueError("the grid resolution must be even, in [2, 32768]")
+    dev = flat.device
+    out = torch.empty((N, L, 5) if mode == 'stroke5' else (N, L), dtype=torch.float32 if mode == 'stroke5' else torch.int64, device=dev)
+    scale = torch.empty(N, dtype=torch.float32, device=dev) if return_scale else None
+    nbytes = _lib.load().skf_sketch_encode_workspace_bytes(P, N)
+    ws = _ws(nbytes, dev)
+    _lib.call("skf_sketch_encode", _p(flat), P, _p(offsets), N, ENCODE_MODES[mode], _p(centers), K, L, 1 if clamp else 0, _p(out),
+              _p(scale), _p(ws), nbytes, _stream())
+    return (out, scale) if return_scale else out
