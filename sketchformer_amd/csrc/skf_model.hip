@@ -45,19 +45,12 @@ int prologue(SkfModel* M, hipStream_t s) {
                            c.seed, s);
 }
 
-// The live-row state is host-side and only valid while ONE backward is being issued: an early (error) return from a backward
-// must not leave it set for the next call on the model, whose batch has other live rows.
-inline void reset_live_rows(SkfModel* M) { M->live16 = M->live32 = nullptr; M->live_rows = 0; }
-
 // Where a plan keeps the staged batch; masks: the two padding masks the staging launch may write as well (fp32 plan), or none
 struct StageAreas { size_t inp, tar, labels; bool masks; size_t enc_mask, dec_mask; };
 
 int stage_inputs(SkfModel* M, const StageAreas& P, const void* inp, const void* tar, int tar_ld, const long long* labels, hipStream_t s) {
   const SkfConfig& c = M->cfg;
-  reset_live_rows(M);
-  M->lists_built = false;
-  M->pre_ready = M->masks_ready = nullptr;
-  M->masks_staged = false;
+  M->ctx.reset();      // every entry stages its batch: nothing of the previous call (an early error return included) reaches this one
   SKF_CHECK_ARG(inp && tar, "null input");
   const size_t row = c.continuous ? (size_t)c.seq_len * 5 * sizeof(float) : (size_t)c.seq_len * 8;     // bytes per sample
   const size_t src_row = c.continuous ? (size_t)tar_ld * 5 * sizeof(float) : (size_t)tar_ld * 8;
@@ -67,7 +60,7 @@ int stage_inputs(SkfModel* M, const StageAreas& P, const void* inp, const void* 
   const int rc = skf_stage_inputs_launch(inp, M->at<char>(P.inp), tar, M->at<char>(P.tar), row, src_row, row < src_row ? row : src_row, c.batch,
                                          labels, M->at<char>(P.labels), s, masks ? M->at<unsigned char>(P.enc_mask) : nullptr,
                                          masks ? M->at<unsigned char>(P.dec_mask) : nullptr, masks ? c.seq_len : 0);
-  if (rc == SKF_OK) M->masks_staged = masks;
+  if (rc == SKF_OK) M->ctx.masks_staged = masks;
   if (rc != SKF_EUNSUPPORTED) return rc;
   SKF_HIP(hipMemcpyAsync(M->at<char>(P.inp), inp, row * c.batch, hipMemcpyDeviceToDevice, s));
   if (tar_ld == c.seq_len) {
@@ -110,22 +103,16 @@ int capture_or_run(SkfModel* M, hipGraphExec_t* exec, hipStream_t s, F body) {
   // in the PROCESS, so the mode needs the caller's explicit SKF_MODEL_TWO_STREAM_GRAPH; without it the same launches go out eagerly on
   // the two streams (bit-equal results, and the faster form anyway).
   if (M->cfg.use_graph == 2 && !(M->flags & SKF_MODEL_TWO_STREAM_GRAPH)) return body();
-  const bool two_stream = M->side != nullptr && exec == &M->g_fb;
+  const bool two_stream = M->sched.side != nullptr && exec == &M->g_fb;
   if (two_stream && !M->red.descs_uploaded) return body();
   if (!*exec) {
     hipGraph_t graph = nullptr;
     SKF_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     ++g_capturing;
     int rc = SKF_OK;
-    if (two_stream) {
-      hipEvent_t fork = M->fork_event;
-      if (hipEventRecord(fork, s) != hipSuccess || hipStreamWaitEvent(M->side, fork, 0) != hipSuccess) rc = SKF_EHIP;
-    }
+    if (two_stream && !M->sched.fork_into_capture(s)) rc = SKF_EHIP;
     if (rc == SKF_OK) rc = body();
-    if (two_stream && rc == SKF_OK) {
-      hipEvent_t join = M->join_event;
-      if (hipEventRecord(join, M->side) != hipSuccess || hipStreamWaitEvent(s, join, 0) != hipSuccess) rc = SKF_EHIP;
-    }
+    if (two_stream && rc == SKF_OK && !M->sched.join_capture(s)) rc = SKF_EHIP;
     --g_capturing;
     hipError_t e = hipStreamEndCapture(s, &graph);
     if (rc != SKF_OK) { if (graph) (void)hipGraphDestroy(graph); if (rc == SKF_EHIP) skf_set_error("two-stream capture: fork / join failed"); return rc; }
@@ -309,12 +296,7 @@ extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
   // measured on MI355X: eager launches + a wgrad side stream beat hipGraph replay (graph nodes of different
   // streams do not overlap, 7.50 vs 7.72 ms/step), so the side stream is only used on the eager path
   // (round 5: use_graph = 2 captures the two-stream step - capture_or_run)
-  if (cfg->use_graph != 1)
-    SKF_HIP(hipStreamCreateWithFlags(&M->side, hipStreamNonBlocking));
-  if (cfg->use_graph == 2 && M->side) {
-    SKF_HIP(hipEventCreateWithFlags(&M->fork_event, hipEventDisableTiming));
-    SKF_HIP(hipEventCreateWithFlags(&M->join_event, hipEventDisableTiming));
-  }
+  if (cfg->use_graph != 1) SKF_TRY(M->sched.create(cfg->use_graph == 2));
   if (!cfg->use_graph) {     // events cannot be recorded for outside waiters inside a captured graph: one bucket there
     M->n_buckets = do_recon(*cfg) ? 2 : 1;
     for (int i = 0; i < 2; ++i) SKF_HIP(hipEventCreateWithFlags(&M->bucket_ready[i], hipEventDisableTiming));
@@ -328,12 +310,9 @@ extern "C" void skf_model_destroy(SkfModel* m) {
   if (m->g_fb) (void)hipGraphExecDestroy(m->g_fb);
   if (m->g_opt) (void)hipGraphExecDestroy(m->g_opt);
   if (m->g_dec) (void)hipGraphExecDestroy(m->g_dec);
-  for (hipEvent_t e : m->events) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; ++i) if (m->bucket_ready[i]) (void)hipEventDestroy(m->bucket_ready[i]);
   if (m->inputs_staged) (void)hipEventDestroy(m->inputs_staged);
-  if (m->fork_event) (void)hipEventDestroy(m->fork_event);
-  if (m->join_event) (void)hipEventDestroy(m->join_event);
-  if (m->side) (void)hipStreamDestroy(m->side);
+  m->sched.destroy();
   delete m;
 }
 

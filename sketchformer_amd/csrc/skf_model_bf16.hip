@@ -112,21 +112,19 @@ int d16_fwd_relu_bits(SkfModel* M, const DenseP& w, const void* x, int ldx, int 
                             bits, nullptr, w.out >> 3, s);
 }
 // dx[rows][w.in] (+)= dy . W^T (o relu mask)
-// Problems with exactly M->live_rows rows (the decoder side, while M->live16 is set) run over the live rows (dgrad: tiles of
-// the compacted row list) / live 64-row blocks (weight gradient).  Dead output rows are always zero-filled: readers that
+// Problems with exactly as many rows as the live lists cover (the decoder side, while StepCtx has them set) run over the live rows
+// (dgrad: tiles of the compacted row list) / live 64-row blocks (weight gradient).  Dead output rows are always zero-filled: readers that
 // do not walk the lists (the 128 x 128 weight-gradient kernel, LayerNorm, attention) see every row.
 int d16_dgrad(SkfModel* M, const DenseP& w, const void* dy, int lddy, int rows, void* dx, int lddx, int accumulate,
               const void* relu_src, int ld_relu, hipStream_t s, const void* relu_bits = nullptr) {
   const int zero_dead = 1;
   const Img16& im = M->p16.img.at(w.w);
-  const bool lists = M->live16 && rows == M->live_rows;
   return skf_gemm_bf16_bits(rows, w.in, w.out, dy, lddy, w16(M, im.w), im.ldw, dx, lddx, nullptr, 0, relu_bits ? nullptr : relu_src, ld_relu,
-                            accumulate, nullptr, 0, lists ? M->at<int>(M->p16.live1) : nullptr, zero_dead, nullptr, relu_bits, w.in >> 3, s);
+                            accumulate, nullptr, 0, M->ctx.live_blocks(rows, 1), zero_dead, nullptr, relu_bits, w.in >> 3, s);
 }
 int d16_wgrad(SkfModel* M, const DenseP& w, const void* x, int ldx, const void* dy, int lddy, int rows, hipStream_t s) {
-  const bool lists = M->live16 && rows == M->live_rows;
   return skf_gemm_bf16_wgrad_rows(w.in, w.out, rows, x, ldx, dy, lddy, M->G(w.w), w.ld, M->G(w.b), w16(M, M->p16.slab), M->p16.slab_bytes,
-                                  lists ? M->at<int>(M->p16.live64) : nullptr, s);
+                                  M->ctx.live_blocks(rows, 64), s);
 }
 int ln16_fwd(SkfModel* M, const LnP& ln, const void* x, void* y_z, void* out, size_t st, int rows, float rate, unsigned site, hipStream_t s) {
   return skf_layernorm_residual_fwd_bf16(x, y_z, M->P(ln.g), M->P(ln.b), out, M->at<float>(st), rows, M->cfg.d_model, rate, site, M->state, s);
@@ -134,8 +132,7 @@ int ln16_fwd(SkfModel* M, const LnP& ln, const void* x, void* y_z, void* out, si
 int ln16_bwd(SkfModel* M, const LnP& ln, const void* dout, size_t z, size_t st, void* dz, void* dy, int rows, float rate, unsigned site,
              hipStream_t s) {
   Plan16& P = M->p16;
-  const bool lists = M->live16 && rows == M->live_rows;       // decoder side of a padded batch: dead rows are stored as zeros
-  const int* ll = lists ? M->at<int>(P.live_len) : nullptr;
+  const int* ll = M->ctx.live_lengths(rows);       // decoder side of a padded batch: dead rows are stored as zeros
   if (P.ln_batched) {
     // partials only, into this call's slab; ln16_reduce() sums a whole side's slabs in one launch
     SKF_CHECK_ARG(P.ln_cursor < P.ln_n, "more LayerNorm backward calls than slabs");
@@ -172,12 +169,12 @@ int run_forward16(SkfModel* M, bool training, bool with_loss, hipStream_t s, boo
   SKF_TRY(skf_padding_mask(inp, Le, B, Le, emask, s));
   SKF_TRY(skf_padding_mask(tar, Le, B, Ld, dmask, s));
   // samples by length, longest first: the attention launches deal their workgroups over XCDs and shader engines from it
-  M->order = nullptr;
+  M->ctx.order = nullptr;
   if (B <= 4096) {
     SKF_TRY(skf_sample_order(emask, Le, Le, encoder_only ? nullptr : dmask, Ld, Ld, B, M->at<int>(P.order), s));
-    M->order = M->at<int>(P.order);
+    M->ctx.order = M->at<int>(P.order);
   }
-  const int* order = M->order;
+  const int* order = M->ctx.order;
   // ---------------- encoder
   SKF_TRY(skf_embed_fwd_bf16(inp, Le, B, Le, M->P(L.enc_emb), c.vocab_size, d, M->pos, W + P.enc[0].x_in, rate, site_enc_embed(), M->state, s));
   for (int i = 0; i < N; ++i) {
@@ -244,7 +241,7 @@ int run_forward16(SkfModel* M, bool training, bool with_loss, hipStream_t s, boo
 }
 
 int run_backward16(SkfModel* M, hipStream_t s) {
-  M->live16 = nullptr; M->live_rows = 0;      // stale state of a backward that returned early must not reach this one
+  M->ctx.begin_backward();      // stale state of a backward that returned early must not reach this one
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
   const Plan16& P = M->p16;
@@ -271,7 +268,7 @@ int run_backward16(SkfModel* M, hipStream_t s) {
   SKF_TRY(skf_target_live_len(M->at<long long>(P.tar), Le, B, Ld, ll, s));
   SKF_TRY(skf_row_blocks_build(ll, B, Ld, 1, M->at<int>(P.live1), s));
   SKF_TRY(skf_row_blocks_build(ll, B, Ld, 64, M->at<int>(P.live64), s));
-  M->live16 = M->at<int>(P.live1); M->live_rows = Md;        // (live16 only serves as the "lists are set" flag on this path)
+  M->ctx.set_live(Md, ll, 1, M->at<int>(P.live1), 64, M->at<int>(P.live64));
   // ---------------- output layer (the logits buffer holds dlogits, pad columns zero)
   SKF_TRY(d16_wgrad(M, L.out, W + P.dec[N - 1].out3, d, W + P.logits, P.ld_logits, Md, s));
   SKF_TRY(d16_dgrad(M, L.out, W + P.logits, P.ld_logits, Md, G, d, 0, nullptr, 0, s));
@@ -288,9 +285,9 @@ int run_backward16(SkfModel* M, hipStream_t s) {
     SKF_TRY(d16_wgrad(M, w.mha2.o, W + a.o2, d, dy, d, Md, s));
     SKF_TRY(d16_dgrad(M, w.mha2.o, dy, d, Md, dO, d, 0, nullptr, 0, s));
     const char* kv2 = W + a.kv2;
-    const int* qlive = M->live16 ? M->at<int>(P.live_len) : nullptr;      // decoder query rows behind it have dO == 0
+    const int* qlive = M->ctx.live_lengths(Md);      // decoder query rows behind it have dO == 0
     SKF_TRY(skf_attention_bf16_bwd_ordered(W + a.q2, d, kv2, 2 * d, kv2 + 2 * d, 2 * d, W + a.o2, d, W + a.olo2, dO, d, M->at<float>(a.astats2), cross_mask,
-                                        Le, 0, B, H, Ld, Le, dh, dq2, d, dkv2, 2 * d, dkv2 + 2 * d, 2 * d, aws, P.attn_ws_bytes, qlive, M->order, s));
+                                        Le, 0, B, H, Ld, Le, dh, dq2, d, dkv2, 2 * d, dkv2 + 2 * d, 2 * d, aws, P.attn_ws_bytes, qlive, M->ctx.order, s));
     SKF_TRY(d16_wgrad(M, w.mha2.q, W + a.out1, d, dq2, d, Md, s));
     SKF_TRY(d16_dgrad(M, w.mha2.q, dq2, d, Md, G, d, 1, nullptr, 0, s));
     SKF_TRY(d16_wgrad(M, w.mha2.kv, W + P.pre, d, dkv2, 2 * d, Me, s));
@@ -300,12 +297,12 @@ int run_backward16(SkfModel* M, hipStream_t s) {
     SKF_TRY(d16_dgrad(M, w.mha1.o, dy, d, Md, dO, d, 0, nullptr, 0, s));
     const char* qkv = W + a.qkv;
     SKF_TRY(skf_attention_bf16_bwd_ordered(qkv, 3 * d, qkv + 2 * d, 3 * d, qkv + 4 * d, 3 * d, W + a.o1, d, W + a.olo1, dO, d, M->at<float>(a.astats1), dmask, Ld,
-                                        1, B, H, Ld, Ld, dh, dqkv, 3 * d, dqkv + 2 * d, 3 * d, dqkv + 4 * d, 3 * d, aws, P.attn_ws_bytes, qlive, M->order, s));
+                                        1, B, H, Ld, Ld, dh, dqkv, 3 * d, dqkv + 2 * d, 3 * d, dqkv + 4 * d, 3 * d, aws, P.attn_ws_bytes, qlive, M->ctx.order, s));
     SKF_TRY(d16_wgrad(M, w.mha1.qkv, W + a.x_in, d, dqkv, 3 * d, Md, s));
     SKF_TRY(d16_dgrad(M, w.mha1.qkv, dqkv, 3 * d, Md, G2, d, 1, nullptr, 0, s));
     char* t = G; G = G2; G2 = t;
   }
-  M->live16 = nullptr; M->live_rows = 0;
+  M->ctx.clear_live();
   SKF_TRY(skf_embed_bwd_sorted_bf16(M->at<char>(P.emb_sort[1]), B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N), M->state, s));
   SKF_TRY(ln16_reduce(M, true, s));
   if (M->bucket_ready[0] && M->n_buckets == 2) SKF_HIP(hipEventRecord(M->bucket_ready[0], s));
@@ -338,7 +335,7 @@ int run_backward16(SkfModel* M, hipStream_t s) {
     SKF_TRY(d16_dgrad(M, w.mha.o, dy, d, Me, dO, d, 0, nullptr, 0, s));
     const char* qkv = W + a.qkv;
     SKF_TRY(skf_attention_bf16_bwd_ordered(qkv, 3 * d, qkv + 2 * d, 3 * d, qkv + 4 * d, 3 * d, W + a.o, d, W + a.olo, dO, d, M->at<float>(a.astats), emask, Le, 0,
-                                   B, H, Le, Le, dh, dqkv, 3 * d, dqkv + 2 * d, 3 * d, dqkv + 4 * d, 3 * d, aws, P.attn_ws_bytes, nullptr, M->order, s));
+                                   B, H, Le, Le, dh, dqkv, 3 * d, dqkv + 2 * d, 3 * d, dqkv + 4 * d, 3 * d, aws, P.attn_ws_bytes, nullptr, M->ctx.order, s));
     SKF_TRY(d16_wgrad(M, w.mha.qkv, W + a.x_in, d, dqkv, 3 * d, Me, s));
     SKF_TRY(d16_dgrad(M, w.mha.qkv, dqkv, 3 * d, Me, G, d, 1, nullptr, 0, s));
   }

@@ -6,10 +6,10 @@ namespace {
 
 // with_tail_event (skf_model_internal.h) with a fresh event of the step's pool, for the "main stream has reached this point" event of the weight-gradient group that
 // is issued right behind `call`: *ready = the event when it rode, null when it did not (or was not wanted) - the group then records
-// one of its own (issue_wgrads).
+// one of its own (SideSched::issue).
 template <typename F>
 int with_ready_event(SkfModel* M, bool want, hipEvent_t* ready, F call) {
-  hipEvent_t e = (want && may_park(M)) ? M->new_event() : nullptr;
+  hipEvent_t e = (want && may_park(M)) ? M->sched.take_event() : nullptr;
   bool rode = false;
   const int rc = with_tail_event(M, e, &rode, call);
   *ready = rode ? e : nullptr;
@@ -18,17 +18,17 @@ int with_ready_event(SkfModel* M, bool want, hipEvent_t* ready, F call) {
 
 int ffn_bwd(SkfModel* M, const DenseP& f1, const DenseP& f2, const float* x_in, const float* h, const float* dy,
             float* dh, float* dx_acc, int rows, hipStream_t s, const void* hbits, const void* image_t) {
-  if (M->ffn_fused) {       // both input gradients in one launch; the weight gradients read dy / h and x / dh as before
+  if (M->ctx.ffn_fused) {       // both input gradients in one launch; the weight gradients read dy / h and x / dh as before
     SKF_TRY(dense_wgrad(M, f2, h, f2.in, dy, f2.out, rows, s));
-    SKF_TRY(before_write(M, dh, s));
-    SKF_TRY(before_write(M, dx_acc, s));
-    const int* blocks = (M->live16 && rows == M->live_rows) ? M->live16 : nullptr;
+    SKF_TRY(M->sched.before_write(M, dh, s));
+    SKF_TRY(M->sched.before_write(M, dx_acc, s));
+    const int* blocks = M->ctx.live_blocks(rows, 16);
     hipEvent_t ready = nullptr;      // the held group's "main stream is here" event rides on this launch
-    SKF_TRY(with_ready_event(M, !M->wq_held.empty(), &ready, [&] {
+    SKF_TRY(with_ready_event(M, M->sched.holding(), &ready, [&] {
       return skf_ffn_fused_bwd_f32(rows, M->cfg.d_model, M->cfg.dff, dy, image_t, hbits, dh, dx_acc, 1, blocks, blocks ? 16 : 0,
                                    M->cfg.gemm_precision, s);
     }));
-    SKF_TRY(issue_held_wgrads(M, s, ready));
+    SKF_TRY(M->sched.issue_held(M, s, ready));
     return dense_wgrad(M, f1, x_in, f1.in, dh, f1.out, rows, s);
   }
   SKF_TRY(dense_wgrad(M, f2, h, f2.in, dy, f2.out, rows, s));
@@ -62,12 +62,12 @@ int ln_bwd(SkfModel* M, const LnP& ln, const float* dout, const float* z, const 
            int rows, float rate, unsigned site, hipStream_t s) {
   const Plan& P = M->plan;
   const int d = M->cfg.d_model;
-  SKF_TRY(before_write(M, dz, s));
-  if (dy != dz) SKF_TRY(before_write(M, dy, s));
+  SKF_TRY(M->sched.before_write(M, dz, s));
+  if (dy != dz) SKF_TRY(M->sched.before_write(M, dy, s));
   // decoder side of a padded batch: rows behind a sample's live length have dout == 0 and are not read
-  const int* ll = (M->live16 && rows == M->live_rows) ? M->at<int>(P.live_len) : nullptr;
+  const int* ll = M->ctx.live_lengths(rows);
   const int rps = M->cfg.seq_len - 1;
-  if (!M->side || ln.b != ln.g + (size_t)d)
+  if (!M->sched.side || ln.b != ln.g + (size_t)d)
     return skf_layernorm_residual_bwd_rows(dout, z, st, M->P(ln.g), dz, dy, M->G(ln.g), M->G(ln.b), rows, d, rate,
                                            site, M->state, M->at<char>(P.small_ws), P.small_ws_bytes, ll, rps, s);
   // eager path: leave the [g][2d] partials in this LayerNorm's own slice; their column sums ride in the batched
@@ -80,67 +80,70 @@ int ln_bwd(SkfModel* M, const LnP& ln, const float* dout, const float* z, const 
   return ln_partials_desc(M, ln, part, (int)(bytes / (8 * (size_t)d)));
 }
 
+// THE routing decision of the backward's row-owner launches: the launch takes this LayerNorm's backward and leaves its `pbytes` of
+// dgamma | dbeta partials in a slice of the partial arena, to be summed by the batched reduction.  o (+ lead_w): the launch is the
+// LayerNorm-backward + projection one (skf_layernorm_bwd_dgrad_lead_f32) over `rows` rows and multiplies by these Dense layers (d x d).
+bool row_owner_takes_ln(const SkfModel* M, const LnP& ln, size_t pbytes, int rows = 0, const DenseP* o = nullptr, const DenseP* lead_w = nullptr) {
+  const int d = M->cfg.d_model;
+  auto square = [d](const DenseP* w) { return !w || (w->in == d && w->out == d); };
+  return M->ctx.ffn_fused && M->sched.side && ln.b == ln.g + (size_t)d && pbytes <= M->plan.ln_part_stride && square(o) && square(lead_w) &&
+         (!o || skf_layernorm_bwd_dgrad_supported(rows, d, M->cfg.gemm_precision));
+}
+
 // Both input gradients of a feed-forward block AND the backward of the LayerNorm that closes it in one launch
 // (skf_ffn_fused_bwd_ln_f32), where that kernel exists and its dgamma / dbeta partials can ride in the batched reduction;
 // otherwise the LayerNorm launch followed by ffn_bwd.  dout: gradient of the LayerNorm output; dx = dz + d(ffn input) is WRITTEN.
 int ffn_ln_bwd(SkfModel* M, const LnP& ln, const DenseP& f1, const DenseP& f2, const float* dout, const float* z, const float* st,
                const float* x_in, const float* h, float* dy, float* dh, float* dx, int rows, float rate, unsigned site, hipStream_t s,
                const void* hbits, const void* image_t) {
-  const Plan& P = M->plan;
   const int d = M->cfg.d_model;
-  M->last_ready = nullptr;
+  M->ctx.last_ready = nullptr;
   const size_t pbytes = (size_t)skf_ffn_fused_ln_partials(rows) * 2 * d * sizeof(float);
-  if (!M->ffn_fused || !M->side || ln.b != ln.g + (size_t)d || pbytes > P.ln_part_stride) {
+  if (!row_owner_takes_ln(M, ln, pbytes)) {
     SKF_TRY(ln_bwd(M, ln, dout, z, st, dx, dy, rows, rate, site, s));
     return ffn_bwd(M, f1, f2, x_in, h, dy, dh, dx, rows, s, hbits, image_t);
   }
   float* part = M->red.take_ln_partial(M);
   if (!part) return SKF_EINVAL;
-  SKF_TRY(before_write(M, dy, s));
-  SKF_TRY(before_write(M, dh, s));
-  SKF_TRY(before_write(M, dx, s));
-  const int* blocks = (M->live16 && rows == M->live_rows) ? M->live16 : nullptr;
+  SKF_TRY(M->sched.before_write(M, dy, s));
+  SKF_TRY(M->sched.before_write(M, dh, s));
+  SKF_TRY(M->sched.before_write(M, dx, s));
+  const int* blocks = M->ctx.live_blocks(rows, 16);
   hipEvent_t ready = nullptr;      // the held group's "main stream is here" event rides on this launch
-  SKF_TRY(with_ready_event(M, !M->wq_held.empty(), &ready, [&] {
+  SKF_TRY(with_ready_event(M, M->sched.holding(), &ready, [&] {
     return skf_ffn_fused_bwd_ln_f32(rows, d, M->cfg.dff, dout, z, st, M->P(ln.g), rate, site, M->state, image_t, hbits, dy, dh, dx, part,
                                     pbytes, blocks, blocks ? 16 : 0, M->cfg.gemm_precision, s);
   }));
   SKF_TRY(ln_partials_desc(M, ln, part, skf_ffn_fused_ln_partials(rows)));
-  M->last_ready = ready;                        // (nothing else reaches the main stream before this function returns: the caller may reuse it)
-  SKF_TRY(issue_held_wgrads(M, s, ready));      // the previous layer's weight gradients: behind this launch (see hold_wgrads)
+  M->ctx.last_ready = ready;                        // (nothing else reaches the main stream before this function returns: the caller may reuse it)
+  SKF_TRY(M->sched.issue_held(M, s, ready));      // the previous layer's weight gradients: behind this launch (see SideSched::hold)
   SKF_TRY(dense_wgrad(M, f2, h, f2.in, dy, f2.out, rows, s));
   return dense_wgrad(M, f1, x_in, f1.in, dh, f1.out, rows, s);
 }
 
 // The backward of an attention sublayer's tail, out = LayerNorm(x + dropout(o_proj(a))): LayerNorm backward + the projection's
 // input gradient in one launch (skf_layernorm_bwd_dgrad_f32) where it exists, else the two launches.  The weight gradient is queued.
-// lead_a / lead_w / lead_image_t (optional): the gradient of the LayerNorm output is dout + lead_a . lead_w^T - one launch where the fused
-// kernel takes it (*lead_done = true), else the caller's accumulating GEMM has to run first (*lead_done = false, nothing done yet)
-bool ln_oproj_bwd_takes_lead(SkfModel* M, const LnP& ln, const DenseP& o, const DenseP& lead_w, int rows) {
-  const Plan& P = M->plan;
-  const int d = M->cfg.d_model;
-  const size_t pbytes = (size_t)skf_layernorm_bwd_dgrad_partials(rows) * 2 * d * sizeof(float);
-  return M->ffn_fused && M->side && ln.b == ln.g + (size_t)d && pbytes <= P.ln_part_stride && o.in == d && o.out == d &&
-         lead_w.in == d && lead_w.out == d && skf_layernorm_bwd_dgrad_supported(rows, d, M->cfg.gemm_precision);
-}
+// lead_a / lead_image_t (optional): the gradient of the LayerNorm output is dout + lead_a . lead_w^T, taken into the fused launch.  The
+// CALLER decides that, once, with row_owner_takes_ln(.., &o, &lead_w) - where it answers false the caller's accumulating GEMM runs
+// first and no lead operand is handed in (a lead operand on the two-launch branch would be dropped silently: refused).
+size_t ln_oproj_partial_bytes(const SkfModel* M, int rows) { return (size_t)skf_layernorm_bwd_dgrad_partials(rows) * 2 * M->cfg.d_model * sizeof(float); }
 int ln_oproj_bwd(SkfModel* M, const LnP& ln, const DenseP& o, const float* dout, const float* z, const float* st, const float* a_in,
                  float* dz, float* dy, float* da, int rows, float rate, unsigned site, hipStream_t s, const void* image_t,
                  const float* lead_a = nullptr, const void* lead_image_t = nullptr) {
-  const Plan& P = M->plan;
   const int d = M->cfg.d_model;
-  const size_t pbytes = (size_t)skf_layernorm_bwd_dgrad_partials(rows) * 2 * d * sizeof(float);
-  if (!M->ffn_fused || !M->side || ln.b != ln.g + (size_t)d || pbytes > P.ln_part_stride || o.in != d || o.out != d ||
-      !skf_layernorm_bwd_dgrad_supported(rows, d, M->cfg.gemm_precision)) {
+  const size_t pbytes = ln_oproj_partial_bytes(M, rows);
+  if (!row_owner_takes_ln(M, ln, pbytes, rows, &o)) {
+    SKF_CHECK_ARG(!lead_a && !lead_image_t, "a lead operand needs the fused launch");
     SKF_TRY(ln_bwd(M, ln, dout, z, st, dz, dy, rows, rate, site, s));
     SKF_TRY(dense_wgrad(M, o, a_in, d, dy, d, rows, s));
     return dense_dgrad(M, o, dy, d, rows, da, d, 0, nullptr, 0, s);
   }
   float* part = M->red.take_ln_partial(M);
   if (!part) return SKF_EINVAL;
-  SKF_TRY(before_write(M, dz, s));
-  SKF_TRY(before_write(M, dy, s));
-  SKF_TRY(before_write(M, da, s));
-  const int* blocks = (M->live16 && rows == M->live_rows) ? M->live16 : nullptr;
+  SKF_TRY(M->sched.before_write(M, dz, s));
+  SKF_TRY(M->sched.before_write(M, dy, s));
+  SKF_TRY(M->sched.before_write(M, da, s));
+  const int* blocks = M->ctx.live_blocks(rows, 16);
   SKF_TRY(skf_layernorm_bwd_dgrad_lead_f32(rows, d, dout, lead_a, lead_image_t, z, st, M->P(ln.g), rate, site, M->state, image_t, dz, dy, da, part,
                                            pbytes, blocks, blocks ? 16 : 0, M->cfg.gemm_precision, s));
   SKF_TRY(ln_partials_desc(M, ln, part, skf_layernorm_bwd_dgrad_partials(rows)));
@@ -151,22 +154,21 @@ int ln_oproj_bwd(SkfModel* M, const LnP& ln, const DenseP& o, const float* dout,
 int build_row_lists(SkfModel* M, hipStream_t s) {
   const SkfConfig& c = M->cfg;
   const Plan& P = M->plan;
-  M->lists_built = false;
+  M->ctx.lists_built = false;
   if (c.continuous || !do_recon(c) || c.gemm_precision == SKF_PREC_F32) return SKF_OK;
   const int B = c.batch, Le = c.seq_len, Ld = c.seq_len - 1;
   SKF_TRY(skf_target_live_len(M->at<long long>(P.tar), Le, B, Ld, M->at<int>(P.live_len), s));
   SKF_TRY(skf_row_blocks_build(M->at<int>(P.live_len), B, Ld, 16, M->at<int>(P.live16), s));
   SKF_TRY(skf_row_blocks_build(M->at<int>(P.live_len), B, Ld, 32, M->at<int>(P.live32), s));
-  M->lists_built = true;
+  M->ctx.lists_built = true;
   return SKF_OK;
 }
 
 }  // namespace
 
 int run_backward(SkfModel* M, hipStream_t s) {
-  M->live16 = M->live32 = nullptr; M->live_rows = 0;      // (set below for the decoder layers only; see reset_live_rows)
-  M->next_event = 0;
-  M->pending_readers.clear();
+  M->ctx.begin_backward();      // (the live rows are set below, for the decoder layers only)
+  M->sched.begin_backward();
   M->red.begin_step();
   const SkfConfig& c = M->cfg;
   const Layout& L = M->lay;
@@ -183,7 +185,6 @@ int run_backward(SkfModel* M, hipStream_t s) {
   float* dO = M->at<float>(P.do_);
   float* dpre = M->at<float>(P.dpre);
   float* demb = M->at<float>(P.demb);
-  M->wq.clear(); M->wq_held.clear();
   int layer_no = 0;     // running layer counter: picks the gradient-buffer set
 
   const bool bott = has_bott(c), cls = has_cls(c), recon = do_recon(c);
@@ -194,16 +195,16 @@ int run_backward(SkfModel* M, hipStream_t s) {
   // (skf_row_blocks.hip): the split-arithmetic GEMMs walk the live row blocks only.  Not in continuous mode (its pen-state
   // loss has a gradient at every position), not for the fp32-MFMA kernels (they ignore the lists).
   // (the lists only depend on the staged targets: issue_embed_sorts builds them on the side stream under the forward)
-  if (!M->lists_built) SKF_TRY(build_row_lists(M, s));
-  if (M->lists_built) { M->live16 = M->at<int>(P.live16); M->live32 = M->at<int>(P.live32); M->live_rows = Md; }
-  M->lists_built = false;
+  if (!M->ctx.lists_built) SKF_TRY(build_row_lists(M, s));
+  if (M->ctx.lists_built) M->ctx.set_live(Md, M->at<int>(P.live_len), 16, M->at<int>(P.live16), 32, M->at<int>(P.live32));
+  M->ctx.lists_built = false;
   // output layer: logits buffer now holds dlogits
   const float* dlog = M->at<float>(P.logits);
   SKF_TRY(dense_wgrad(M, L.out, M->at<float>(P.dec[N - 1].out3), d, dlog, L.out.out, Md, s));
   {
     hipEvent_t ready = nullptr;      // the group's "main stream is here" event rides on the input-gradient launch (the last of its chain)
     SKF_TRY(with_ready_event(M, true, &ready, [&] { return dense_dgrad(M, L.out, dlog, L.out.out, Md, G, d, 0, nullptr, 0, s); }));
-    SKF_TRY(issue_wgrads(M, s, ready));
+    SKF_TRY(M->sched.issue(M, s, ready));
   }
   const unsigned char* cross_mask = c.blind_decoder_mask ? nullptr : emask;
   for (int i = N - 1; i >= 0; --i, ++layer_no) {
@@ -219,40 +220,40 @@ int run_backward(SkfModel* M, hipStream_t s) {
     SKF_TRY(ln_oproj_bwd(M, w.ln2, w.mha2.o, G2, M->at<float>(a.z2), M->at<float>(a.st2), M->at<float>(a.o2), G, dy2, dO, Md, rate,
                          site_dec(N, i, 1), s, M->at<char>(a.img_o2)));
     const float* kv2 = M->at<float>(a.kv2);
-    SKF_TRY(before_write(M, dq2, s));
-    SKF_TRY(before_write(M, dkv2, s));
-    const int* qlive = M->live16 ? M->at<int>(P.live_len) : nullptr;      // decoder query rows behind it have dO == 0
+    SKF_TRY(M->sched.before_write(M, dq2, s));
+    SKF_TRY(M->sched.before_write(M, dkv2, s));
+    const int* qlive = M->ctx.live_lengths(Md);      // decoder query rows behind it have dO == 0
     SKF_TRY(skf_attention_bwd_ordered(M->at<float>(a.q2), d, kv2, 2 * d, kv2 + d, 2 * d, M->at<float>(a.o2), d, dO, d,
                                       M->at<float>(a.astats2), cross_mask, Le, 0, B, H, Ld, Le, dh, dq2, d, dkv2, 2 * d,
-                                      dkv2 + d, 2 * d, M->cfg.gemm_precision, qlive, M->order, s));
+                                      dkv2 + d, 2 * d, M->cfg.gemm_precision, qlive, M->ctx.order, s));
     SKF_TRY(dense_wgrad(M, w.mha2.q, M->at<float>(a.out1), d, dq2, d, Md, s));
     // d(out1) += dq2 . Wq^T: inside the LayerNorm-backward launch of the self-attention sublayer below where that kernel takes it
-    const bool lead = ln_oproj_bwd_takes_lead(M, w.ln1, w.mha1.o, w.mha2.q, Md);
+    const bool lead = row_owner_takes_ln(M, w.ln1, ln_oproj_partial_bytes(M, Md), Md, &w.mha1.o, &w.mha2.q);
     if (!lead) SKF_TRY(dense_dgrad(M, w.mha2.q, dq2, d, Md, G, d, 1, nullptr, 0, s));
     SKF_TRY(dense_wgrad(M, w.mha2.kv, pre, L.E, dkv2, 2 * d, Me, s));
     // (the last layer of the loop runs it on the main stream: its reader follows too soon to gain anything)
     if (i == 0) {
-      SKF_TRY(before_read(M, dpre, s));   // the side-stream writers of the layers above have finished accumulating
+      SKF_TRY(M->sched.before_read(M, dpre, s));   // the side-stream writers of the layers above have finished accumulating
       SKF_TRY(dense_dgrad(M, w.mha2.kv, dkv2, 2 * d, Me, dpre, L.E, i != N - 1, nullptr, 0, s));
     } else SKF_TRY(dense_dgrad_deferred(M, w.mha2.kv, dkv2, 2 * d, Me, dpre, L.E, i != N - 1, s));
     // out1 = LN1(x + drop(mha1(x,x,x)))
     SKF_TRY(ln_oproj_bwd(M, w.ln1, w.mha1.o, G, M->at<float>(a.z1), M->at<float>(a.st1), M->at<float>(a.o1), G2, dy1, dO, Md, rate,
                          site_dec(N, i, 0), s, M->at<char>(a.img_o1), lead ? dq2 : nullptr, lead ? M->at<char>(a.img_q2t) : nullptr));
     const float* qkv = M->at<float>(a.qkv);
-    SKF_TRY(before_write(M, dqkv, s));
+    SKF_TRY(M->sched.before_write(M, dqkv, s));
     SKF_TRY(skf_attention_bwd_ordered(qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, M->at<float>(a.o1), d, dO, d,
                                       M->at<float>(a.astats1), dmask, Ld, 1, B, H, Ld, Ld, dh, dqkv, 3 * d, dqkv + d, 3 * d,
-                                      dqkv + 2 * d, 3 * d, M->cfg.gemm_precision, qlive, M->order, s));
+                                      dqkv + 2 * d, 3 * d, M->cfg.gemm_precision, qlive, M->ctx.order, s));
     SKF_TRY(dense_wgrad(M, w.mha1.qkv, M->at<float>(a.x_in), d, dqkv, 3 * d, Md, s));
     // the 8 weight gradients of this layer: one event pair - held until the next layer's fused feed-forward launch is queued
-    const bool hold = M->ffn_fused && i > 0;
+    const bool hold = M->ctx.ffn_fused && i > 0;
     hipEvent_t ready = nullptr;      // not held: the group's event rides on this layer's last launch
     SKF_TRY(with_ready_event(M, !hold, &ready, [&] { return dense_dgrad(M, w.mha1.qkv, dqkv, 3 * d, Md, G2, d, 1, nullptr, 0, s); }));
     float* t = G; G = G2; G2 = t;
-    if (hold) SKF_TRY(hold_wgrads(M, s));
-    else SKF_TRY(issue_wgrads(M, s, ready));
+    if (hold) SKF_TRY(M->sched.hold(M, s));
+    else SKF_TRY(M->sched.issue(M, s, ready));
   }
-  M->live16 = M->live32 = nullptr; M->live_rows = 0;
+  M->ctx.clear_live();
   hipEvent_t dec_emb_done = nullptr;
   // decoder embedding
   if (c.continuous) {
@@ -271,13 +272,13 @@ int run_backward(SkfModel* M, hipStream_t s) {
   }
   // every gradient of [decoder embedding .. output layer] is issued: first bucket of the flat buffer
   if (M->n_buckets == 2) SKF_TRY(flush_wgrads(M, s, 0, false, true, dec_emb_done));
-  SKF_TRY(before_read(M, dpre, s));     // the deferred K/V-projection input gradients (side stream) are complete
+  SKF_TRY(M->sched.before_read(M, dpre, s));     // the deferred K/V-projection input gradients (side stream) are complete
   }   // recon
   const int E = L.E, Ua = L.Ua, U = c.lowerdim, NB = c.class_buffer_layers;
   hipEvent_t bott_ready = nullptr;
   if (bott) {
     // expander, classifier
-    const bool defer_sums = M->side && Ua <= 4096;      // (wherever the batched reduction runs: the eager step and its two-stream capture)
+    const bool defer_sums = M->sched.side && Ua <= 4096;      // (wherever the batched reduction runs: the eager step and its two-stream capture)
     float* xp1 = M->at<float>(P.bott_part);
     float* xp2 = xp1 + (size_t)B * Le;
     float* pvp = xp2 + (size_t)B * Le;
@@ -297,7 +298,7 @@ int run_backward(SkfModel* M, hipStream_t s) {
     } else if (cls) {
       float* dz = M->at<float>(P.dcb[0]);
       float* dz2 = M->at<float>(P.dcb[1]);
-      SKF_TRY(before_write(M, dz, s));
+      SKF_TRY(M->sched.before_write(M, dz, s));
       SKF_TRY(dense_wgrad(M, L.cls, M->at<float>(P.cb_f[NB - 1]), U, dcls, c.n_classes, B, s));
       SKF_TRY(dense_dgrad(M, L.cls, dcls, c.n_classes, B, dz, U, 0, M->at<float>(P.cb_h[NB - 1]), U, s));
       for (int i = NB - 1; i >= 0; --i) {
@@ -308,7 +309,7 @@ int run_backward(SkfModel* M, hipStream_t s) {
         if (i == 0) {
           SKF_TRY(dense_dgrad(M, L.cbuf[0], dz, U, B, demb, E, acc_emb, nullptr, 0, s));
         } else {
-          SKF_TRY(before_write(M, dz2, s));
+          SKF_TRY(M->sched.before_write(M, dz2, s));
           SKF_TRY(dense_dgrad(M, L.cbuf[i], dz, U, B, dz2, U, 0, M->at<float>(P.cb_h[i - 1]), U, s));
           float* t = dz; dz = dz2; dz2 = t;
         }
@@ -317,12 +318,12 @@ int run_backward(SkfModel* M, hipStream_t s) {
     // bottleneck
     const float* dpool = demb;
     if (c.attn_version == 2) {
-      SKF_TRY(before_write(M, M->at<float>(P.dpooled), s));
+      SKF_TRY(M->sched.before_write(M, M->at<float>(P.dpooled), s));
       SKF_TRY(dense_wgrad(M, L.bott_e, M->at<float>(P.pooled), d, demb, U, B, s));
       SKF_TRY(dense_dgrad(M, L.bott_e, demb, U, B, M->at<float>(P.dpooled), d, 0, nullptr, 0, s));
       dpool = M->at<float>(P.dpooled);
     }
-    SKF_TRY(before_write(M, G, s));
+    SKF_TRY(M->sched.before_write(M, G, s));
     if (defer_sums) {
       SKF_TRY(skf_pool_bwd_partials(M->at<float>(P.u), M->P(L.bott_v), enc_out, M->at<float>(P.pool_a), dpool, B, Le, Ua, d, G, pvp, s));
       SKF_TRY(colsum_desc(M, pvp, B, Ua, M->G(L.bott_v)));
@@ -336,7 +337,7 @@ int run_backward(SkfModel* M, hipStream_t s) {
     float* spare = (G == M->at<float>(P.gA)) ? M->at<float>(P.gB) : M->at<float>(P.gA);
     G = dpre; G2 = spare;
   }
-  SKF_TRY(issue_wgrads(M, s, bott_ready));            // expander / classifier / bottleneck group
+  SKF_TRY(M->sched.issue(M, s, bott_ready));            // expander / classifier / bottleneck group
   for (int i = N - 1; i >= 0; --i, ++layer_no) {
     const EncLayerP& w = L.enc[i];
     const EncAct& a = P.enc[i];
@@ -348,21 +349,21 @@ int run_backward(SkfModel* M, hipStream_t s) {
     // last layer of the backward: nothing is left on the main stream to hide a whole layer's weight gradients behind
     // (only the embedding gradient follows), so they go out per sublayer - the step's tail before Adam is one wgrad, not four
     // (the fused launch's completion signal already served the held group as its "main stream is here" event: this group shares it)
-    if (i == 0) SKF_TRY(issue_wgrads(M, s, M->last_ready));
-    M->last_ready = nullptr;
+    if (i == 0) SKF_TRY(M->sched.issue(M, s, M->ctx.last_ready));
+    M->ctx.last_ready = nullptr;
     {
       hipEvent_t ready = nullptr;
       SKF_TRY(with_ready_event(M, i == 0, &ready, [&] {
         return ln_oproj_bwd(M, w.ln1, w.mha.o, G2, M->at<float>(a.z1), M->at<float>(a.st1), M->at<float>(a.o), G, dy1, dO, Me, rate,
                             site_enc(i, 0), s, M->at<char>(a.img_o));
       }));
-      if (i == 0) SKF_TRY(issue_wgrads(M, s, ready));
+      if (i == 0) SKF_TRY(M->sched.issue(M, s, ready));
     }
     const float* qkv = M->at<float>(a.qkv);
-    SKF_TRY(before_write(M, dqkv, s));
+    SKF_TRY(M->sched.before_write(M, dqkv, s));
     SKF_TRY(skf_attention_bwd_ordered(qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, M->at<float>(a.o), d, dO, d,
                                       M->at<float>(a.astats), emask, Le, 0, B, H, Le, Le, dh, dqkv, 3 * d, dqkv + d, 3 * d,
-                                      dqkv + 2 * d, 3 * d, M->cfg.gemm_precision, nullptr, M->order, s));
+                                      dqkv + 2 * d, 3 * d, M->cfg.gemm_precision, nullptr, M->ctx.order, s));
     SKF_TRY(dense_wgrad(M, w.mha.qkv, M->at<float>(a.x_in), d, dqkv, 3 * d, Me, s));
     // last layer of the backward: the weight gradient only needs dqkv, so it goes out BEFORE the input-gradient GEMM - the hop
     // to the side stream and the kernel itself then run under that GEMM and the embedding gradient instead of behind them.
@@ -370,16 +371,16 @@ int run_backward(SkfModel* M, hipStream_t s) {
     // queued behind the held group of the layer above and finished ~20 us AFTER the main stream's last kernel
     // (profiles/r06h_timeline.txt: 34 us of idle main stream in front of the final reduction); with the 18-us q|k|v gradient in line
     // here both streams end together and the final reduction starts without waiting for a hop.
-    if (i == 0) SKF_TRY(issue_wgrads(M, s, nullptr, M->wq_held.empty()));
+    if (i == 0) SKF_TRY(M->sched.issue(M, s, nullptr, !M->sched.holding()));
     SKF_TRY(dense_dgrad(M, w.mha.qkv, dqkv, 3 * d, Me, G, d, 1, nullptr, 0, s));
-    if (M->ffn_fused && i > 0) SKF_TRY(hold_wgrads(M, s));
-    else SKF_TRY(issue_wgrads(M, s));
+    if (M->ctx.ffn_fused && i > 0) SKF_TRY(M->sched.hold(M, s));
+    else SKF_TRY(M->sched.issue(M, s));
     // half-way through the encoder: the slabs and LayerNorm partials finished so far are reduced on the side stream now, under the
     // remaining layers - the final reduction, which the optimizer waits for on the main stream, shrinks to the last layers' share
     // (with a held group: only what is already on the side stream - issuing the held group here would put it beside the next layer's
     //  fused feed-forward launch again)
     // (not with the fused feed-forward blocks: the reduction launch lands beside a fused launch it cannot share CUs with - A/B 3.95 vs 3.99 ms)
-    if (!M->ffn_fused && M->side && N >= 2 && i == N / 2) SKF_TRY(flush_wgrads(M, s, -1, false, M->wq_held.empty()));
+    if (!M->ctx.ffn_fused && M->sched.side && N >= 2 && i == N / 2) SKF_TRY(flush_wgrads(M, s, -1, false, !M->sched.holding()));
   }
   if (c.continuous) {
     SKF_TRY(skf_embed_continuous_bwd(M->at<float>(P.inp), Le, B, Le, G, d, M->G(L.enc_embd.w), M->G(L.enc_embd.b), rate,
@@ -406,24 +407,24 @@ int issue_embed_sorts(SkfModel* M, hipStream_t s) {
   if (!P.emb_sort_bytes) return SKF_OK;
   const int B = c.batch, Le = c.seq_len, Ld = c.seq_len - 1, d = c.d_model;
   hipStream_t ss = s;
-  if (M->side && do_recon(c)) {
+  if (M->sched.side && do_recon(c)) {
     // (the staged inputs are all the side stream's first launches read: it waits for the staging launch's own completion signal,
     //  no packet of its own on the main stream)
     hipEvent_t staged = (M->inputs_staged && M->inputs_staged_valid && !g_capturing) ? M->inputs_staged : nullptr;
     if (!staged) {
-      staged = M->new_event();
+      staged = M->sched.take_event();
       SKF_CHECK_ARG(staged, "event allocation failed");
       SKF_HIP(hipEventRecord(staged, s));
     }
-    SKF_HIP(hipStreamWaitEvent(M->side, staged, 0));
-    ss = M->side;
+    SKF_HIP(hipStreamWaitEvent(M->sched.side, staged, 0));
+    ss = M->sched.side;
     // first on the side stream: what the forward does not need before its first attention (forward_preamble) - the main stream goes
     // straight to the embedding and the first q|k|v projection (30 us of one-workgroup and short launches off the critical path)
-    hipEvent_t masks = M->new_event(), ready = M->new_event();
+    hipEvent_t masks = M->sched.take_event(), ready = M->sched.take_event();
     SKF_CHECK_ARG(masks && ready, "event allocation failed");
     SKF_TRY(forward_preamble(M, true, false, ss, masks));
     SKF_HIP(hipEventRecord(ready, ss));
-    M->masks_ready = masks; M->pre_ready = ready;
+    M->ctx.masks_ready = masks; M->ctx.pre_ready = ready;
   }
   SKF_TRY(skf_embed_sort(M->at<long long>(P.inp), Le, B, Le, c.vocab_size, M->G(L.enc_emb), d, M->at<char>(P.emb_sort[0]),
                          P.emb_sort_bytes, ss));

@@ -63,6 +63,11 @@ int build_ffn_images(SkfModel* M, bool with_backward, bool encoder_only, hipStre
     }
   return skf_dense_weight_images((int)src.size(), src.data(), ld.data(), tr.data(), K.data(), N.data(), img.data(), c.gemm_precision, s);
 }
+// The Dense that consumes a row-owner launch's output can be chained into that launch: d inputs, one of the projection widths the
+// fused kernels are built for, dense rows
+bool chains(const SkfModel* M, const DenseP& next) {
+  return next.in == M->cfg.d_model && (next.out == 128 || next.out == 256 || next.out == 384) && next.ld == next.out;
+}
 // out = LayerNorm(x + dropout(ffn(x))): one launch, or Dense(relu) + Dense + residual-LayerNorm
 // next / next_image / next_out: the Dense that consumes `out` (the next layer's q|k|v projection), taken into the same launch when
 // the fused kernel runs (*next_done = true), else left to the caller
@@ -71,12 +76,12 @@ int ffn_ln_fwd(SkfModel* M, const DenseP& f1, const DenseP& f2, const LnP& ln, c
                const DenseP* next = nullptr, const void* next_image = nullptr, float* next_out = nullptr, bool* next_done = nullptr) {
   const int d = M->cfg.d_model;
   if (next_done) *next_done = false;
-  if (M->ffn_fused && next && next->in == d && (next->out == 128 || next->out == 256 || next->out == 384) && next->ld == next->out) {
+  if (M->ctx.ffn_fused && next && chains(M, *next)) {
     if (next_done) *next_done = true;
     return skf_ffn_fused_fwd_proj_f32(rows, d, M->cfg.dff, x, image, M->P(f1.b), M->P(f2.b), h, bits, M->P(ln.g), M->P(ln.b), z, out, stats,
                                       rate, site, M->state, next_image, M->P(next->b), next->out, next_out, M->cfg.gemm_precision, s);
   }
-  if (M->ffn_fused)
+  if (M->ctx.ffn_fused)
     return skf_ffn_fused_fwd_f32(rows, d, M->cfg.dff, x, image, M->P(f1.b), M->P(f2.b), h, bits, M->P(ln.g), M->P(ln.b), z, out, stats,
                                  rate, site, M->state, M->cfg.gemm_precision, s);
   SKF_TRY(dense_fwd_relu_bits(M, f1, x, rows, h, bits, s));
@@ -92,7 +97,7 @@ int attn_tail_ffn_fwd(SkfModel* M, const DenseP& o, const LnP& ln_a, const float
                       const void* image, float* z, float* out, float* stats, unsigned site, int rows, float rate, hipStream_t s,
                       const DenseP* next, const void* next_image, float* next_out, bool* next_done) {
   const int d = M->cfg.d_model;
-  if (!M->ffn_fused || o.in != d || o.out != d || ln_a.b != ln_a.g + (size_t)d) {
+  if (!M->ctx.ffn_fused || o.in != d || o.out != d || ln_a.b != ln_a.g + (size_t)d) {
     SKF_TRY(dense_ln_fwd(M, o, a, rows, x, z1, ln_a, x1, st1, rate, site_a, s));
     return ffn_ln_fwd(M, f1, f2, ln, x1, rows, h, bits, image, z, out, stats, rate, site, s, next, next_image, next_out, next_done);
   }
@@ -102,7 +107,7 @@ int attn_tail_ffn_fwd(SkfModel* M, const DenseP& o, const LnP& ln_a, const float
   b.gamma = M->P(ln.g); b.beta = M->P(ln.b); b.z = z; b.out = out; b.stats = stats; b.rate = rate; b.site = site; b.step_state = M->state;
   b.pre_image = o_image; b.pre_bias = M->P(o.b); b.pre_residual = x; b.pre_gamma = M->P(ln_a.g); b.pre_beta = M->P(ln_a.b);
   b.pre_z = z1; b.pre_out = x1; b.pre_stats = st1; b.pre_site = site_a;
-  const bool chain = next && next->in == d && (next->out == 128 || next->out == 256 || next->out == 384) && next->ld == next->out;
+  const bool chain = next && chains(M, *next);
   if (chain) { b.proj_image = next_image; b.proj_bias = M->P(next->b); b.proj_out = next_out; b.proj_n = next->out; }
   if (next_done) *next_done = chain;
   return skf_ffn_block_fwd_f32(&b, s);
@@ -119,7 +124,7 @@ int forward_preamble(SkfModel* M, bool with_backward, bool encoder_only, hipStre
   const int B = c.batch, Le = c.seq_len, Ld = c.seq_len - 1;
   unsigned char* emask = M->at<unsigned char>(P.enc_mask);
   unsigned char* dmask = M->at<unsigned char>(P.dec_mask);
-  if (M->masks_staged) {
+  if (M->ctx.masks_staged) {
     // (written by the staging launch of this call)
   } else if (c.continuous) {
     SKF_TRY(skf_padding_mask_continuous(M->at<float>(P.inp), Le, B, Le, emask, s));
@@ -128,14 +133,14 @@ int forward_preamble(SkfModel* M, bool with_backward, bool encoder_only, hipStre
     SKF_TRY(skf_padding_mask(M->at<long long>(P.inp), Le, B, Le, emask, s));
     SKF_TRY(skf_padding_mask(M->at<long long>(P.tar), Le, B, Ld, dmask, s));
   }
-  M->order = nullptr;
+  M->ctx.order = nullptr;
   if (B <= 4096) {
     SKF_TRY(skf_sample_order(emask, Le, Le, encoder_only ? nullptr : dmask, Ld, Ld, B, M->at<int>(P.order), s));
-    M->order = M->at<int>(P.order);
+    M->ctx.order = M->at<int>(P.order);
   }
   if (masks_ready) SKF_HIP(hipEventRecord(masks_ready, s));      // (the images are only read by the launch BEHIND the first attention)
-  M->ffn_fused = ffn_fused_on(M);
-  if (M->ffn_fused) SKF_TRY(build_ffn_images(M, with_backward, encoder_only, s));
+  M->ctx.ffn_fused = ffn_fused_on(M);
+  if (M->ctx.ffn_fused) SKF_TRY(build_ffn_images(M, with_backward, encoder_only, s));
   return SKF_OK;
 }
 
@@ -154,10 +159,9 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
   const float* inpf = M->at<float>(P.inp);      // continuous mode: (B, L, 5) stroke-5 rows
   const float* tarf = M->at<float>(P.tar);
   // weight images, padding masks, sample order: here, unless the train step already put them on the side stream (issue_embed_sorts)
-  hipEvent_t images_ready = M->pre_ready, masks_ready = M->masks_ready;
-  M->pre_ready = M->masks_ready = nullptr;
+  const hipEvent_t images_ready = M->ctx.pre_ready, masks_ready = M->ctx.masks_ready;
   if (!images_ready) SKF_TRY(forward_preamble(M, training && with_loss, encoder_only, s));
-  const int* order = M->order;
+  const int* order = M->ctx.order;
 
   // ---------------- encoder (builders/layers/transformer.py:288-301)
   if (c.continuous)
@@ -206,12 +210,11 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
   // pre_decoder: the expanded embedding, or the encoder output itself when there is no bottleneck (:172-176)
   float* pre = bott ? M->at<float>(P.pre) : enc_out;
   // pre_decoder is all the side stream's cross-attention K|V projections wait for: their event rides on the expander launch
-  // (the event pool restarts here: the step's earlier events - masks, images - were waited for in front of the first encoder layer)
   hipEvent_t dec_in_ready = nullptr;
   bool dec_in_recorded = false;
-  if (recon && M->side) {
-    M->next_event = 0;
-    dec_in_ready = M->new_event();
+  if (recon && M->sched.side) {
+    M->sched.rewind_events();      // (the step's earlier events - masks, images - were waited for in front of the first encoder layer)
+    dec_in_ready = M->sched.take_event();
     SKF_CHECK_ARG(dec_in_ready, "event allocation failed");
   }
   if (recon && bott) {
@@ -233,17 +236,17 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
   // (round 5: the first layer's cross-attention waits for ITS projection only - it used to wait for all of them, 45 us with the main
   //  stream idle at cfg 2 - the second layer's for the rest)
   hipEvent_t kv_done = nullptr, kv_first = nullptr;
-  if (M->side) {
-    kv_done = M->new_event();
-    kv_first = N > 1 ? M->new_event() : kv_done;
+  if (M->sched.side) {
+    kv_done = M->sched.take_event();
+    kv_first = N > 1 ? M->sched.take_event() : kv_done;
     SKF_CHECK_ARG(dec_in_ready && kv_done && kv_first, "event allocation failed");
     if (!dec_in_recorded) SKF_HIP(hipEventRecord(dec_in_ready, s));
-    SKF_HIP(hipStreamWaitEvent(M->side, dec_in_ready, 0));
+    SKF_HIP(hipStreamWaitEvent(M->sched.side, dec_in_ready, 0));
     for (int i = 0; i < N; ++i) {
-      SKF_TRY(dense_fwd(M, L.dec[i].mha2.kv, pre, Me, M->at<float>(P.dec[i].kv2), 0, M->side));
-      if (i == 0 && kv_first != kv_done) SKF_HIP(hipEventRecord(kv_first, M->side));
+      SKF_TRY(dense_fwd(M, L.dec[i].mha2.kv, pre, Me, M->at<float>(P.dec[i].kv2), 0, M->sched.side));
+      if (i == 0 && kv_first != kv_done) SKF_HIP(hipEventRecord(kv_first, M->sched.side));
     }
-    SKF_HIP(hipEventRecord(kv_done, M->side));
+    SKF_HIP(hipEventRecord(kv_done, M->sched.side));
   }
   bool dec_qkv_done = false;
   for (int i = 0; i < N; ++i) {
@@ -256,8 +259,8 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
                                       M->at<float>(a.o1), d, M->at<float>(a.astats1), M->cfg.gemm_precision, order, s));
     // out1 = LayerNorm(x + dropout(o1 . Wo + bo)) and q2 = out1 . Wq + bq: one row-owner launch where that kernel runs
     // (skf_ffn_block_fwd_f32 without a feed-forward image), else the fused Dense + LayerNorm launch and the projection launch
-    const bool tail_proj = M->ffn_fused && w.mha1.o.in == d && w.mha1.o.out == d && w.mha2.q.in == d && w.mha2.q.out == d &&
-                           w.mha2.q.ld == d && w.ln1.b == w.ln1.g + (size_t)d;
+    const bool tail_proj = M->ctx.ffn_fused && w.mha1.o.in == d && w.mha1.o.out == d && chains(M, w.mha2.q) && w.mha2.q.out == d &&
+                           w.ln1.b == w.ln1.g + (size_t)d;
     if (tail_proj) {
       SkfFfnBlockFwd tb{};
       tb.struct_size = sizeof(SkfFfnBlockFwd); tb.M = Md; tb.d = d; tb.dff = c.dff; tb.precision = c.gemm_precision;

@@ -1,10 +1,11 @@
 // What the units of the train-step orchestrator share (included by the skf_model*.hip files only): the parameter layout and the two
 // workspace plans, struct SkfModel, and the functions that cross a file boundary.  Those live in namespace skf_model_detail, out of
-// the way of the skf_* launchers; what one unit alone uses stays in that unit's anonymous namespace.
+// the way of the skf_* launchers; what one unit alone uses stays in that unit's anonymous namespace.  A step's host state has three
+// owners, one member of SkfModel each: SideSched (which stream, what waits for what), StepCtx (valid during one call only), ReduceBatch.
 //   skf_model.hip          error slot, config, create / bind / destroy, input staging, graph capture, every skf_model_* entry
 //   skf_model_prof.hip     the launch profiler
 //   skf_model_layout.hip   parameter layout, workspace plans (fp32 and bf16), decode areas
-//   skf_model_sched.hip    Dense helpers, the two-stream weight-gradient scheduler, the batched reduction's bookkeeping
+//   skf_model_sched.hip    Dense helpers, the two-stream scheduler (SideSched), the batched reduction's bookkeeping (ReduceBatch)
 //   skf_model_fwd.hip      fp32 forward                  skf_model_bwd.hip      fp32 backward, embedding sorts
 //   skf_model_decode.hip   KV-cached reconstruction      skf_model_bf16.hip     the bf16 model's launch sequences
 #pragma once
@@ -158,15 +159,95 @@ struct ReduceBatch {
   void end_phase(bool final);
 };
 
+// ------------------------------------------------------------------ the two-stream scheduler (skf_model_sched.hip)
+// The ONE owner of what decides which stream a launch of the fp32 step goes to and what waits for what.  Weight-gradient GEMMs (and
+// the input gradients nobody on the main stream needs soon) are queued per layer and issued as groups on the side stream, off the
+// dgrad critical path; the main stream waits for a group only where it touches one of the group's buffers again.
+struct SideSched {
+  hipStream_t side = nullptr;           // null: the step runs on one stream (use_graph = 1, the bf16 model) and nothing is ever queued
+  hipEvent_t fork_event = nullptr, join_event = nullptr;      // use_graph = 2: the side stream's entry into / exit from the capture
+  std::vector<hipEvent_t> events;       // the pool every event between the two streams is taken from ...
+  size_t next_event = 0;                // ... and its cursor
+  // Side-stream events carry a sequence number (their record order on the in-order side stream): once the main stream has
+  // waited for event k, every event <= k is complete too - later waits for those are dropped (a decoder layer's seven dY
+  // buffers share one `done` event: one barrier packet on the main stream instead of seven, ~5 us each)
+  struct SideEvent { hipEvent_t e; long seq; };
+  long side_seq = 0, side_waited = 0;
+  std::map<const void*, SideEvent> pending_readers;    // buffer -> completion event of its last side-stream reader
+  std::map<const void*, SideEvent> pending_writers;    // buffers a side-stream dgrad still writes
+  // kind 0: dW = X^T dY (+ bias grad); kind 1: an input gradient nobody on the main stream needs soon (dx (+)= dY W^T)
+  struct Queued { DenseP w; const float* x; int ldx; const float* dy; int lddy; int rows; int kind = 0; float* dx = nullptr; int lddx = 0; int accumulate = 0; const int* blocks32 = nullptr; };
+  std::vector<Queued> wq;               // the current layer's group, not yet issued
+  std::vector<Queued> wq_held;          // the PREVIOUS layer's group, held back until the next layer's first kernel is queued (hold)
+
+  int create(bool captured);            // skf_model_create: the stream (+ the fork / join events of a captured two-stream step)
+  void destroy();                       // skf_model_destroy: the pool, the fork / join events, the stream
+  hipEvent_t take_event();              // the pool's next event (created on first use); null = allocation failed
+  // The pool starts again at its first event.  Safe in the middle of a step because every event taken earlier in the call has been
+  // waited for by then (a wait that is already enqueued keeps the record it saw: recording the event again does not move it).  Two
+  // callers: run_forward in front of the decoder (the masks / images events were waited for in front of the first encoder layer)
+  // and begin_backward (the forward's events were waited for by the side stream / in front of the first two cross-attentions).
+  void rewind_events() { next_event = 0; }
+  // A backward starts: the scheduler's start state - both queues and both pending maps empty, the pool rewound (whatever a backward
+  // that returned early left behind goes here, nowhere else)
+  void begin_backward() { wq.clear(); wq_held.clear(); pending_readers.clear(); pending_writers.clear(); rewind_events(); }
+  void queue_wgrad(const DenseP& w, const float* x, int ldx, const float* dy, int lddy, int rows, const int* blocks32) { wq.push_back(Queued{w, x, ldx, dy, lddy, rows, 0, nullptr, 0, 0, blocks32}); }
+  void queue_dgrad(const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate) { wq.push_back(Queued{w, nullptr, 0, dy, lddy, rows, 1, dx, lddx, accumulate}); }
+  bool holding() const { return !wq_held.empty(); }
+  int hold(SkfModel* M, hipStream_t s);           // the queued group becomes the held one
+  // The queued group goes out (behind the held one); ready_recorded: an event that already marks "the main stream is here" (the
+  // completion signal of the launch in front of this call); on_main: the group runs on the main stream, in place
+  int issue(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded = nullptr, bool on_main = false);
+  int issue_held(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded = nullptr);
+  // Main-stream kernels that overwrite `buf` first wait for the side-stream group that still reads it, those that read `buf` for the
+  // deferred input gradient that still writes it (a group that is still queued or held is issued first)
+  int before_write(SkfModel* M, const void* buf, hipStream_t s) { return wait_side(M, false, buf, s); }
+  int before_read(SkfModel* M, const void* buf, hipStream_t s) { return wait_side(M, true, buf, s); }
+  int wait_side(SkfModel* M, bool writers, const void* buf, hipStream_t s);
+  int join(hipStream_t s);              // final flush: the main stream waits for everything on the side stream; nothing stays pending
+  // use_graph = 2 (capture_or_run): the side stream enters the capture of `s` / is joined back before the capture ends
+  bool fork_into_capture(hipStream_t s) { return hipEventRecord(fork_event, s) == hipSuccess && hipStreamWaitEvent(side, fork_event, 0) == hipSuccess; }
+  bool join_capture(hipStream_t s) { return hipEventRecord(join_event, side) == hipSuccess && hipStreamWaitEvent(s, join_event, 0) == hipSuccess; }
+};
+
+// ------------------------------------------------------------------ what is valid during ONE call only
+// Set by one function of a call and consumed by another; nothing here may survive into the next call on the model (whose batch has
+// other live rows, whose events are other events).  reset() runs where the batch is staged (stage_inputs: every entry stages),
+// begin_backward() at the entry of run_backward / run_backward16 for what a backward that returned early may have left set.
+struct StepCtx {
+  // Live rows of the decoder-side backward (skf_row_blocks.hip), set while the decoder layers' gradients are issued: a problem with
+  // exactly `live_rows` rows walks the row-block list of its granule (fp32: 16 / 32 rows; bf16: single rows / 64), everything else
+  // and every problem while no lists are set visits every row
+  bool lists_set = false;
+  int live_rows = 0;
+  const int* live_len = nullptr;        // per-sample live length
+  struct LiveList { int granule; const int* blocks; } lists[2] = {};
+  const int* order = nullptr;           // this call's samples sorted by length (forward), or null
+  hipEvent_t pre_ready = nullptr, masks_ready = nullptr;    // train step: forward_preamble ran on the side stream; the forward waits for the masks before its first attention, for the images behind it
+  bool lists_built = false;             // this step's lists are in P.live16 / P.live32 (issued, not necessarily complete)
+  bool masks_staged = false;            // the padding masks of this call were written by its staging launch (stage_inputs)
+  bool ffn_fused = false;               // the feed-forward blocks run as one launch per direction (skf_ffn_fused.hip); set per forward
+  hipEvent_t last_ready = nullptr;      // ffn_ln_bwd: the event attached to its fused launch (valid until the caller's next main-stream launch)
+
+  void reset() { *this = StepCtx(); }
+  void begin_backward() { clear_live(); last_ready = nullptr; }
+  void set_live(int rows, const int* len, int g0, const int* b0, int g1, const int* b1) { lists_set = true; live_rows = rows; live_len = len; lists[0] = {g0, b0}; lists[1] = {g1, b1}; }
+  void clear_live() { lists_set = false; live_rows = 0; live_len = nullptr; lists[0] = lists[1] = LiveList{}; }
+  bool live(int rows) const { return lists_set && rows == live_rows; }
+  const int* live_lengths(int rows) const { return live(rows) ? live_len : nullptr; }
+  const int* live_blocks(int rows, int granule) const {
+    return !live(rows) ? nullptr : lists[0].granule == granule ? lists[0].blocks : lists[1].granule == granule ? lists[1].blocks : nullptr;
+  }
+};
+
 }  // namespace skf_model_detail
 
 struct SkfModel {
   SkfConfig cfg;
   uint32_t flags = 0;                // skf_model_set_flags
-  bool no_ln_fuse = false, no_relu_bits = false;   // a fused entry answered SKF_EUNSUPPORTED once: this model takes the general pair
-  bool ffn_fused = false;            // the feed-forward blocks run as one launch per direction (skf_ffn_fused.hip); set per forward
-  bool masks_staged = false;         // the padding masks of this call were written by its staging launch (stage_inputs)
-  hipEvent_t last_ready = nullptr;   // ffn_ln_bwd: the event attached to its fused launch (valid until the caller's next main-stream launch)
+  // sticky for the model's lifetime (not per call): a fused entry answered SKF_EUNSUPPORTED once, this model takes the general pair
+  bool no_ln_fuse = false, no_relu_bits = false;
+  skf_model_detail::StepCtx ctx;     // what is valid during one call only
   skf_model_detail::Layout lay;
   skf_model_detail::Plan plan;
   skf_model_detail::Plan16 p16;                        // bf16 path (cfg.act_dtype == SKF_ACT_BF16): its own workspace plan
@@ -179,30 +260,9 @@ struct SkfModel {
   long long dec_dyn_host[2] = {0, 0};
   std::vector<int> dec_stream_host;  // stream ids of a sampled decode on their way to the device
   float g_opt_scale = 0.f;
-  // weight-gradient GEMMs run on a side stream, off the dgrad critical path
-  hipStream_t side = nullptr;
-  hipEvent_t fork_event = nullptr, join_event = nullptr;      // use_graph = 2: the side stream's entry into / exit from the capture
+  skf_model_detail::SideSched sched;                   // the side stream and everything that orders the two streams
   hipEvent_t inputs_staged = nullptr;                         // recorded behind the staging copies of every call (skf_model_wait_inputs_staged)
   bool inputs_staged_valid = false;
-  std::vector<hipEvent_t> events;
-  size_t next_event = 0;
-  // Side-stream events carry a sequence number (their record order on the in-order side stream): once the main stream has
-  // waited for event k, every event <= k is complete too - later waits for those are dropped (a decoder layer's seven dY
-  // buffers share one `done` event: one barrier packet on the main stream instead of seven, ~5 us each)
-  struct SideEvent { hipEvent_t e; long seq; };
-  long side_seq = 0, side_waited = 0;
-  std::map<const void*, SideEvent> pending_readers;    // buffer -> completion event of its last side-stream reader
-  // kind 0: dW = X^T dY (+ bias grad); kind 1: an input gradient nobody on the main stream needs soon (dx (+)= dY W^T)
-  struct QueuedWgrad { skf_model_detail::DenseP w; const float* x; int ldx; const float* dy; int lddy; int rows; int kind = 0; float* dx = nullptr; int lddx = 0; int accumulate = 0; const int* blocks32 = nullptr; };
-  // Live row blocks of the decoder-side backward (skf_row_blocks.hip): set while the decoder layers' gradients are issued,
-  // consulted by dense_dgrad / dense_wgrad for problems with exactly `live_rows` rows; null = every row is visited
-  const int* live16 = nullptr; const int* live32 = nullptr; int live_rows = 0;
-  const int* order = nullptr;        // this step's samples sorted by length (run_forward), or null
-  hipEvent_t pre_ready = nullptr, masks_ready = nullptr;    // train step: forward_preamble ran on the side stream; the forward waits for the masks before its first attention, for the images behind it
-  bool lists_built = false;             // this step's lists are in P.live16 / P.live32 (issued, not necessarily complete)
-  std::map<const void*, SideEvent> pending_writers;    // buffers a side-stream dgrad still writes
-  std::vector<QueuedWgrad> wq;                         // wgrads of the current layer, not yet issued
-  std::vector<QueuedWgrad> wq_held;                    // the PREVIOUS layer's group, held back until the next layer's first kernel is queued (hold_wgrads)
   skf_model_detail::ReduceBatch red;                   // the batched reduction of the step's slabs and partials
   // gradient buckets (data parallelism): the flat gradient buffer becomes final in two pieces, in production order -
   // [dec_off, total) after the decoder backward, [0, dec_off) at the end; an event marks each piece complete so that
@@ -210,17 +270,6 @@ struct SkfModel {
   hipEvent_t bucket_ready[2] = {nullptr, nullptr};
   int n_buckets = 1;
 
-  hipEvent_t new_event() {
-    if (next_event == events.size()) {
-      hipEvent_t e = nullptr;
-      // Events that only order the library's own two streams on ONE device: a device-scope release is all the waiter needs
-      // (the default system-scope fence of hipEventRecord writes caches back for host / peer visibility).  (The gradient-bucket
-      // events handed to the caller keep the default.)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return nullptr;
-      events.push_back(e);
-    }
-    return events[next_event++];
-  }
   // the activations a caller may look at by name (skf_model_buffer / skf_model_buffer_info): filled by register_buffers(16)
   struct Named { size_t off; int rows, cols, ld, bf16; };
   std::map<std::string, Named> named;
@@ -253,7 +302,7 @@ inline unsigned site_dec(int N, int layer, int j) { return 2 + 2 * N + 3 * layer
 // Run `call` with event `e` riding on its LAST launch as that launch's completion signal instead of a packet of its own (skf_common.h:
 // the attach protocol).  *rode = the launch carries it; false = the caller records `e` where it needs it.  Nothing is parked for a null
 // `e`, while the step is being captured, or - the events that hand work to the side stream - without a side stream (`needs_side`).
-inline bool may_park(const SkfModel* M, bool needs_side = true) { return !g_capturing && (M->side || !needs_side); }
+inline bool may_park(const SkfModel* M, bool needs_side = true) { return !g_capturing && (M->sched.side || !needs_side); }
 template <typename F>
 int with_tail_event(SkfModel* M, hipEvent_t e, bool* rode, F call, bool needs_side = true) {
   SkfTailScope scope(may_park(M, needs_side) ? e : nullptr);
@@ -275,12 +324,7 @@ int dense_ln_fwd(SkfModel* M, const DenseP& w, const float* a, int rows, const f
 void* hbits_of(SkfModel* M, size_t off, int rows);
 int dense_fwd_relu_bits(SkfModel* M, const DenseP& w, const float* x, int rows, float* y, void* bits, hipStream_t s);
 int dense_fwd_ld(SkfModel* M, const DenseP& w, const float* x, int ldx, int rows, float* y, int ldy, int act, hipStream_t s);
-int before_write(SkfModel* M, const void* buf, hipStream_t s);
-int before_read(SkfModel* M, const void* buf, hipStream_t s);
 int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const float* dy, int lddy, int rows, hipStream_t s);
-int issue_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded = nullptr, bool on_main = false);
-int issue_held_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded = nullptr);
-int hold_wgrads(SkfModel* M, hipStream_t s);
 int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_queued = true, hipEvent_t main_here = nullptr);
 int dense_dgrad(SkfModel* M, const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate,
                 const float* relu_src, int ld_relu, hipStream_t s, const void* relu_bits = nullptr);

@@ -1,6 +1,6 @@
-// The Dense helpers of the fp32 model and its two-stream weight-gradient scheduler: weight gradients are queued per layer, issued as
-// groups on a side stream (hold / issue / flush), their split-K slabs and the LayerNorm partials reduced by one batched launch per
-// phase (ReduceBatch, skf_model_internal.h).
+// The Dense helpers of the fp32 model and its two-stream scheduler (SideSched, skf_model_internal.h): weight gradients are queued per
+// layer, issued as groups on a side stream (hold / issue / flush), their split-K slabs and the LayerNorm partials reduced by one
+// batched launch per phase (ReduceBatch).
 #include "skf_model_internal.h"
 
 namespace skf_model_detail {
@@ -25,7 +25,7 @@ int dense_ln_fwd(SkfModel* M, const DenseP& w, const float* a, int rows, const f
 }
 // sign-bit buffer of an ffn hidden tensor (rows x dff from d inputs), or null when the shape has no such path
 void* hbits_of(SkfModel* M, size_t off, int rows) {
-  if (M->ffn_fused) return M->at<char>(off);      // (the fused block always writes / reads its own sign-bit words)
+  if (M->ctx.ffn_fused) return M->at<char>(off);      // (the fused block always writes / reads its own sign-bit words)
   if (M->no_relu_bits || !skf_gemm_relu_bits_bytes(rows, M->cfg.dff, M->cfg.d_model, M->cfg.gemm_precision)) return nullptr;
   return M->at<char>(off);
 }
@@ -51,38 +51,46 @@ int dense_wgrad_on(SkfModel* M, const DenseP& w, const float* x, int ldx, const 
   return skf_gemm_f32(0, 0, w.in, w.out, rows, x, ldx, dy, lddy, M->G(w.w), w.ld, nullptr, 0, nullptr, 0, 0, splits,
                       M->G(w.b), 0, M->at<char>(M->plan.gemm_ws), M->plan.gemm_ws_bytes, M->cfg.gemm_precision, s);
 }
-// The main stream waits for the side-stream event `pending` holds for `buf` (unless it already waited for a later one); a queued or
-// held group that `touches` the buffer is issued first.
-template <typename Touches>
-int wait_side(SkfModel* M, std::map<const void*, SkfModel::SideEvent>& pending, const void* buf, hipStream_t s, Touches touches) {
-  for (const auto* qs : {&M->wq_held, &M->wq})
-    for (const auto& q : *qs)
-      if (touches(q)) { SKF_TRY(issue_wgrads(M, s)); break; }
-  auto it = pending.find(buf);
-  if (it == pending.end()) return SKF_OK;
-  if (it->second.seq > M->side_waited) {
-    SKF_HIP(hipStreamWaitEvent(s, it->second.e, 0));
-    M->side_waited = it->second.seq;
-  }
-  pending.erase(it);
+}  // namespace
+
+// ------------------------------------------------------------------ SideSched (skf_model_internal.h)
+int SideSched::create(bool captured) {
+  SKF_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+  if (captured) SKF_HIP(hipEventCreateWithFlags(&fork_event, hipEventDisableTiming));
+  if (captured) SKF_HIP(hipEventCreateWithFlags(&join_event, hipEventDisableTiming));
   return SKF_OK;
 }
-}  // namespace
-// Main-stream kernels that overwrite `buf` must first wait for the side-stream wgrad that still reads it
-// (a wgrad that is still queued is issued first; with the alternating gradient-buffer sets this is the rare case).
-int before_write(SkfModel* M, const void* buf, hipStream_t s) {
-  return wait_side(M, M->pending_readers, buf, s, [buf](const SkfModel::QueuedWgrad& q) { return q.dy == buf || q.x == buf; });
+void SideSched::destroy() {
+  for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {fork_event, join_event}) if (e) (void)hipEventDestroy(e);
+  if (side) (void)hipStreamDestroy(side);
 }
-// Main-stream kernels that read `buf` first wait for the side-stream dgrad that writes it.
-int before_read(SkfModel* M, const void* buf, hipStream_t s) {
-  return wait_side(M, M->pending_writers, buf, s, [buf](const SkfModel::QueuedWgrad& q) { return q.kind == 1 && q.dx == buf; });
+hipEvent_t SideSched::take_event() {
+  if (next_event == events.size()) {
+    hipEvent_t e = nullptr;
+    // Events that only order the library's own two streams on ONE device: a device-scope release is all the waiter needs
+    // (the default system-scope fence of hipEventRecord writes caches back for host / peer visibility).  (The gradient-bucket
+    // events handed to the caller keep the default.)
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return nullptr;
+    events.push_back(e);
+  }
+  return events[next_event++];
 }
-// dW = X^T dY (+ bias grad).  Eager path: queued, and issued per layer on the side stream by issue_wgrads().
-int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const float* dy, int lddy, int rows, hipStream_t s) {
-  if (!M->side) return dense_wgrad_on(M, w, x, ldx, dy, lddy, rows, s);
-  SkfModel::QueuedWgrad q{w, x, ldx, dy, lddy, rows};
-  if (M->live32 && rows == M->live_rows) q.blocks32 = M->live32;
-  M->wq.push_back(q);
+// before_write / before_read: a queued or held group that touches `buf` is issued first (with the alternating gradient-buffer sets the
+// rare case); then the main stream waits for the event the pending map holds for `buf`, unless it already waited for a later one
+int SideSched::wait_side(SkfModel* M, bool writers, const void* buf, hipStream_t s) {
+  auto touches = [&](const Queued& q) { return writers ? q.kind == 1 && q.dx == buf : q.dy == buf || q.x == buf; };
+  for (const auto* qs : {&wq_held, &wq})
+    for (const auto& q : *qs)
+      if (touches(q)) { SKF_TRY(issue(M, s)); break; }
+  auto& pending = writers ? pending_writers : pending_readers;
+  auto it = pending.find(buf);
+  if (it == pending.end()) return SKF_OK;
+  if (it->second.seq > side_waited) {
+    SKF_HIP(hipStreamWaitEvent(s, it->second.e, 0));
+    side_waited = it->second.seq;
+  }
+  pending.erase(it);
   return SKF_OK;
 }
 // Issue the queued wgrads on the side stream: ONE ready event (everything queued on `s` so far is complete before they
@@ -92,35 +100,35 @@ int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const flo
 // stream, the block on the main stream - they ran one after the other (134 + 136 us where 45 + 100 were expected, per layer).  So a
 // layer's group is HELD at the end of the layer and goes out right behind the next layer's first launch: it then runs beside the
 // LayerNorm / projection / attention kernels of that layer, which share CUs with it well.
-int issue_held_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded) {
-  if (M->wq_held.empty()) return SKF_OK;
-  std::vector<SkfModel::QueuedWgrad> cur;
-  cur.swap(M->wq);
-  M->wq.swap(M->wq_held);
-  const int rc = issue_wgrads(M, s, ready_recorded);
-  M->wq.swap(cur);
+int SideSched::issue_held(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded) {
+  if (wq_held.empty()) return SKF_OK;
+  std::vector<Queued> cur;
+  cur.swap(wq);
+  wq.swap(wq_held);
+  const int rc = issue(M, s, ready_recorded);
+  wq.swap(cur);
   return rc;
 }
-int hold_wgrads(SkfModel* M, hipStream_t s) {
-  if (!M->wq_held.empty()) SKF_TRY(issue_wgrads(M, s));       // (never two groups held)
-  M->wq_held.swap(M->wq);
+int SideSched::hold(SkfModel* M, hipStream_t s) {
+  if (!wq_held.empty()) SKF_TRY(issue(M, s));       // (never two groups held)
+  wq_held.swap(wq);
   return SKF_OK;
 }
 // on_main: the queued group runs on the MAIN stream, in place (no events, no hop) - for the one weight gradient at the very end of
 // the backward that the side stream would finish last (see run_backward)
-int issue_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool on_main) {
+int SideSched::issue(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool on_main) {
   SkfTailScope shield(nullptr);      // this function may run INSIDE a parked call (before_write): its side-stream launches must not take that event
-  SKF_TRY(issue_held_wgrads(M, s));                            // the held group first, as a group of its own
-  if (M->wq.empty()) return SKF_OK;
-  std::vector<SkfModel::QueuedWgrad> group;
-  group.swap(M->wq);
-  hipStream_t ws = on_main ? s : M->side;                      // the stream the group runs on
+  SKF_TRY(issue_held(M, s));                                   // the held group first, as a group of its own
+  if (wq.empty()) return SKF_OK;
+  std::vector<Queued> group;
+  group.swap(wq);
+  hipStream_t ws = on_main ? s : side;                         // the stream the group runs on
   hipEvent_t ready = nullptr, done = nullptr;
   if (!on_main) {
-    ready = ready_recorded ? ready_recorded : M->new_event(); done = M->new_event();
+    ready = ready_recorded ? ready_recorded : take_event(); done = take_event();
     SKF_CHECK_ARG(ready && done, "event allocation failed");
     if (!ready_recorded) SKF_HIP(hipEventRecord(ready, s));   // (else: already the completion signal of the launch in front of this call)
-    SKF_HIP(hipStreamWaitEvent(M->side, ready, 0));
+    SKF_HIP(hipStreamWaitEvent(side, ready, 0));
   }
   // deferred input gradients first, with their own completion event: their reader must not wait for the weight gradients
   hipEvent_t dgrad_done = nullptr;
@@ -129,14 +137,14 @@ int issue_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool on_
     const DenseP& w = q.w;
     SKF_TRY(skf_gemm_f32(1, 1, q.rows, w.in, w.out, q.dy, q.lddy, M->P(w.w), w.ld, q.dx, q.lddx, nullptr, 0, nullptr, 0,
                          q.accumulate, 1, nullptr, 0, nullptr, 0, M->cfg.gemm_precision, ws));
-    if (!dgrad_done && !on_main) { dgrad_done = M->new_event(); SKF_CHECK_ARG(dgrad_done, "event allocation failed"); }
+    if (!dgrad_done && !on_main) { dgrad_done = take_event(); SKF_CHECK_ARG(dgrad_done, "event allocation failed"); }
   }
   long dgrad_seq = 0;
-  if (dgrad_done) { SKF_HIP(hipEventRecord(dgrad_done, M->side)); dgrad_seq = ++M->side_seq; }
+  if (dgrad_done) { SKF_HIP(hipEventRecord(dgrad_done, side)); dgrad_seq = ++side_seq; }
   // the large problems of the group: partial tiles by ONE grouped launch (up to 8 problems each); every slab of the phase is
   // reduced by one launch in flush_wgrads()
   std::vector<SkfWgradProblem> probs;
-  std::vector<const SkfModel::QueuedWgrad*> prob_q;
+  std::vector<const Queued*> prob_q;
   for (const auto& q : group) {
     const DenseP& w = q.w;
     if (q.kind == 1) continue;
@@ -172,23 +180,40 @@ int issue_wgrads(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool on_
   }
   M->red.side_used = true;                                         // (the slabs are reduced by the batched launch either way)
   if (on_main) return SKF_OK;                                  // same stream as every later reader / writer of the operands: nothing to track
-  SKF_HIP(hipEventRecord(done, M->side));
-  const long done_seq = ++M->side_seq;
+  SKF_HIP(hipEventRecord(done, side));
+  const long done_seq = ++side_seq;
   for (const auto& q : group) {
-    M->pending_readers[q.dy] = SkfModel::SideEvent{done, done_seq};
-    if (q.x) M->pending_readers[q.x] = SkfModel::SideEvent{done, done_seq};
-    if (q.kind == 1) M->pending_writers[q.dx] = SkfModel::SideEvent{dgrad_done, dgrad_seq};
+    pending_readers[q.dy] = SideEvent{done, done_seq};
+    if (q.x) pending_readers[q.x] = SideEvent{done, done_seq};
+    if (q.kind == 1) pending_writers[q.dx] = SideEvent{dgrad_done, dgrad_seq};
   }
+  return SKF_OK;
+}
+int SideSched::join(hipStream_t s) {
+  hipEvent_t e = take_event();
+  SKF_CHECK_ARG(e, "event allocation failed");
+  SKF_HIP(hipEventRecord(e, side));
+  SKF_HIP(hipStreamWaitEvent(s, e, 0));
+  pending_readers.clear();
+  pending_writers.clear();
+  side_waited = side_seq;        // every event recorded so far is behind the main stream
+  return SKF_OK;
+}
+// dW = X^T dY (+ bias grad).  Two streams: queued, and issued per layer on the side stream (SideSched::issue).
+int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const float* dy, int lddy, int rows, hipStream_t s) {
+  if (!M->sched.side) return dense_wgrad_on(M, w, x, ldx, dy, lddy, rows, s);
+  M->sched.queue_wgrad(w, x, ldx, dy, lddy, rows, M->ctx.live_blocks(rows, 32));
   return SKF_OK;
 }
 // Reduce the split-K partials of the wgrads issued since the last flush (one batched launch on the side stream) and
 // mark gradient bucket `bucket` complete.  final = the main stream waits for the side stream (before the optimizer).
 int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_queued, hipEvent_t main_here) {
-  if (issue_queued) SKF_TRY(issue_wgrads(M, s));      // (false: reduce what has been issued; queued / held groups stay where they are)
+  if (issue_queued) SKF_TRY(M->sched.issue(M, s));      // (false: reduce what has been issued; queued / held groups stay where they are)
   const size_t begin = M->red.begin(), end = M->red.end();
   hipStream_t ready_on = s;
   bool bucket_recorded = false;
-  if (M->side && M->red.side_used && end > begin) {
+  hipStream_t side = M->sched.side;
+  if (side && M->red.side_used && end > begin) {
     if (!M->red.descs_uploaded) {      // the launch sequence is fixed: descriptors are built and uploaded once (first step)
       SKF_HIP(hipMemcpy(M->at<SkfReduceDesc>(M->plan.descs) + begin, M->red.descs.data() + begin,
                         (end - begin) * sizeof(SkfReduceDesc), hipMemcpyHostToDevice));
@@ -199,36 +224,28 @@ int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_
     if (final) {
       // end of the backward: the optimizer waits for this reduction anyway, so it runs on the MAIN stream behind ONE hop
       // (side -> main after the last weight gradient) instead of two (main -> side for the partials, side -> main for the result)
-      hipEvent_t e = M->new_event();
-      SKF_CHECK_ARG(e, "event allocation failed");
-      SKF_HIP(hipEventRecord(e, M->side));
-      SKF_HIP(hipStreamWaitEvent(s, e, 0));
+      SKF_TRY(M->sched.join(s));
       // the bucket-ready event rides on the reduction launch as its completion signal (skf_common.h: SKF_LAUNCH_TAIL)
       SKF_TRY(with_tail_event(M, bucket >= 0 ? M->bucket_ready[bucket] : nullptr, &bucket_recorded, [&] {
         return skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->red.blocks(), s);
       }));
     } else {
-      hipEvent_t em = main_here ? main_here : M->new_event();      // (main_here: already the completion signal of the main stream's last launch)
+      hipEvent_t em = main_here ? main_here : M->sched.take_event();      // (main_here: already the completion signal of the main stream's last launch)
       SKF_CHECK_ARG(em, "event allocation failed");
       if (!main_here) SKF_HIP(hipEventRecord(em, s));
-      SKF_HIP(hipStreamWaitEvent(M->side, em, 0));
-      SKF_TRY(skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->red.blocks(), M->side));
-      ready_on = M->side;
+      SKF_HIP(hipStreamWaitEvent(side, em, 0));
+      SKF_TRY(skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->red.blocks(), side));
+      ready_on = side;
     }
   }
   if (bucket >= 0 && M->bucket_ready[bucket] && !bucket_recorded) SKF_HIP(hipEventRecord(M->bucket_ready[bucket], ready_on));   // bucket < 0: an intermediate reduction
   M->red.end_phase(final);
-  if (final) {
-    M->pending_readers.clear();
-    M->pending_writers.clear();
-    M->side_waited = M->side_seq;        // the main stream has joined the side stream: every event recorded so far is behind it
-  }
   return SKF_OK;
 }
 int dense_dgrad(SkfModel* M, const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate,
                 const float* relu_src, int ld_relu, hipStream_t s, const void* relu_bits) {
-  SKF_TRY(before_write(M, dx, s));
-  const int* blocks = (M->live16 && rows == M->live_rows) ? M->live16 : nullptr;
+  SKF_TRY(M->sched.before_write(M, dx, s));
+  const int* blocks = M->ctx.live_blocks(rows, 16);
   if (relu_bits)      // relu'(hidden) from the sign bits the forward left (skf_gemm_f32_bits): the hidden tensor is not re-read
     return skf_gemm_f32_bits(1, 1, rows, w.in, w.out, dy, lddy, M->P(w.w), w.ld, dx, lddx, nullptr, 0, nullptr, 0,
                              accumulate, 1, nullptr, 0, nullptr, 0, M->cfg.gemm_precision, blocks, 16, nullptr, relu_bits, s);
@@ -241,10 +258,8 @@ int dense_dgrad(SkfModel* M, const DenseP& w, const float* dy, int lddy, int row
 // before_read(dx).  Successive deferred writers of one dx stay in order (one side stream).
 int dense_dgrad_deferred(SkfModel* M, const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate,
                          hipStream_t s) {
-  if (!M->side) return dense_dgrad(M, w, dy, lddy, rows, dx, lddx, accumulate, nullptr, 0, s);
-  SkfModel::QueuedWgrad q{w, nullptr, 0, dy, lddy, rows};
-  q.kind = 1; q.dx = dx; q.lddx = lddx; q.accumulate = accumulate;
-  M->wq.push_back(q);
+  if (!M->sched.side) return dense_dgrad(M, w, dy, lddy, rows, dx, lddx, accumulate, nullptr, 0, s);
+  M->sched.queue_dgrad(w, dy, lddy, rows, dx, lddx, accumulate);
   return SKF_OK;
 }
 

@@ -246,6 +246,56 @@ def test_launch_attached_events_and_input_handover_have_one_owner():
     assert "`SKF_CLONE_INPUTS=1`" in open(os.path.join(ROOT, "tools", "README.md")).read()
 
 
+def test_step_scheduler_and_per_call_state_have_one_owner_each():
+    """The two-stream scheduler's state lives in SideSched (declared in skf_model_internal.h, defined in skf_model_sched.hip) and is
+    named nowhere else; what is valid during one call only lives in StepCtx; struct SkfModel declares neither set of members; and
+    each routing decision of the row-owner launches is stated once."""
+    import glob
+    csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
+    strip = lambda text: re.sub(r"//[^\n]*", "", text)      # noqa: E731  (code only: comments may speak of anything)
+    units = {os.path.basename(p): strip(open(p, encoding="utf-8").read()) for p in glob.glob(os.path.join(csrc, "skf_model*"))}
+    assert len(units) == len(_MODEL_UNITS) + 1 and "skf_model_internal.h" in units, sorted(units)
+    header = units["skf_model_internal.h"]
+    # the owners exist, with their single reset points
+    sched = re.search(r"struct SideSched \{.*?\n\};", header, re.S)
+    ctx = re.search(r"struct StepCtx \{.*?\n\};", header, re.S)
+    model = re.search(r"\nstruct SkfModel \{.*?\n\};", header, re.S)
+    assert sched and ctx and model
+    sched, ctx, model = sched.group(0), ctx.group(0), model.group(0)
+    assert re.search(r"\bSideSched sched;", model) and re.search(r"\bStepCtx ctx;", model)
+    assert len(re.findall(r"\bvoid begin_backward\(\)", sched)) == 1 and len(re.findall(r"\bvoid reset\(\)", ctx)) == 1
+    assert re.search(r"\bbool lists_set\b", ctx) and re.search(r"\blive_blocks\(int rows, int granule\)", ctx)
+    scheduler_names = ("pending_readers", "pending_writers", "wq_held", "side_waited", "side_seq", "next_event")
+    call_names = ("live16", "live32", "live_rows", "lists_built", "masks_staged", "pre_ready", "masks_ready", "last_ready")
+    for name in scheduler_names:
+        word = re.compile(r"\b%s\b" % name)
+        assert word.search(sched), name                       # declared by the owner ...
+        assert not word.search(header.replace(sched, "")), name      # ... and nowhere else in the header
+        users = sorted(u for u, text in units.items() if word.search(text))
+        assert users == ["skf_model_internal.h", "skf_model_sched.hip"], (name, users)
+        begin = re.search(r"void begin_backward\(\) \{[^}]*\}", sched).group(0)
+        if name not in ("side_waited", "side_seq"):           # (the two counters only ever grow)
+            assert name in begin or (name == "next_event" and "rewind_events()" in begin), (name, begin)
+    for name in scheduler_names + call_names:
+        assert not re.search(r"\b%s\b" % name, model), "struct SkfModel declares %s" % name
+    assert "M->ctx.reset()" in units["skf_model.hip"] and sum(text.count("ctx.reset()") for text in units.values()) == 1
+    # the live-row expression, the row-owner routing predicate and the chained-projection width list are stated once
+    sources = glob.glob(os.path.join(csrc, "*"))
+    assert len(sources) > 30
+    for path in sources:
+        assert "live_rows) ?" not in open(path, encoding="utf-8").read(), path
+    bwd, fwd = units["skf_model_bwd.hip"], units["skf_model_fwd.hip"]
+    # top-level functions of the backward unit (a body ends at the first `}` in column 0) that compare against ln_part_stride
+    bodies = re.findall(r"^[A-Za-z][^\n;]*\b(\w+)\([^;{]*\) \{\n(.*?)^\}", bwd, re.S | re.M)
+    assert len(bodies) >= 8 and {"ffn_ln_bwd", "ln_oproj_bwd", "run_backward"} <= {n for n, _ in bodies}, [n for n, _ in bodies]
+    comparing = [n for n, body in bodies if re.search(r"[<>=!]=?\s*(M->plan|P)\.ln_part_stride|ln_part_stride\s*[<>=!]", body)]
+    assert comparing == ["row_owner_takes_ln"] and bwd.count("ln_part_stride") == 1, comparing
+    for caller in ("ffn_ln_bwd", "ln_oproj_bwd", "run_backward"):
+        assert dict(bodies)[caller].count("row_owner_takes_ln(") == 1, caller
+    assert "SKF_CHECK_ARG(!lead_a" in dict(bodies)["ln_oproj_bwd"] and "ln_oproj_bwd_takes_lead" not in bwd
+    assert fwd.count("== 384") == 1 and fwd.count("chains(M, ") >= 3
+
+
 def test_gemm_wsx_isa_has_no_crossed_select_packed_fp32():
     """Round 4 bisected the run-to-run wrong results of round 3's 'accumulate only' epilogue kind to a compiler-formed
     v_pk_add_f32 with crossed operand selects in gemm_wsx_kernel's exit block (skf_gemm_wsx.hip: launch_wsx).  The kind is gone; this

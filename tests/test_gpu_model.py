@@ -709,6 +709,36 @@ def test_two_stream_step_is_deterministic_in_every_model_structure(over):
     assert np.isfinite(a.params.cpu().numpy()).all()
 
 
+@pytest.mark.parametrize("over", [dict(), dict(do_reconstruction=False)], ids=["default", "do_reconstruction=False"])
+def test_call_kinds_interleaved_on_one_model_leave_no_state_behind(over):
+    """What one call sets on the host (live-row lists, the side-stream preamble's events, the scheduler's queues, maps and event
+    cursor) must not reach the next call of another kind.  Two engines from one seed: A takes train_step(b0), train_step(b1); B takes
+    train_step(b0), an inference forward, encode, a 4-step greedy decode, a forward_backward whose gradients are dropped, then
+    train_step(b1).  Parameters and both Adam moments bit-equal, two optimizer steps each.  2 layers: the smallest model with a held
+    weight-gradient group and a deferred K|V input gradient; 64 x 33 = 2112 decoder rows: every d x d weight gradient is above the
+    small-GEMM size (128 x 128 x rows > 2^25), so it takes the grouped slab launches and the batched reduction.  Without a decoder the
+    event pool is never rewound inside the forward (and there is nothing to decode)."""
+    from sketchformer_amd import engine
+    B, L = 64, 34
+    kw = dict(batch=B, seq_len=L, d_model=128, num_heads=8, dff=512, num_layers=2, vocab_size=1004, n_classes=345, lowerdim=64,
+              dropout_rate=0.1, use_graph=False, seed=9)
+    kw.update(over)
+    a, b = (engine.TrainEngine(engine.make_config(**kw), init_seed=4) for _ in range(2))
+    b0, b1, b2, b3 = (synthetic.token_batch(B, L, 1004, 345, seed=80 + i) for i in range(4))
+    a.train_step(*b0)
+    a.train_step(*b1)
+    b.train_step(*b0)
+    b.forward(b2[0], training=False)
+    b.encode(b3[0])
+    if kw.get("do_reconstruction", True):
+        b.greedy_decode(max_steps=4)
+    b.forward_backward(b2[0], None, b2[1])
+    b.train_step(*b1)
+    torch.cuda.synchronize()
+    assert torch.equal(a.params, b.params) and torch.equal(a.adam_m, b.adam_m) and torch.equal(a.adam_v, b.adam_v)
+    assert a.iterations == 2 and b.iterations == 2
+
+
 def test_inputs_staged_event_and_model_flags_reject_misuse():
     """skf_model_wait_inputs_staged before any call has staged inputs, and skf_model_set_flags with an unknown bit, fail loudly
     (SKF_EINVAL with a message); the three defined flag bits are accepted together."""
