@@ -997,6 +997,38 @@ int skf_sketch_encode(const float* flat, long long P, const long long* offsets, 
                       int L, unsigned flags, void* out, float* scale, void* workspace, size_t workspace_bytes,
                       skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Sequence alignment (token edit distance, point DTW)
+ * The reference has nothing in this place: it judges a reconstruction by eye (metrics/samples.py) and its README's retrieval has
+ * no classical baseline.  What is compared here is what the model emits: the ids that models/sketchformer.py `predict` returns
+ * against the ids of utils/tokenizer.py, and the pen positions both decode to (skf_sketch_points).  Both distances are O(La Lb)
+ * dynamic programs per pair; one wavefront sweeps a pair's table as a systolic array (a strip of columns per lane, one cross-lane
+ * move per row), with no table in memory.  Nothing here allocates, synchronises with the host or uses an atomic; two calls on the
+ * same inputs agree bit for bit and a pair's result does not depend on the rest of the batch.
+ * Shared rules.  cross == 0: Na == Nb, out is (Na) and pairs row i of a with row i of b.  cross == 1: out is (Na, Nb) row-major
+ *   and holds every (i, j).  len_* / n_* are int32 on the device, one per row; they are clamped to [0, T] inside the kernel and never
+ *   trusted as an index.  Elements behind a row's length are never read into a result.  lda, ldb: elements of the row's type
+ *   (ids; floats) from row to row.  Limits (SKF_EINVAL): Na, Nb >= 1; 1 <= Ta, Tb <= SKF_ALIGN_MAX_LEN; lda >= Ta, ldb >= Tb (ids),
+ *   lda >= 2 Ta, ldb >= 2 Tb (points); a, b 8-byte aligned (ids), xy_a, xy_b, the lengths and out 4-byte aligned; cross in {0, 1};
+ *   cross == 0 with Na != Nb; cross == 1 with Na * ceil(Nb / 4) >= 2^31.
+ * skf_edit_distance_i64: unit-cost Levenshtein distance (insert, delete, substitute = 1) between ids a[i, 0 .. len_a[i]) and
+ *   b[j, 0 .. len_b[j]): D(0, j) = j, D(i, 0) = i, D(i, j) = min(D(i-1, j) + 1, D(i, j-1) + 1, D(i-1, j-1) + (a_i != b_j)), the
+ *   result is D(len_a, len_b).  Ids are compared as full 64-bit integers.  An empty side gives the other side's length.  Results
+ *   are int32 and exact.
+ * skf_dtw_f32: dynamic time warping between the point rows xy_a[i] and xy_b[j]: (x, y) fp32 pairs as skf_sketch_points writes them
+ *   (the pen byte plays no part), n_a[i] and n_b[j] of them.  Local cost c(i, j) = sqrt(dx * dx + dy * dy), dx = ax - bx,
+ *   dy = ay - by: every operation rounded to fp32 on its own, no fused multiply-add, the square root correctly rounded.
+ *   D(0, 0) = c(0, 0); D(i, 0) = c(i, 0) + D(i-1, 0); D(0, j) = c(0, j) + D(0, j-1);
+ *   D(i, j) = c(i, j) + min(D(i-1, j), D(i, j-1), D(i-1, j-1)); the result is D(n_a - 1, n_b - 1), not normalised.  An empty side is
+ *   replaced by the single point (0, 0), the dummy row the host decoders return for an empty sketch.  Every cell is one fixed
+ *   fp32 expression of its three neighbours (min is exact), so the result does not depend on the order of the sweep: a float32
+ *   numpy restatement matches it BIT FOR BIT.  Non-finite inputs are the caller's error (a NaN or an infinity in a row makes the
+ *   results of its pairs meaningless; nothing else is affected). */
+#define SKF_ALIGN_MAX_LEN 512
+int skf_edit_distance_i64(const long long* a, long long lda, const int* len_a, int Na, int Ta, const long long* b, long long ldb,
+                          const int* len_b, int Nb, int Tb, int cross, int* out, skf_stream_t stream);
+int skf_dtw_f32(const float* xy_a, long long lda, const int* n_a, int Na, int Ta, const float* xy_b, long long ldb, const int* n_b,
+                int Nb, int Tb, int cross, float* out, skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

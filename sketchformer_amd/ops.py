@@ -1021,3 +1021,66 @@ def sketch_encode(flat, offsets, mode, max_seq_len, centers=None, resolution=Non
     _lib.call("skf_sketch_encode", _p(flat), P, _p(offsets), N, ENCODE_MODES[mode], _p(centers), K, L, 1 if clamp else 0, _p(out),
               _p(scale), _p(ws), nbytes, _stream())
     return (out, scale) if return_scale else out
+
+
+ALIGN_MAX_LEN = 512                                               # SKF_ALIGN_MAX_LEN of include/skf.h
+
+
+def _align_lengths(t, name, N, dev):
+    if t.dtype != torch.int32 or tuple(t.shape) != (N,) or not t.is_contiguous() or t.device != dev:
+        raise TypeError("%s must be a contiguous int32 tensor of shape (%d,) on the device of its rows" % (name, N))
+    return t
+
+
+def _align_check(Na, Nb, Ta, Tb, cross):
+    if Na < 1 or Nb < 1 or Ta < 1 or Tb < 1:
+        raise ValueError("both sides need at least one row and one position")
+    if Ta > ALIGN_MAX_LEN or Tb > ALIGN_MAX_LEN:
+        raise ValueError("rows hold at most %d positions (got %d and %d)" % (ALIGN_MAX_LEN, Ta, Tb))
+    if not cross and Na != Nb:
+        raise ValueError("paired mode needs as many rows of a as of b (got %d and %d); cross=True compares every pair" % (Na, Nb))
+
+
+def edit_distance(a, b, len_a, len_b, cross=False):
+    """Unit-cost Levenshtein distance between rows of token ids (skf_edit_distance_i64): a (Na, Ta), b (Nb, Tb) int64 with a unit
+    innermost stride (the row stride is free: a view into a wider row is fine), len_a (Na,), len_b (Nb,) int32 = how many ids of
+    each row count (clamped to [0, T] on the device), T <= 512.  -> int32 (Na,) pairing row i with row i, or with cross=True
+    (Na, Nb) holding every pair.  Exact; ids are compared as 64-bit integers; an empty side gives the other side's length."""
+    for t, name in ((a, "a"), (b, "b")):
+        if t.dtype != torch.int64 or t.dim() != 2:
+            raise TypeError("%s must be an int64 tensor of shape (N, T)" % name)
+        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError("%s must have a unit innermost stride and rows that do not overlap" % name)
+    if b.device != a.device:
+        raise ValueError("a and b must be on one device")
+    (Na, Ta), (Nb, Tb) = a.shape, b.shape
+    _align_lengths(len_a, "len_a", Na, a.device); _align_lengths(len_b, "len_b", Nb, a.device)
+    _align_check(Na, Nb, Ta, Tb, cross)
+    _p(a); _p(b); _p(len_a); _p(len_b)                           # CPU tensors: SkfError before anything is allocated
+    out = torch.empty((Na, Nb) if cross else (Na,), dtype=torch.int32, device=a.device)
+    _lib.call("skf_edit_distance_i64", _p(a), max(a.stride(0), Ta), _p(len_a), Na, Ta, _p(b), max(b.stride(0), Tb), _p(len_b), Nb, Tb,
+              1 if cross else 0, _p(out), _stream())
+    return out
+
+
+def dtw_distance(xy_a, n_a, xy_b, n_b, cross=False):
+    """Dynamic time warping between point rows (skf_dtw_f32): xy_a (Na, Ta, 2), xy_b (Nb, Tb, 2) float32 absolute positions as
+    sketch_points returns them (points contiguous; the row stride is free), n_a (Na,), n_b (Nb,) int32 = the points of each row
+    (clamped to [0, T] on the device), T <= 512.  -> float32 (Na,), or with cross=True (Na, Nb): the accumulated Euclidean
+    distance along the best monotone alignment, not normalised.  An empty row stands for the single point (0, 0).  Every cell is
+    c + min(up, left, diagonal) in float32 without a fused multiply-add: bit-equal to a float32 numpy restatement."""
+    for t, name in ((xy_a, "xy_a"), (xy_b, "xy_b")):
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 2:
+            raise TypeError("%s must be a float32 tensor of shape (N, T, 2)" % name)
+        if t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != 2) or (t.shape[0] > 1 and t.stride(0) < 2 * t.shape[1]):
+            raise ValueError("%s must hold contiguous (x, y) points in rows that do not overlap" % name)
+    if xy_b.device != xy_a.device:
+        raise ValueError("xy_a and xy_b must be on one device")
+    (Na, Ta), (Nb, Tb) = xy_a.shape[:2], xy_b.shape[:2]
+    _align_lengths(n_a, "n_a", Na, xy_a.device); _align_lengths(n_b, "n_b", Nb, xy_a.device)
+    _align_check(Na, Nb, Ta, Tb, cross)
+    _p(xy_a); _p(xy_b); _p(n_a); _p(n_b)                         # CPU tensors: SkfError before anything is allocated
+    out = torch.empty((Na, Nb) if cross else (Na,), dtype=torch.float32, device=xy_a.device)
+    _lib.call("skf_dtw_f32", _p(xy_a), max(xy_a.stride(0), 2 * Ta), _p(n_a), Na, Ta, _p(xy_b), max(xy_b.stride(0), 2 * Tb), _p(n_b), Nb, Tb,
+              1 if cross else 0, _p(out), _stream())
+    return out
