@@ -997,6 +997,36 @@ int skf_sketch_encode(const float* flat, long long P, const long long* offsets, 
                       int L, unsigned flags, void* out, float* scale, void* workspace, size_t workspace_bytes,
                       skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Sketch augmentation (random scale, point dropout)
+ * The training augmentation of continuous sketches, in front of skf_sketch_encode.  The specification is the project's own host
+ * code - DistributedStroke3DataLoader._augment_sketch (random_scale, then augment_strokes) - and the results are BIT-EQUAL to it.
+ * There is no device random generator: the host draws, the device replays.  The reference draws np.random.random() twice per
+ * sketch and once per point whether the draw is used or not, so the stream depends on the lengths alone and one host call
+ * np.random.random(size = 2 N + P) yields it.  Nothing here allocates, synchronises with the host or uses an atomic; every output
+ * element has one writer per launch; two calls on the same inputs agree bit for bit.
+ * skf_sketch_augment: flat (P, 3) fp32 and offsets (N + 1 int64) as for skf_sketch_encode.  rnd: 2 N + P fp64 in the order the host
+ *   draws them: sketch s owns rnd[offsets[s] + 2 s ..]: ux, uy, then one draw u per point.  out_flat has room for P rows (P, 3);
+ *   out_offsets (N + 1 int64) receives the offsets of the augmented sketches, out_offsets[N] = the number of rows kept, P' <= P;
+ *   rows P' .. P - 1 of out_flat are not written.  Per sketch, in this order and precision:
+ *     flags & SKF_AUGMENT_CLAMP: all three columns are clamped to +-1000 first (np.clip);
+ *     fx = (float)(((ux - 0.5) * 2.0) * scale_factor + 1.0), every operation in fp64, rounded to fp32 once; fy likewise from uy;
+ *     x = x * fx, y = y * fy in fp32;
+ *     the loop of augment_strokes over the points: prev = the pen of the last kept row, 1 before the first point; count = 0 where
+ *       pen == 1 or prev == 1, else count + 1; a point is DROPPED when pen == 0 and prev == 0 and count > 2 and u < prob, u and
+ *       prob compared in fp64.  The (x, y) of a dropped point are added to the last kept row in fp32, one add per point in point
+ *       order (not the sum of the run added once); a kept point is copied, pen included.
+ *   No fused multiply-add anywhere.  An empty sketch consumes its two draws and contributes no row.  Hand the result to
+ *   skf_sketch_encode with P' as its P (its offsets must cover its flat exactly) and without SKF_ENCODE_CLAMP: the sketches were
+ *   clamped before the augmentation, like the reference.
+ *   Limits (SKF_EINVAL): N >= 1, 1 <= P < 2^31, 0 < prob <= 1, 0 <= scale_factor < 1, unknown flag bits, pointers not aligned to
+ *   their element, a workspace below skf_sketch_augment_workspace_bytes(P, N) bytes (0 = bad sizes) or not 16-byte aligned; its
+ *   contents carry nothing from one call to the next.  Inputs must be finite. */
+#define SKF_AUGMENT_CLAMP 1u
+size_t skf_sketch_augment_workspace_bytes(long long P, int N);
+int skf_sketch_augment(const float* flat, long long P, const long long* offsets, int N, const double* rnd, double scale_factor,
+                       double prob, unsigned flags, float* out_flat, long long* out_offsets, void* workspace,
+                       size_t workspace_bytes, skf_stream_t stream);
+
 /* ------------------------------------------------------------------ Sequence alignment (token edit distance, point DTW)
  * The reference has nothing in this place: it judges a reconstruction by eye (metrics/samples.py) and its README's retrieval has
  * no classical baseline.  What is compared here is what the model emits: the ids that models/sketchformer.py `predict` returns

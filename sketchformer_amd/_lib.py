@@ -281,6 +281,8 @@ SIGNATURES = {
     "skf_nearest_center_f64": (_I, [_P, _I, _L, _P, _I, _P, _P]),
     "skf_sketch_encode_workspace_bytes": (_Z, [_L, _I]),
     "skf_sketch_encode": (_I, [_P, _L, _P, _I, _I, _P, _I, _I, _U, _P, _P, _P, _Z, _P]),
+    "skf_sketch_augment_workspace_bytes": (_Z, [_L, _I]),
+    "skf_sketch_augment": (_I, [_P, _L, _P, _I, _P, _D, _D, _U, _P, _P, _P, _Z, _P]),
     "skf_edit_distance_i64": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
     "skf_dtw_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
 }

@@ -1023,7 +1023,45 @@ def sketch_encode(flat, offsets, mode, max_seq_len, centers=None, resolution=Non
     return (out, scale) if return_scale else out
 
 
-ALIGN_MAX_LEN = 512                                               # SKF_ALIGN_MAX_LEN of include/skf.h
+def sketch_augment(flat, offsets, rnd, scale_factor, prob, clamp=True):
+    """The training augmentation of continuous sketches (skf_sketch_augment): random scale, then point dropout, bit-equal to the
+    loader's host `_augment_sketch` under the same draws.  flat (P, 3) float32 and offsets (N + 1) int64 as for sketch_encode; rnd
+    (2 N + P) float64 on the same device, in the order the host draws: per sketch ux, uy, then one draw per point
+    (np.random.random(size=2 * N + P) is that stream).  0 <= scale_factor < 1, 0 < prob <= 1.  clamp: all three columns to +-1000
+    first.  -> (out_flat (P', 3) float32, out_offsets (N + 1) int64): the augmented sketches back to back, ready for sketch_encode
+    with clamp=False.  Reading P' = out_offsets[N] is one small device-to-host copy that waits for the current stream: sketch_encode
+    needs offsets that cover its flat exactly, so the rows come back sliced to P' and never at their capacity P."""
+    _p(flat); _p(offsets); _p(rnd)                               # CPU tensors: SkfError before anything is allocated
+    if flat.dtype != torch.float32 or flat.dim() != 2 or flat.shape[1] != 3 or not flat.is_contiguous():
+        raise TypeError("flat must be a contiguous float32 tensor of shape (P, 3)")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.device != flat.device:
+        raise TypeError("offsets must be a contiguous int64 tensor of shape (N + 1,) on the device of flat")
+    P, N = flat.shape[0], offsets.shape[0] - 1
+    if rnd.dtype != torch.float64 or rnd.dim() != 1 or not rnd.is_contiguous() or rnd.device != flat.device:
+        raise TypeError("rnd must be a contiguous float64 tensor of shape (2 N + P,) on the device of flat")
+    if N < 1 or P < 1:
+        raise ValueError("sketch_augment needs at least one sketch and one point")
+    if P >= 1 << 31:
+        raise ValueError("sketch_augment takes fewer than 2^31 points")
+    if rnd.shape[0] != 2 * N + P:
+        raise ValueError("rnd must hold 2 N + P = %d draws (got %d)" % (2 * N + P, rnd.shape[0]))
+    scale_factor, prob = float(scale_factor), float(prob)
+    if not 0.0 <= scale_factor < 1.0:
+        raise ValueError("scale_factor must be in [0, 1)")
+    if not 0.0 < prob <= 1.0:
+        raise ValueError("prob must be in (0, 1]")
+    dev = flat.device
+    out_flat = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    out_offsets = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    nbytes = _lib.load().skf_sketch_augment_workspace_bytes(P, N)
+    ws = _ws(nbytes, dev)
+    _lib.call("skf_sketch_augment", _p(flat), P, _p(offsets), N, _p(rnd), scale_factor, prob, 1 if clamp else 0, _p(out_flat),
+              _p(out_offsets), _p(ws), nbytes, _stream())
+    kept = int(out_offsets[N].item())
+    return out_flat[:kept], out_offsets
+
+
+ALIGN_MAX_LEN = 512                                              # SKF_ALIGN_MAX_LEN of include/skf.h
 
 
 def _align_lengths(t, name, N, dev):

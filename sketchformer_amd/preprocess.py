@@ -30,11 +30,14 @@ def device_path_supported(hps, tokenizer):
                 and (hps["use_continuous_data"] or isinstance(tokenizer, (GridTokenizer, Tokenizer))))
 
 
-def encode_chunk(data, hps, tokenizer, clamp=True, device=None, stream=None):
+def encode_chunk(data, hps, tokenizer, clamp=True, device=None, stream=None, augment=False):
     """One chunk of stroke-3 sketches -> what `preprocess` returns for it: int64 (N, L) tokens, or float64 (N, L, 5) stroke-5 rows
     (cast up from the device's float32, which is exact).  clamp: clamp every column to +-1000 first (off for sketches that were
-    clamped before an augmentation).  Runs on a side stream of its own - the loader calls this from its background thread while the
-    training thread issues steps - and synchronises only that stream."""
+    clamped before an augmentation).  augment: the training augmentation, on the device too (ops.sketch_augment, DESIGN.md section
+    3o) and exactly where the host applies it - continuous data with augment_stroke_prob > 0; it consumes the global numpy stream
+    like the host, 2 N + P draws in one call, and nothing in token modes or at augment_stroke_prob == 0.  Runs on a side stream of
+    its own - the loader calls this from its background thread while the training thread issues steps - and synchronises only
+    that stream."""
     if not device_path_supported(hps, tokenizer):
         raise ValueError("these hparams have no device path (device_path_supported)")
     if len(data) == 0:
@@ -52,7 +55,13 @@ def encode_chunk(data, hps, tokenizer, clamp=True, device=None, stream=None):
     with torch.cuda.device(dev), torch.cuda.stream(side):
         flat_d = torch.from_numpy(flat).to(dev)
         off_d = torch.from_numpy(offsets).to(dev)
-        if hps["use_continuous_data"]:
+        if augment and hps["use_continuous_data"] and hps["augment_stroke_prob"] > 0:
+            # the host's draws in the host's order (two per sketch, then one per point), replayed by the device; the clamp comes
+            # before the augmentation, like the reference, and not again behind it
+            rnd_d = torch.from_numpy(np.random.random(size=2 * len(data) + len(flat))).to(dev)
+            flat_d, off_d = ops.sketch_augment(flat_d, off_d, rnd_d, hps["random_scale_factor"], hps["augment_stroke_prob"], clamp=clamp)
+            out = ops.sketch_encode(flat_d, off_d, 'stroke5', L, clamp=False)
+        elif hps["use_continuous_data"]:
             out = ops.sketch_encode(flat_d, off_d, 'stroke5', L, clamp=clamp)
         elif isinstance(tokenizer, GridTokenizer):
             out = ops.sketch_encode(flat_d, off_d, 'grid', L, resolution=tokenizer.resolution, clamp=clamp)
