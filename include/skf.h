@@ -1027,6 +1027,54 @@ int skf_sketch_augment(const float* flat, long long P, const long long* offsets,
                        double prob, unsigned flags, float* out_flat, long long* out_offsets, void* workspace,
                        size_t workspace_bytes, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Stroke simplification (Ramer-Douglas-Peucker)
+ * The step in front of everything above: raw drawings -> the simplified stroke-3 sketches the loaders read (QuickDraw's published
+ * files are its raw drawings after RDP at epsilon 2.0; the reference pulls in the `rdp` package for user drawings).  The
+ * specification is the project's own host restatement (tests/simplify_reference.py) and the results are BIT-EQUAL to it.
+ * The rule.  A polyline of n points (x, y) in fp32, indices 0 .. n - 1.  Points 0 and n - 1 are kept; n <= 2 keeps everything.  A
+ *   segment (a, b) with b - a >= 2 is examined so, the inputs widened to fp64 and every operation rounded to fp64 on its own (no
+ *   fused multiply-add): ex = xb - xa, ey = yb - ya; for every interior i: px = xi - xa, py = yi - ya; if ex == 0 and ey == 0 (a
+ *   closed or degenerate segment) m_i = px * px + py * py and L2 = 1, otherwise c = ex * py - ey * px, m_i = c * c and
+ *   L2 = ex * ex + ey * ey; k = the LOWEST index with the largest m; if m_k > (epsilon * epsilon) * L2 (strict; epsilon * epsilon
+ *   is one fp64 product) k is kept and (a, k) and (k, b) are examined, otherwise nothing between a and b is kept.  There is no
+ *   division and no square root: for integer-valued coordinates (QuickDraw's 0 .. 255 grid) every quantity is an exact integer in
+ *   fp64 and the result is exact RDP.  The kept set depends on the per-segment decisions alone, so the order in which segments are
+ *   examined is free: the device examines all live segments of a recursion level at once, one wavefront per polyline, and needs
+ *   as many levels as the recursion is deep (n - 1 for a zigzag of shrinking amplitude).
+ * Nothing here allocates, synchronises with the host or uses an atomic; every output element has one writer per launch; two calls
+ * on the same inputs agree bit for bit and a polyline's result does not depend on the rest of the batch.  Polyline length is not
+ * limited: up to SKF_RDP_LDS_POINTS points a wavefront holds its polyline on chip, a longer one runs from the workspace with the
+ * same result.  Inputs must be finite.
+ * skf_rdp_f32: xy (P, 2) fp32 absolute points, ldp floats from row to row; stroke_offsets (S + 1 int64, on the device,
+ *   non-decreasing from 0 to P: stroke s owns points stroke_offsets[s] .. stroke_offsets[s + 1] - 1; the caller checks that, the
+ *   kernel clamps what it reads and never trusts it as an index).  keep (P bytes): 1 = kept, 0 = dropped, every byte a stroke owns
+ *   is written exactly once; an empty stroke writes nothing.
+ *   Limits (SKF_EINVAL): S >= 1, 1 <= P < 2^31, ldp >= 2, epsilon finite and >= 0, xy and stroke_offsets not aligned to their
+ *   element, a workspace below skf_rdp_workspace_bytes(P) bytes (0 = bad size) or not 16-byte aligned; its contents carry
+ *   nothing from one call to the next.
+ * skf_stroke3_simplify: flat (P, 3) fp32 rows (dx, dy, pen) and offsets (N + 1 int64) as for skf_sketch_encode and
+ *   skf_sketch_augment.  Per sketch, in this order:
+ *     the absolute position A_j of row j is the sequential fp32 running sum of dx and of dy, one add per point (the grid
+ *       tokenizer's rule); the position before the first row is (0, 0);
+ *     a stroke is a run of rows that ends at a row with pen == 1, or at the sketch's last row;
+ *     the rule above runs per stroke over its absolute points (stroke ends are always kept: pen values and the number of strokes
+ *       do not change);
+ *     a kept row j gives the output row (A_j - A_prev, pen_j), one fp32 subtraction per coordinate, A_prev the position of the
+ *       kept row before it in the same sketch, (0, 0) for the first.
+ *   out_flat has room for P rows (P, 3); out_offsets (N + 1 int64) receives the offsets of the simplified sketches,
+ *   out_offsets[N] = the number of rows kept, P' <= P; rows P' .. P - 1 of out_flat are not written.  An empty sketch contributes
+ *   no row.  flags: none defined, must be 0.
+ *   Limits (SKF_EINVAL): N >= 1, 1 <= P < 2^31, epsilon finite and >= 0, flags != 0, pointers not aligned to their element, a
+ *   workspace below skf_stroke3_simplify_workspace_bytes(P, N) bytes (0 = bad sizes) or not 16-byte aligned; its contents carry
+ *   nothing from one call to the next. */
+#define SKF_RDP_LDS_POINTS 512
+size_t skf_rdp_workspace_bytes(long long P);
+int skf_rdp_f32(const float* xy, int ldp, long long P, const long long* stroke_offsets, int S, double epsilon, unsigned char* keep,
+                void* workspace, size_t workspace_bytes, skf_stream_t stream);
+size_t skf_stroke3_simplify_workspace_bytes(long long P, int N);
+int skf_stroke3_simplify(const float* flat, long long P, const long long* offsets, int N, double epsilon, unsigned flags,
+                         float* out_flat, long long* out_offsets, void* workspace, size_t workspace_bytes, skf_stream_t stream);
+
 /* ------------------------------------------------------------------ Sequence alignment (token edit distance, point DTW)
  * The reference has nothing in this place: it judges a reconstruction by eye (metrics/samples.py) and its README's retrieval has
  * no classical baseline.  What is compared here is what the model emits: the ids that models/sketchformer.py `predict` returns

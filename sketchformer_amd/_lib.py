@@ -283,6 +283,10 @@ SIGNATURES = {
     "skf_sketch_encode": (_I, [_P, _L, _P, _I, _I, _P, _I, _I, _U, _P, _P, _P, _Z, _P]),
     "skf_sketch_augment_workspace_bytes": (_Z, [_L, _I]),
     "skf_sketch_augment": (_I, [_P, _L, _P, _I, _P, _D, _D, _U, _P, _P, _P, _Z, _P]),
+    "skf_rdp_workspace_bytes": (_Z, [_L]),
+    "skf_rdp_f32": (_I, [_P, _I, _L, _P, _I, _D, _P, _P, _Z, _P]),
+    "skf_stroke3_simplify_workspace_bytes": (_Z, [_L, _I]),
+    "skf_stroke3_simplify": (_I, [_P, _L, _P, _I, _D, _U, _P, _P, _P, _Z, _P]),
     "skf_edit_distance_i64": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
     "skf_dtw_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
 }

@@ -1061,6 +1061,72 @@ def sketch_augment(flat, offsets, rnd, scale_factor, prob, clamp=True):
     return out_flat[:kept], out_offsets
 
 
+RDP_LDS_POINTS = 512                                             # SKF_RDP_LDS_POINTS of include/skf.h
+
+
+def _rdp_epsilon(epsilon):
+    epsilon = float(epsilon)
+    if not 0.0 <= epsilon < float("inf"):                        # (false for a NaN)
+        raise ValueError("epsilon must be finite and not negative (got %r)" % epsilon)
+    return epsilon
+
+
+def rdp_keep(xy, stroke_offsets, epsilon):
+    """Ramer-Douglas-Peucker keep mask of S polylines (skf_rdp_f32), bit-equal to the host restatement of the rule in
+    include/skf.h.  xy (P, 2) float32 absolute points with a unit innermost stride (the row stride is free); stroke_offsets (S + 1)
+    int64 on the same device, non-decreasing from 0 to P (the caller checks that on the host); epsilon finite, >= 0, in the units
+    of xy.  -> uint8 (P,): 1 = kept.  The ends of every polyline are kept; a polyline of any length is accepted."""
+    _p(xy); _p(stroke_offsets)                                   # CPU tensors: SkfError before anything is allocated
+    if xy.dtype != torch.float32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.stride(1) != 1:
+        raise TypeError("xy must be a float32 tensor of shape (P, 2) with a unit innermost stride")
+    if stroke_offsets.dtype != torch.int64 or stroke_offsets.dim() != 1 or not stroke_offsets.is_contiguous() \
+            or stroke_offsets.device != xy.device:
+        raise TypeError("stroke_offsets must be a contiguous int64 tensor of shape (S + 1,) on the device of xy")
+    P, S = xy.shape[0], stroke_offsets.shape[0] - 1
+    epsilon = _rdp_epsilon(epsilon)
+    if S < 1 or P < 1:
+        raise ValueError("rdp_keep needs at least one polyline and one point")
+    if P >= 1 << 31:
+        raise ValueError("rdp_keep takes fewer than 2^31 points")
+    ldp = xy.stride(0) if P > 1 else 2                           # (the row stride of a single row is never used)
+    if ldp < 2:                                                  # an expanded or overlapping view: rows the tensor does not own
+        raise ValueError("the rows of xy must not overlap (row stride %d < 2)" % ldp)
+    if ldp >= 1 << 31:
+        raise ValueError("the row stride of xy must be below 2^31")
+    keep = torch.empty(P, dtype=torch.uint8, device=xy.device)
+    nbytes = _lib.load().skf_rdp_workspace_bytes(P)
+    ws = _ws(nbytes, xy.device)
+    _lib.call("skf_rdp_f32", _p(xy), ldp, P, _p(stroke_offsets), S, epsilon, _p(keep), _p(ws), nbytes, _stream())
+    return keep
+
+
+def stroke3_simplify(flat, offsets, epsilon):
+    """Stroke-3 sketches simplified stroke by stroke (skf_stroke3_simplify): positions by the sequential fp32 running sum, the RDP
+    rule of include/skf.h per stroke, the kept rows as offsets from the kept row before them.  flat (P, 3) float32 and offsets
+    (N + 1) int64 as for sketch_encode.  -> (out_flat (P', 3) float32, out_offsets (N + 1) int64).  Stroke ends are always kept:
+    pen values and the number of strokes do not change.  Reading P' = out_offsets[N] is one small device-to-host copy that waits
+    for the current stream."""
+    _p(flat); _p(offsets)                                        # CPU tensors: SkfError before anything is allocated
+    if flat.dtype != torch.float32 or flat.dim() != 2 or flat.shape[1] != 3 or not flat.is_contiguous():
+        raise TypeError("flat must be a contiguous float32 tensor of shape (P, 3)")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.device != flat.device:
+        raise TypeError("offsets must be a contiguous int64 tensor of shape (N + 1,) on the device of flat")
+    P, N = flat.shape[0], offsets.shape[0] - 1
+    epsilon = _rdp_epsilon(epsilon)
+    if N < 1 or P < 1:
+        raise ValueError("stroke3_simplify needs at least one sketch and one point")
+    if P >= 1 << 31:
+        raise ValueError("stroke3_simplify takes fewer than 2^31 points")
+    dev = flat.device
+    out_flat = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    out_offsets = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    nbytes = _lib.load().skf_stroke3_simplify_workspace_bytes(P, N)
+    ws = _ws(nbytes, dev)
+    _lib.call("skf_stroke3_simplify", _p(flat), P, _p(offsets), N, epsilon, 0, _p(out_flat), _p(out_offsets), _p(ws), nbytes, _stream())
+    kept = int(out_offsets[N].item())
+    return out_flat[:kept], out_offsets
+
+
 ALIGN_MAX_LEN = 512                                              # SKF_ALIGN_MAX_LEN of include/skf.h
 
 
