@@ -14,18 +14,16 @@
 //   * No contraction.  This file is compiled with -ffp-contract=off (build.SOURCE_FLAGS) and carries the pragma below as well: the
 //     scale factor's multiply and add, and the scaling multiply followed by a merging add, are rounded one by one.
 //
-// Launches of skf_sketch_augment: count (per sketch: the keep bit of every point, the number of kept rows) -> offsets (one block:
-// exclusive scan of the N counts) -> write (per sketch: the compacted rows with the merged sums).  No atomics; every output element
+// Launches of skf_sketch_augment: count (per sketch: the keep bit of every point, the number of kept rows) -> offsets (the shared
+// scan of skf_ragged.hip) -> write (per sketch: the compacted rows with the merged sums).  No atomics; every output element
 // has one writer per launch and the launches are ordered by the stream.
-#include "skf_common.h"
+#include "skf_ragged.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int AUG_THREADS = 64;           // one wave per workgroup, like the encode scan: 70k sketches are ~1100 waves
-constexpr int OFFS_THREADS = 1024;        // the block width of the offsets scan: N counts go through in tiles of this many
-constexpr float AUG_LIMIT = 1000.0f;
 
 struct AugmentParams {
   const float* flat;            // (P, 3) rows (dx, dy, pen)
@@ -40,16 +38,6 @@ struct AugmentParams {
   unsigned char* keep;          // workspace: per point, 1 = kept, 0 = merged into the kept row before it
 };
 
-__device__ __forceinline__ float aug_clamp(float v, int clamp) { return clamp ? fminf(fmaxf(v, -AUG_LIMIT), AUG_LIMIT) : v; }
-
-// the rows of sketch s inside flat, whatever the offsets hold
-__device__ __forceinline__ void aug_range(const AugmentParams& q, long long s, long long& beg, int& n) {
-  const long long a0 = q.offsets[s], a1 = q.offsets[s + 1];
-  beg = a0 < 0 ? 0 : (a0 > q.P ? q.P : a0);
-  const long long end = a1 < beg ? beg : (a1 > q.P ? q.P : a1);
-  n = (int)(end - beg);                                                        // P < 2^31
-}
-
 // Walk 1.  augment_strokes' loop without its arithmetic: prev is the pen of the last kept row (1 before the first point), count
 // the distance to the last point where either pen was 1; a point goes when pen == 0, prev == 0, count > 2 and its draw is below
 // prob.  A dropped point has pen 0 and so has the row it is merged into: prev only changes at kept points.
@@ -58,49 +46,20 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_count_kernel(AugmentParam
   if (s >= q.N) return;
   long long beg;
   int n;
-  aug_range(q, s, beg, n);
+  skf_ragged_range(q.offsets, s, q.P, beg, n);
   const float* rows = q.flat + 3 * (size_t)beg;
   const double* u = q.rnd + (size_t)beg + 2 * (size_t)s + 2;                   // behind the sketch's two scale draws
   unsigned char* keep = q.keep + (size_t)beg;
   float prev = 1.0f;
   int count = 0, kept = 0;
   for (int t = 0; t < n; ++t) {
-    const float pen = aug_clamp(rows[3 * t + 2], q.clamp);
+    const float pen = skf_sketch_clamp(rows[3 * t + 2], q.clamp);
     count = (pen == 1.0f || prev == 1.0f) ? 0 : count + 1;
     const bool drop = pen == 0.0f && prev == 0.0f && count > 2 && u[t] < q.prob;
     keep[t] = drop ? 0 : 1;
     if (!drop) { prev = pen; ++kept; }
   }
   q.counts[s] = kept;
-}
-
-// out_offsets[0] = 0, out_offsets[i + 1] = counts[0] + .. + counts[i].  One block walks the counts in tiles of OFFS_THREADS with a
-// carry: a shuffle scan inside every wave, the waves' totals through LDS.  Integer sums: the order is free.
-__global__ __launch_bounds__(OFFS_THREADS) void augment_offsets_kernel(const int* __restrict__ counts, int N,
-                                                                        long long* __restrict__ out_offsets) {
-  __shared__ long long wave_total[OFFS_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long carry = 0;
-  for (long long base = 0; base < N; base += OFFS_THREADS) {                   // (the trip count is the same for every thread)
-    const long long i = base + threadIdx.x;
-    long long v = i < N ? (long long)counts[i] : 0;
-    for (int d = 1; d < 64; d <<= 1) {
-      const long long up = __shfl_up(v, d, 64);
-      if (lane >= d) v += up;
-    }
-    if (lane == 63) wave_total[wave] = v;
-    __syncthreads();
-    long long before = 0, total = 0;
-    for (int w = 0; w < OFFS_THREADS / 64; ++w) {
-      const long long t = wave_total[w];
-      if (w < wave) before += t;
-      total += t;
-    }
-    if (i < N) out_offsets[i + 1] = carry + before + v;
-    carry += total;
-    __syncthreads();                                                           // wave_total is rewritten by the next tile
-  }
-  if (threadIdx.x == 0) out_offsets[0] = 0;
 }
 
 // Walk 2.  fx, fy in float64 and rounded once; every point scaled in fp32; a kept point opens a row, a dropped point is added to
@@ -110,7 +69,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_write_kernel(AugmentParam
   if (s >= q.N) return;
   long long beg;
   int n;
-  aug_range(q, s, beg, n);
+  skf_ragged_range(q.offsets, s, q.P, beg, n);
   if (n == 0) return;
   const float* rows = q.flat + 3 * (size_t)beg;
   const unsigned char* keep = q.keep + (size_t)beg;
@@ -121,13 +80,13 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_write_kernel(AugmentParam
   float ax = 0.0f, ay = 0.0f, ap = 0.0f;
   bool open = false;
   for (int t = 0; t < n; ++t) {
-    const float x = aug_clamp(rows[3 * t], q.clamp) * fx;
-    const float y = aug_clamp(rows[3 * t + 1], q.clamp) * fy;
+    const float x = skf_sketch_clamp(rows[3 * t], q.clamp) * fx;
+    const float y = skf_sketch_clamp(rows[3 * t + 1], q.clamp) * fy;
     if (keep[t]) {
       // (o < P: offsets that overlap - the caller's error - would count more rows than out_flat holds)
       if (open && o < q.P) { float* r = q.out_flat + 3 * (size_t)o; r[0] = ax; r[1] = ay; r[2] = ap; }
       if (open) ++o;
-      ax = x; ay = y; ap = aug_clamp(rows[3 * t + 2], q.clamp);
+      ax = x; ay = y; ap = skf_sketch_clamp(rows[3 * t + 2], q.clamp);
       open = true;
     } else {
       ax = ax + x; ay = ay + y;
@@ -136,39 +95,40 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_write_kernel(AugmentParam
   if (open && o < q.P) { float* r = q.out_flat + 3 * (size_t)o; r[0] = ax; r[1] = ay; r[2] = ap; }
 }
 
-constexpr size_t aug_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// the workspace of skf_sketch_augment; returns its size
+size_t augment_carve(void* ws, long long P, int N, AugmentParams& q) {
+  SkfWsCarver c(ws);
+  q.counts = c.take<int>(N); q.keep = c.take<unsigned char>(P);
+  return c.used;
+}
 
 }  // namespace
 
 extern "C" size_t skf_sketch_augment_workspace_bytes(long long P, int N) {
   if (P < 1 || P >= (1ll << 31) || N < 1) return 0;
-  return aug_align((size_t)N * sizeof(int)) + aug_align((size_t)P);
+  AugmentParams q;
+  return augment_carve(nullptr, P, N, q);
 }
 
 extern "C" int skf_sketch_augment(const float* flat, long long P, const long long* offsets, int N, const double* rnd,
                                   double scale_factor, double prob, unsigned flags, float* out_flat, long long* out_offsets,
                                   void* workspace, size_t workspace_bytes, skf_stream_t stream) {
-  SKF_CHECK_ARG(flat && offsets && rnd && out_flat && out_offsets && workspace, "null pointer");
-  SKF_CHECK_ARG(N >= 1, "N must be at least 1");
-  SKF_CHECK_ARG(P >= 1 && P < (1ll << 31), "P must be in [1, 2^31)");
+  SKF_RAGGED_CHECK_ARGS(flat, P, offsets, N, workspace, workspace_bytes, skf_sketch_augment_workspace_bytes(P, N));
+  SKF_CHECK_ARG(rnd && out_flat && out_offsets, "null pointer");
   SKF_CHECK_ARG(prob > 0.0 && prob <= 1.0, "prob must be in (0, 1]");
   SKF_CHECK_ARG(scale_factor >= 0.0 && scale_factor < 1.0, "scale_factor must be in [0, 1)");
   SKF_CHECK_ARG((flags & ~(unsigned)SKF_AUGMENT_CLAMP) == 0, "unknown flag");
-  SKF_CHECK_ARG(((uintptr_t)flat & 3) == 0 && ((uintptr_t)offsets & 7) == 0 && ((uintptr_t)rnd & 7) == 0 &&
-                    ((uintptr_t)out_flat & 3) == 0 && ((uintptr_t)out_offsets & 7) == 0 && ((uintptr_t)workspace & 15) == 0,
-                "flat, offsets, rnd, out_flat, out_offsets must be aligned to their element, the workspace to 16 bytes");
-  SKF_CHECK_ARG(workspace_bytes >= skf_sketch_augment_workspace_bytes(P, N), "workspace too small");
+  SKF_CHECK_ARG(((uintptr_t)rnd & 7) == 0 && ((uintptr_t)out_flat & 3) == 0 && ((uintptr_t)out_offsets & 7) == 0,
+                "rnd, out_flat, out_offsets must be aligned to their element");
   hipStream_t st = (hipStream_t)stream;
   AugmentParams q;
   q.flat = flat; q.offsets = offsets; q.rnd = rnd; q.P = P; q.N = N; q.clamp = (flags & SKF_AUGMENT_CLAMP) ? 1 : 0;
   q.scale_factor = scale_factor; q.prob = prob; q.out_flat = out_flat; q.out_offsets = out_offsets;
-  char* ws = (char*)workspace;
-  q.counts = (int*)ws;
-  q.keep = (unsigned char*)(ws + aug_align((size_t)N * sizeof(int)));
+  augment_carve(workspace, P, N, q);
 
   hipLaunchKernelGGL(augment_count_kernel, dim3(skf_cdiv(N, AUG_THREADS)), dim3(AUG_THREADS), 0, st, q);
   SKF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(augment_offsets_kernel, dim3(1), dim3(OFFS_THREADS), 0, st, (const int*)q.counts, N, out_offsets);
+  skf_counts_to_offsets_launch(q.counts, N, out_offsets, st);
   SKF_LAUNCH_CHECK();
   hipLaunchKernelGGL(augment_write_kernel, dim3(skf_cdiv(N, AUG_THREADS)), dim3(AUG_THREADS), 0, st, q);
   SKF_LAUNCH_CHECK();

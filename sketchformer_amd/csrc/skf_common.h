@@ -72,8 +72,22 @@ int skf_expander_bwd_partials(const float* dpre, const float* emb, const float* 
 int skf_stage_inputs_launch(const void* inp, void* dinp, const void* tar, void* dtar, size_t row, size_t src_row, size_t copy, int batch,
                             const void* labels, void* dlabels, hipStream_t st, unsigned char* emask = nullptr, unsigned char* dmask = nullptr,
                             int mask_L = 0);
+// skf_ragged.hip: out_offsets[0] = 0, out_offsets[i + 1] = counts[0] + .. + counts[i]; one launch, the caller checks it
+// (SKF_LAUNCH_CHECK).
+int skf_counts_to_offsets_launch(const int* counts, int N, long long* out_offsets, hipStream_t stream);
 
 static inline int skf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Workspaces are cut into regions that each start on a 256-byte boundary.  An operation states its layout ONCE, as a function that
+// takes its regions from a carver in order; its *_workspace_bytes runs that function on a null base and returns `used`, its entry
+// point runs it on the caller's buffer.
+constexpr size_t skf_ws_align(size_t n) { return (n + 255) & ~(size_t)255; }
+struct SkfWsCarver {
+  uintptr_t base;
+  size_t used = 0;
+  explicit SkfWsCarver(void* ws) : base((uintptr_t)ws) {}
+  template <class T> T* take(size_t count) { T* p = (T*)(base + used); used += skf_ws_align(count * sizeof(T)); return p; }
+};
 
 // An event that means "everything this stream was given so far is complete" costs the stream ~5 us as a packet of its own
 // (hipEventRecord) and ~1.3 us attached to the kernel launch in front of it as that command's completion signal (hipExtLaunchKernelGGL's
@@ -178,6 +192,20 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// The fp64 sum over a 256-thread block, sRed = 4 doubles of LDS; every thread gets the sum.  The order (butterfly, then waves
+// 0..3) is fixed: it is part of the bit-equality of the k-means and t-SNE results.
+__device__ __forceinline__ double block_sum(double v, double* sRed) {
+  v = wave_sum(v);
+  __syncthreads();                                // sRed of the previous use is read
+  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
 }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -17,12 +17,6 @@ constexpr int ITP_PAIRS = ITP_THREADS / SKF_WAVE;      // pairs per workgroup
 constexpr int ITP_MAXT = 256;
 constexpr int ITP_MAXD = 4096;
 
-__device__ __forceinline__ double itp_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(ITP_THREADS) void interpolate_kernel(const float* a, int lda, const float* b, int ldb, int P, int d,
                                                                   const float* t, int T, int mode, float* out, int ldo) {
   __shared__ float sW[ITP_PAIRS][2 * ITP_MAXT];         // [w0 of the T steps | w1 of the T steps] per wave
@@ -44,7 +38,7 @@ __global__ __launch_bounds__(ITP_THREADS) void interpolate_kernel(const float* a
         aa = fma(x2, x2, aa); bb = fma(y2, y2, bb); ab = fma(x2, y2, ab);
         aa = fma(x3, x3, aa); bb = fma(y3, y3, bb); ab = fma(x3, y3, ab);
       }
-      aa = itp_wave_sum(aa); bb = itp_wave_sum(bb); ab = itp_wave_sum(ab);
+      aa = wave_sum(aa); bb = wave_sum(bb); ab = wave_sum(ab);
       // the reference takes arccos of the unclamped dot product of the normalised rows (NaN once rounding pushes it past 1);
       // clamped, those pairs land in the branch below
       const double cs = fmin(1.0, fmax(-1.0, ab / sqrt(aa * bb)));

@@ -33,20 +33,6 @@ struct KmParams {
   long N; int ldp, ldc, K, ntiles; float scale;
 };
 
-__device__ __forceinline__ double km_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// every thread gets the sum; the order (butterfly, then waves 0..3) is fixed
-__device__ __forceinline__ double km_block_sum(double v, double* sRed) {
-  v = km_wave_sum(v);
-  __syncthreads();                                // sRed of the previous use is read
-  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
-}
-
 template <bool ACC>
 __global__ __launch_bounds__(KM_THREADS) void kmeans_assign_kernel(KmParams p) {
   extern __shared__ __align__(16) unsigned char km_smem[];
@@ -105,7 +91,7 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_assign_kernel(KmParams p) {
       }
     }
     if (ACC) {
-      part = km_block_sum(part, sRed);
+      part = block_sum(part, sRed);
       if (tid == 0) p.partials[tile] = part;
     }
   }
@@ -143,9 +129,9 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_update_kernel(float* ctr, i
     c[0] = nx; c[1] = ny;
   }
   for (int t = tid; t < ntiles; t += KM_THREADS) inertia += partials[t];
-  shift = km_block_sum(shift, sRed);
-  inertia = km_block_sum(inertia, sRed);
-  empty = km_block_sum(empty, sRed);
+  shift = block_sum(shift, sRed);
+  inertia = block_sum(inertia, sRed);
+  empty = block_sum(empty, sRed);
   if (tid == 0) {
     state->iterations += 1;
     state->n_empty = (int)empty;
@@ -156,8 +142,12 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_update_kernel(float* ctr, i
 }
 
 bool km_sizes_ok(long long N, int K) { return N >= 1 && N < (1ll << 31) && K >= 1 && K <= KM_MAXK; }
-size_t km_align(size_t n) { return (n + 255) & ~(size_t)255; }
-size_t km_acc_bytes(int K) { return km_align((size_t)K * 16) + km_align((size_t)K * 4); }      // sums, counts: zeroed every step
+// the workspace of skf_kmeans_step_f32: sums and counts (zeroed every step: all in front of the partials), a partial per tile; -> its size
+size_t km_carve(void* ws, long long N, int K, KmParams& p) {
+  SkfWsCarver c(ws);
+  p.sums = c.take<u64>(2 * (size_t)K); p.counts = c.take<unsigned>(K); p.partials = c.take<double>(skf_cdiv((long)N, KM_TILE));
+  return c.used;
+}
 size_t km_smem_bytes(int K, bool acc) {
   const size_t Kp = ((size_t)K + 1) & ~(size_t)1;
   return Kp * 8 + (acc ? (size_t)K * 16 + 32 + (size_t)K * 4 : 0);
@@ -204,7 +194,8 @@ int km_launch_assign(const KmParams& p, hipStream_t st) {
 
 extern "C" size_t skf_kmeans_workspace_bytes(long long N, int K) {
   if (!km_sizes_ok(N, K)) return 0;
-  return km_acc_bytes(K) + km_align((size_t)skf_cdiv((long)N, KM_TILE) * 8);
+  KmParams p;
+  return km_carve(nullptr, N, K, p);
 }
 
 extern "C" int skf_kmeans_assign_f32(const float* points, int ldp, long long N, int d, const float* centers, int ldc, int K,
@@ -230,14 +221,12 @@ extern "C" int skf_kmeans_step_f32(const float* points, int ldp, long long N, in
   hipStream_t st = (hipStream_t)stream;
   KmParams p{};
   p.pts = points; p.ctr = centers; p.labels = labels; p.dist = nullptr; p.state = state;
-  p.sums = (u64*)workspace;
-  p.counts = (unsigned*)((char*)workspace + km_align((size_t)K * 16));
-  p.partials = (double*)((char*)workspace + km_acc_bytes(K));
+  km_carve(workspace, N, K, p);
   p.N = (long)N; p.ldp = ldp; p.ldc = ldc; p.K = K; p.ntiles = skf_cdiv((long)N, KM_TILE);
   p.scale = __builtin_ldexpf(1.f, scale_exp);
   // the same three commands every iteration, converged or not (a stopped fit's kernels return at once; the zeroed accumulators are
   // then never read)
-  SKF_HIP(hipMemsetAsync(workspace, 0, km_acc_bytes(K), st));
+  SKF_HIP(hipMemsetAsync(workspace, 0, (size_t)((char*)p.partials - (char*)workspace), st));
   const int rc2 = km_launch_assign<true>(p, st);
   if (rc2 != SKF_OK) return rc2;
   hipLaunchKernelGGL(kmeans_update_kernel, dim3(1), dim3(KM_THREADS), 0, st, centers, ldc, K, p.sums, p.counts, p.partials, p.ntiles,

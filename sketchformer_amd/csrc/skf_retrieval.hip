@@ -341,14 +341,20 @@ KnnSplit knn_split(int Q, int G) {
   return r;
 }
 bool knn_sizes_ok(int Q, int G, int k) { return Q >= 1 && G >= 1 && k >= 1 && k <= KNN_MAXK && k <= G; }
-size_t knn_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// the workspace of skf_knn_topk_f32: query norms, gallery norms, then the partial lists, which end it without rounding; -> its size
+size_t knn_carve(void* ws, int Q, int G, int k, int S, KnnParams& p) {
+  SkfWsCarver c(ws);
+  p.qn = c.take<float>(Q); p.gn = c.take<float>(G); p.part = c.take<u64>(0);
+  return c.used + (size_t)Q * S * k * 8;
+}
 
 }  // namespace
 
 extern "C" size_t skf_knn_workspace_bytes(int Q, int G, int k) {
   if (!knn_sizes_ok(Q, G, k)) return 0;
   const KnnSplit sp = knn_split(Q, G);
-  return knn_align((size_t)Q * 4) + knn_align((size_t)G * 4) + (size_t)Q * sp.S * k * 8;
+  KnnParams p;
+  return knn_carve(nullptr, Q, G, k, sp.S, p);
 }
 
 extern "C" int skf_knn_topk_f32(const float* queries, int ldq, int Q, const float* gallery, int ldg, int G, int d, int k,
@@ -366,10 +372,7 @@ extern "C" int skf_knn_topk_f32(const float* queries, int ldq, int Q, const floa
   const KnnSplit sp = knn_split(Q, G);
   KnnParams p;
   p.q = queries; p.g = gallery; p.excl = exclude;
-  float* qn = (float*)workspace;
-  float* gn = (float*)((char*)workspace + knn_align((size_t)Q * 4));
-  p.qn = qn; p.gn = gn;
-  p.part = (u64*)((char*)workspace + knn_align((size_t)Q * 4) + knn_align((size_t)G * 4));
+  knn_carve(workspace, Q, G, k, sp.S, p);
   p.ldq = ldq; p.ldg = ldg; p.Q = Q; p.G = G; p.d = d; p.k = k; p.S = sp.S; p.rows_per_split = sp.rows_per_split; p.nqt = sp.nqt;
   static SkfOncePerDevice attr;
   if (attr.needed()) {
@@ -377,7 +380,7 @@ extern "C" int skf_knn_topk_f32(const float* queries, int ldq, int Q, const floa
     attr.mark();
   }
   const long nrows = (long)Q + G;
-  hipLaunchKernelGGL(knn_norms_kernel, dim3(skf_cdiv(nrows, KNN_THREADS / 64)), dim3(KNN_THREADS), 0, st, queries, ldq, Q, gallery, ldg, G, d, qn, gn);
+  hipLaunchKernelGGL(knn_norms_kernel, dim3(skf_cdiv(nrows, KNN_THREADS / 64)), dim3(KNN_THREADS), 0, st, queries, ldq, Q, gallery, ldg, G, d, (float*)p.qn, (float*)p.gn);
   SKF_LAUNCH_CHECK();
   {
     SkfProfScope ps_(st, "knn_partial<64x128,f32>", 2.0 * Q * G * d, 4.0 * ((double)sp.nqt * G * d + (double)Q * d) + 8.0 * Q * sp.S * k);

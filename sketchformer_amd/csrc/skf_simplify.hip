@@ -20,7 +20,7 @@
 //     one lane walks the sketch, the other lanes wait.
 // A polyline of up to SKF_RDP_LDS_POINTS points lives in LDS (points, marks, the pass-A indices: 13 bytes a point); a longer one
 // runs the same code on the workspace.  Lanes of a wave exchange data through memory between the passes: wave_fence().
-#include "skf_common.h"
+#include "skf_ragged.h"
 #include <float.h>
 #include <limits.h>
 
@@ -31,7 +31,6 @@ namespace {
 constexpr int RDP_WAVES = 4;              // polylines per workgroup, one wave each; 4 x 13 x 512 B = 26 KiB of LDS
 constexpr int RDP_THREADS = 64 * RDP_WAVES;
 constexpr int RDP_LDS = SKF_RDP_LDS_POINTS;
-constexpr int OFFS_THREADS = 1024;        // the block width of the offsets scan: N counts go through in tiles of this many
 
 // What one lane wrote, every lane of the wave may read behind this.  Writer and readers are lanes of ONE wave, hence of one
 // workgroup on one CU: a workgroup-scope fence orders the wave's earlier stores - to LDS and, in the workspace form, to global
@@ -40,14 +39,6 @@ constexpr int OFFS_THREADS = 1024;        // the block width of the offsets scan
 __device__ __forceinline__ void wave_fence() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   __builtin_amdgcn_wave_barrier();
-}
-
-// the rows [beg, beg + n) that item s owns, whatever the offsets hold
-__device__ __forceinline__ void rdp_range(const long long* offsets, long long s, long long P, long long& beg, int& n) {
-  const long long a0 = offsets[s], a1 = offsets[s + 1];
-  beg = a0 < 0 ? 0 : (a0 > P ? P : a0);
-  const long long end = a1 < beg ? beg : (a1 > P ? P : a1);
-  n = (int)(end - beg);                                                        // P < 2^31
 }
 
 // The level loop over one polyline of n points: xy[i * ld], xy[i * ld + 1]; mark[i]: 0 undecided, 1 kept, 2 kept and the segment
@@ -141,7 +132,7 @@ __global__ __launch_bounds__(RDP_THREADS) void rdp_keep_kernel(RdpParams q) {
   if (s >= q.S) return;                                                        // (no workgroup barrier anywhere below)
   long long beg;
   int n;
-  rdp_range(q.offsets, s, q.P, beg, n);
+  skf_ragged_range(q.offsets, s, q.P, beg, n);
   if (n == 0) return;
   const float* src = q.xy + (size_t)beg * q.ldp;
   unsigned char* keep = q.keep + (size_t)beg;
@@ -193,7 +184,7 @@ __global__ __launch_bounds__(RDP_THREADS) void simplify_mark_kernel(SimplifyPara
   if (s >= q.N) return;                                                        // (no workgroup barrier anywhere below)
   long long beg;
   int n;
-  rdp_range(q.offsets, s, q.P, beg, n);
+  skf_ragged_range(q.offsets, s, q.P, beg, n);
   if (n == 0) {
     if (lane == 0) q.counts[s] = 0;
     return;
@@ -248,34 +239,7 @@ __global__ __launch_bounds__(RDP_THREADS) void simplify_mark_kernel(SimplifyPara
   if (lane == 0) q.counts[s] = kept;
 }
 
-// Launch 2.  out_offsets[0] = 0, out_offsets[i + 1] = counts[0] + .. + counts[i]: the tiled scan of skf_augment.hip.  One block
-// walks the counts in tiles of OFFS_THREADS with a carry: a shuffle scan inside every wave, the waves' totals through LDS.
-__global__ __launch_bounds__(OFFS_THREADS) void simplify_offsets_kernel(const int* __restrict__ counts, int N,
-                                                                         long long* __restrict__ out_offsets) {
-  __shared__ long long wave_total[OFFS_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long carry = 0;
-  for (long long base = 0; base < N; base += OFFS_THREADS) {                   // (the trip count is the same for every thread)
-    const long long i = base + threadIdx.x;
-    long long v = i < N ? (long long)counts[i] : 0;
-    for (int d = 1; d < 64; d <<= 1) {
-      const long long up = __shfl_up(v, d, 64);
-      if (lane >= d) v += up;
-    }
-    if (lane == 63) wave_total[wave] = v;
-    __syncthreads();
-    long long before = 0, total = 0;
-    for (int w = 0; w < OFFS_THREADS / 64; ++w) {
-      const long long t = wave_total[w];
-      if (w < wave) before += t;
-      total += t;
-    }
-    if (i < N) out_offsets[i + 1] = carry + before + v;
-    carry += total;
-    __syncthreads();                                                           // wave_total is rewritten by the next tile
-  }
-  if (threadIdx.x == 0) out_offsets[0] = 0;
-}
+// Launch 2 is the shared counts -> offsets scan (skf_ragged.hip).
 
 // Launch 3.  Per sketch: a kept row goes to out_offsets[s] + its rank among the kept rows, as (A - A_prev, pen): one fp32
 // subtraction per coordinate, A_prev the position of the kept row before it in the sketch, (0, 0) for the first.
@@ -285,7 +249,7 @@ __global__ __launch_bounds__(RDP_THREADS) void simplify_write_kernel(SimplifyPar
   if (s >= q.N) return;
   long long beg;
   int n;
-  rdp_range(q.offsets, s, q.P, beg, n);
+  skf_ragged_range(q.offsets, s, q.P, beg, n);
   if (n == 0) return;
   const float* rows = q.flat + 3 * (size_t)beg;
   const unsigned char* mark = q.mark + (size_t)beg;
@@ -313,7 +277,17 @@ __global__ __launch_bounds__(RDP_THREADS) void simplify_write_kernel(SimplifyPar
   }
 }
 
-constexpr size_t rdp_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// the workspaces of skf_rdp_f32 and skf_stroke3_simplify; each returns its size
+size_t rdp_carve(void* ws, long long P, RdpParams& q) {
+  SkfWsCarver c(ws);
+  q.mark = c.take<unsigned char>(P); q.rgt = c.take<int>(P);
+  return c.used;
+}
+size_t simplify_carve(void* ws, long long P, int N, SimplifyParams& q) {
+  SkfWsCarver c(ws);
+  q.counts = c.take<int>(N); q.mark = c.take<unsigned char>(P); q.pos = c.take<float>(2 * (size_t)P); q.rgt = c.take<int>(P);
+  return c.used;
+}
 
 bool rdp_epsilon_ok(double e) { return e >= 0.0 && e <= DBL_MAX; }             // (false for a NaN)
 
@@ -321,24 +295,19 @@ bool rdp_epsilon_ok(double e) { return e >= 0.0 && e <= DBL_MAX; }             /
 
 extern "C" size_t skf_rdp_workspace_bytes(long long P) {
   if (P < 1 || P >= (1ll << 31)) return 0;
-  return rdp_align((size_t)P) + rdp_align((size_t)P * sizeof(int));
+  RdpParams q;
+  return rdp_carve(nullptr, P, q);
 }
 
 extern "C" int skf_rdp_f32(const float* xy, int ldp, long long P, const long long* stroke_offsets, int S, double epsilon,
                            unsigned char* keep, void* workspace, size_t workspace_bytes, skf_stream_t stream) {
-  SKF_CHECK_ARG(xy && stroke_offsets && keep && workspace, "null pointer");
-  SKF_CHECK_ARG(S >= 1, "S must be at least 1");
-  SKF_CHECK_ARG(P >= 1 && P < (1ll << 31), "P must be in [1, 2^31)");
+  SKF_RAGGED_CHECK_ARGS(xy, P, stroke_offsets, S, workspace, workspace_bytes, skf_rdp_workspace_bytes(P));
+  SKF_CHECK_ARG(keep, "null pointer");
   SKF_CHECK_ARG(ldp >= 2, "ldp must be at least 2");
   SKF_CHECK_ARG(rdp_epsilon_ok(epsilon), "epsilon must be finite and not negative");
-  SKF_CHECK_ARG(((uintptr_t)xy & 3) == 0 && ((uintptr_t)stroke_offsets & 7) == 0 && ((uintptr_t)workspace & 15) == 0,
-                "xy and stroke_offsets must be aligned to their element, the workspace to 16 bytes");
-  SKF_CHECK_ARG(workspace_bytes >= skf_rdp_workspace_bytes(P), "workspace too small");
   RdpParams q;
   q.xy = xy; q.ldp = ldp; q.P = P; q.offsets = stroke_offsets; q.S = S; q.eps2 = epsilon * epsilon; q.keep = keep;
-  char* ws = (char*)workspace;
-  q.mark = (unsigned char*)ws;
-  q.rgt = (int*)(ws + rdp_align((size_t)P));
+  rdp_carve(workspace, P, q);
   hipLaunchKernelGGL(rdp_keep_kernel, dim3(skf_cdiv(S, RDP_WAVES)), dim3(RDP_THREADS), 0, (hipStream_t)stream, q);
   SKF_LAUNCH_CHECK();
   return SKF_OK;
@@ -346,37 +315,26 @@ extern "C" int skf_rdp_f32(const float* xy, int ldp, long long P, const long lon
 
 extern "C" size_t skf_stroke3_simplify_workspace_bytes(long long P, int N) {
   if (P < 1 || P >= (1ll << 31) || N < 1) return 0;
-  return rdp_align((size_t)N * sizeof(int)) + rdp_align((size_t)P) + rdp_align((size_t)P * 2 * sizeof(float)) +
-         rdp_align((size_t)P * sizeof(int));
+  SimplifyParams q;
+  return simplify_carve(nullptr, P, N, q);
 }
 
 extern "C" int skf_stroke3_simplify(const float* flat, long long P, const long long* offsets, int N, double epsilon, unsigned flags,
                                     float* out_flat, long long* out_offsets, void* workspace, size_t workspace_bytes,
                                     skf_stream_t stream) {
-  SKF_CHECK_ARG(flat && offsets && out_flat && out_offsets && workspace, "null pointer");
-  SKF_CHECK_ARG(N >= 1, "N must be at least 1");
-  SKF_CHECK_ARG(P >= 1 && P < (1ll << 31), "P must be in [1, 2^31)");
+  SKF_RAGGED_CHECK_ARGS(flat, P, offsets, N, workspace, workspace_bytes, skf_stroke3_simplify_workspace_bytes(P, N));
+  SKF_CHECK_ARG(out_flat && out_offsets, "null pointer");
   SKF_CHECK_ARG(rdp_epsilon_ok(epsilon), "epsilon must be finite and not negative");
   SKF_CHECK_ARG(flags == 0, "unknown flag");
-  SKF_CHECK_ARG(((uintptr_t)flat & 3) == 0 && ((uintptr_t)offsets & 7) == 0 && ((uintptr_t)out_flat & 3) == 0 &&
-                    ((uintptr_t)out_offsets & 7) == 0 && ((uintptr_t)workspace & 15) == 0,
-                "flat, offsets, out_flat, out_offsets must be aligned to their element, the workspace to 16 bytes");
-  SKF_CHECK_ARG(workspace_bytes >= skf_stroke3_simplify_workspace_bytes(P, N), "workspace too small");
+  SKF_CHECK_ARG(((uintptr_t)out_flat & 3) == 0 && ((uintptr_t)out_offsets & 7) == 0, "out_flat, out_offsets must be aligned to their element");
   hipStream_t st = (hipStream_t)stream;
   SimplifyParams q;
   q.flat = flat; q.offsets = offsets; q.P = P; q.N = N; q.eps2 = epsilon * epsilon; q.out_flat = out_flat; q.out_offsets = out_offsets;
-  char* ws = (char*)workspace;
-  q.counts = (int*)ws;
-  ws += rdp_align((size_t)N * sizeof(int));
-  q.mark = (unsigned char*)ws;
-  ws += rdp_align((size_t)P);
-  q.pos = (float*)ws;
-  ws += rdp_align((size_t)P * 2 * sizeof(float));
-  q.rgt = (int*)ws;
+  simplify_carve(workspace, P, N, q);
 
   hipLaunchKernelGGL(simplify_mark_kernel, dim3(skf_cdiv(N, RDP_WAVES)), dim3(RDP_THREADS), 0, st, q);
   SKF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(simplify_offsets_kernel, dim3(1), dim3(OFFS_THREADS), 0, st, (const int*)q.counts, N, out_offsets);
+  skf_counts_to_offsets_launch(q.counts, N, out_offsets, st);
   SKF_LAUNCH_CHECK();
   hipLaunchKernelGGL(simplify_write_kernel, dim3(skf_cdiv(N, RDP_WAVES)), dim3(RDP_THREADS), 0, st, q);
   SKF_LAUNCH_CHECK();

@@ -16,7 +16,7 @@
 // Launches of skf_sketch_encode: fill (rows := PAD, or the stroke-5 end row) -> scan (per sketch: bounds, divisor, normalised
 // offsets, grid ids, every point's place in its row, SOS / EOS) -> [DICT: nearest centre] -> pack (per point: one or two stores).
 // No atomics; every output element has one writer per launch and the launches are ordered by the stream.
-#include "skf_common.h"
+#include "skf_ragged.h"
 
 #pragma clang fp contract(off)
 
@@ -27,7 +27,6 @@ constexpr int NC_THREADS = 256;
 constexpr int NC_PTS = 4;                 // points per thread: one LDS read of a centre serves four distances
 constexpr int SCAN_THREADS = 64;          // one wave per workgroup: 70k sketches are ~1100 waves, spread over every CU
 constexpr int PACK_THREADS = 256;
-constexpr float TOK_LIMIT = 1000.0f;
 
 // ---------------------------------------------------------------- nearest centre, float64
 // d = (x - cx)^2 + (y - cy)^2 with x, y widened to fp64 and each of the five operations rounded on its own; the lowest index wins
@@ -81,8 +80,6 @@ struct EncodeParams {
   long long* dst;               // workspace: per point, -1 = not stored, else 2 * (element index of its token / row) + (SEP follows)
 };
 
-__device__ __forceinline__ float tok_clamp(float v, int clamp) { return clamp ? fminf(fmaxf(v, -TOK_LIMIT), TOK_LIMIT) : v; }
-
 __global__ __launch_bounds__(PACK_THREADS) void encode_fill_kernel(void* out, long long n, int stroke5) {
   const long long stride = (long long)gridDim.x * PACK_THREADS;
   for (long long i = (long long)blockIdx.x * PACK_THREADS + threadIdx.x; i < n; i += stride) {
@@ -97,20 +94,21 @@ __global__ __launch_bounds__(PACK_THREADS) void encode_fill_kernel(void* out, lo
 __global__ __launch_bounds__(SCAN_THREADS) void encode_scan_kernel(EncodeParams q) {
   const long long s = (long long)blockIdx.x * SCAN_THREADS + threadIdx.x;
   if (s >= q.N) return;
-  const long long a0 = q.offsets[s], a1 = q.offsets[s + 1];
-  const long long beg = a0 < 0 ? 0 : (a0 > q.P ? q.P : a0);                  // stay inside flat whatever the offsets hold
-  const long long end = a1 < beg ? beg : (a1 > q.P ? q.P : a1);
-  const int n = (int)(end - beg);                                              // P < 2^31
+  long long beg_;
+  int n_;
+  skf_ragged_range(q.offsets, s, q.P, beg_, n_);
+  const long long beg = beg_;                // (const copies: with the reference arguments themselves as the loop bounds below,
+  const int n = n_;                          //  the compiler numbers this kernel's registers differently)
   const float* rows = q.flat + 3 * (size_t)beg;
 
   double cx = 0.0, cy = 0.0, min_x = 0.0, max_x = 0.0, min_y = 0.0, max_y = 0.0;
   int last = -1, nlift = 0;
   for (int t = 0; t < n; ++t) {
-    cx = cx + (double)tok_clamp(rows[3 * t], q.clamp);
-    cy = cy + (double)tok_clamp(rows[3 * t + 1], q.clamp);
+    cx = cx + (double)skf_sketch_clamp(rows[3 * t], q.clamp);
+    cy = cy + (double)skf_sketch_clamp(rows[3 * t + 1], q.clamp);
     min_x = fmin(min_x, cx); max_x = fmax(max_x, cx);
     min_y = fmin(min_y, cy); max_y = fmax(max_y, cy);
-    if (tok_clamp(rows[3 * t + 2], q.clamp) == 1.0f) { last = t; ++nlift; }
+    if (skf_sketch_clamp(rows[3 * t + 2], q.clamp) == 1.0f) { last = t; ++nlift; }
   }
   const float div = (float)fmax(fmax(max_x - min_x, max_y - min_y), 1.0);
   if (q.scale) q.scale[s] = div;
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void encode_scan_kernel(EncodeParams 
   if (q.mode == SKF_ENCODE_STROKE5) {
     for (int t = 0; t < n; ++t) {
       const long long p = beg + t;
-      q.xy[p] = make_float2(tok_clamp(rows[3 * t], q.clamp) / div, tok_clamp(rows[3 * t + 1], q.clamp) / div);
+      q.xy[p] = make_float2(skf_sketch_clamp(rows[3 * t], q.clamp) / div, skf_sketch_clamp(rows[3 * t + 1], q.clamp) / div);
       q.dst[p] = t < L ? 2 * (s * L + t) : -1;
     }
     return;
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void encode_scan_kernel(EncodeParams 
   long long pos = 1;
   for (int t = 0; t < n; ++t) {
     const long long p = beg + t;
-    const float X = tok_clamp(rows[3 * t], q.clamp) / div, Y = tok_clamp(rows[3 * t + 1], q.clamp) / div;
+    const float X = skf_sketch_clamp(rows[3 * t], q.clamp) / div, Y = skf_sketch_clamp(rows[3 * t + 1], q.clamp) / div;
     if (grid) {
       gx = gx + X; gy = gy + Y;
       long long ix = (long long)((gx + 1.0f) * half), iy = (long long)((gy + 1.0f) * half);
@@ -146,7 +144,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void encode_scan_kernel(EncodeParams 
       q.xy[p] = make_float2(X, Y);
     }
     if (t >= stop) { q.dst[p] = -1; continue; }
-    const bool sep = grid && nlift == 0 ? t == n - 1 : tok_clamp(rows[3 * t + 2], q.clamp) == 1.0f;
+    const bool sep = grid && nlift == 0 ? t == n - 1 : skf_sketch_clamp(rows[3 * t + 2], q.clamp) == 1.0f;
     q.dst[p] = pos < L ? 2 * (s * L + pos) + (sep && pos + 1 < L ? 1 : 0) : -1;
     pos += sep ? 2 : 1;
   }
@@ -163,7 +161,7 @@ __global__ __launch_bounds__(PACK_THREADS) void encode_pack_kernel(EncodeParams 
   if (d < 0 || e + (d & 1) >= (long long)q.N * q.L) return;
   if (q.mode == SKF_ENCODE_STROKE5) {
     const float2 v = q.xy[p];
-    const float pen = tok_clamp(q.flat[3 * (size_t)p + 2], q.clamp);
+    const float pen = skf_sketch_clamp(q.flat[3 * (size_t)p + 2], q.clamp);
     float* r = (float*)q.out + 5 * (size_t)e;
     r[0] = v.x; r[1] = v.y; r[2] = 1.0f - pen; r[3] = pen;
     r[4] = (e % q.L == q.L - 1) ? 1.0f : 0.0f;                               // the last row always carries the end flag
@@ -174,7 +172,12 @@ __global__ __launch_bounds__(PACK_THREADS) void encode_pack_kernel(EncodeParams 
   if (d & 1) o[1] = (q.mode == SKF_ENCODE_GRID ? (long long)q.K * q.K : (long long)q.K) + 1;
 }
 
-constexpr size_t tok_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// the workspace of skf_sketch_encode; returns its size
+size_t encode_carve(void* ws, long long P, EncodeParams& q) {
+  SkfWsCarver c(ws);
+  q.xy = c.take<float2>(P); q.ids = c.take<long long>(P); q.dst = c.take<long long>(P);
+  return c.used;
+}
 
 int nearest_center_launch(const float* points, int ldp, long long P, const double* centers, int K, int* labels, hipStream_t st) {
   const long long blocks = (P + NC_THREADS * NC_PTS - 1) / (NC_THREADS * NC_PTS);
@@ -200,15 +203,15 @@ extern "C" int skf_nearest_center_f64(const float* points, int ldp, long long P,
 
 extern "C" size_t skf_sketch_encode_workspace_bytes(long long P, int N) {
   if (P < 1 || P >= (1ll << 31) || N < 1) return 0;
-  return tok_align((size_t)P * sizeof(float2)) + 2 * tok_align((size_t)P * sizeof(long long));
+  EncodeParams q;
+  return encode_carve(nullptr, P, q);
 }
 
 extern "C" int skf_sketch_encode(const float* flat, long long P, const long long* offsets, int N, int mode, const double* centers,
                                  int K, int L, unsigned flags, void* out, float* scale, void* workspace, size_t workspace_bytes,
                                  skf_stream_t stream) {
-  SKF_CHECK_ARG(flat && offsets && out && workspace, "null pointer");
-  SKF_CHECK_ARG(N >= 1, "N must be at least 1");
-  SKF_CHECK_ARG(P >= 1 && P < (1ll << 31), "P must be in [1, 2^31)");
+  SKF_RAGGED_CHECK_ARGS(flat, P, offsets, N, workspace, workspace_bytes, skf_sketch_encode_workspace_bytes(P, N));
+  SKF_CHECK_ARG(out, "null pointer");
   SKF_CHECK_ARG(L >= 2, "L must be at least 2");
   SKF_CHECK_ARG(mode == SKF_ENCODE_DICT || mode == SKF_ENCODE_GRID || mode == SKF_ENCODE_STROKE5, "mode must be DICT, GRID or STROKE5");
   SKF_CHECK_ARG((flags & ~(unsigned)SKF_ENCODE_CLAMP) == 0, "unknown flag");
@@ -218,18 +221,12 @@ extern "C" int skf_sketch_encode(const float* flat, long long P, const long long
   } else if (mode == SKF_ENCODE_GRID) {
     SKF_CHECK_ARG(K >= 2 && K <= 32768 && K % 2 == 0, "the grid resolution must be even, in [2, 32768]");
   }
-  SKF_CHECK_ARG(((uintptr_t)flat & 3) == 0 && ((uintptr_t)offsets & 7) == 0 && ((uintptr_t)out & 7) == 0 &&
-                    ((uintptr_t)scale & 3) == 0 && ((uintptr_t)workspace & 15) == 0,
-                "flat, offsets, out, scale must be aligned to their element, the workspace to 16 bytes");
-  SKF_CHECK_ARG(workspace_bytes >= skf_sketch_encode_workspace_bytes(P, N), "workspace too small");
+  SKF_CHECK_ARG(((uintptr_t)out & 7) == 0 && ((uintptr_t)scale & 3) == 0, "out, scale must be aligned to their element");
   hipStream_t st = (hipStream_t)stream;
   EncodeParams q;
   q.flat = flat; q.offsets = offsets; q.P = P; q.N = N; q.mode = mode; q.K = K; q.L = L; q.clamp = (flags & SKF_ENCODE_CLAMP) ? 1 : 0;
   q.out = out; q.scale = scale;
-  char* ws = (char*)workspace;
-  q.xy = (float2*)ws;
-  q.ids = (long long*)(ws + tok_align((size_t)P * sizeof(float2)));
-  q.dst = (long long*)(ws + tok_align((size_t)P * sizeof(float2)) + tok_align((size_t)P * sizeof(long long)));
+  encode_carve(workspace, P, q);
 
   const long long elems = (long long)N * L * (mode == SKF_ENCODE_STROKE5 ? 5 : 1);
   const long long fill_blocks = (elems + PACK_THREADS - 1) / PACK_THREADS;

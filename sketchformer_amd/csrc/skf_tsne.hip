@@ -24,22 +24,7 @@ constexpr int TS_PAIR_WAVES = TS_PAIR_THREADS / 64;
 constexpr int TS_PAIR_MAXGRID = 512;              // 2 resident workgroups per CU at N = 8192 (64 KB of LDS each)
 constexpr int TS_TILE = 64, TS_KC = 32;           // distance tiles
 
-size_t ts_align(size_t n) { return (n + 255) & ~(size_t)255; }
 bool ts_n_ok(long long N) { return N >= 3 && N <= TS_MAXN; }
-
-__device__ __forceinline__ double ts_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// every thread gets the sum; butterfly, then waves 0..3
-__device__ __forceinline__ double ts_block_sum(double v, double* sRed) {
-  v = ts_wave_sum(v);
-  __syncthreads();                                // sRed of the previous use is read
-  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
-}
 
 // ---------------------------------------------------------------- affinities
 __global__ __launch_bounds__(256) void tsne_dist_kernel(const float* __restrict__ x, int ldx, int N, int d, float* __restrict__ D, int ldp) {
@@ -139,8 +124,8 @@ __global__ __launch_bounds__(TS_THREADS) void tsne_search_kernel(const float* __
         t += e * p;
       }
     }
-    s = ts_block_sum(s, sRed) + zeros;
-    t = ts_block_sum(t, sRed2);
+    s = block_sum(s, sRed) + zeros;
+    t = block_sum(t, sRed2);
     double diff;                                   // H - log(perplexity), in the form that is well conditioned where the row stands
     if (s > 0.75 * n) {
       // near uniform: H - log n = -(1/n) sum_j f(n w_j - 1), n w_j - 1 = (expm1(-beta e_j) - mean) / (1 + mean); no cancellation
@@ -149,13 +134,13 @@ __global__ __launch_bounds__(TS_THREADS) void tsne_search_kernel(const float* __
         const float v = ts_row[j];
         if (v > 0.f) ms += expm1(-beta * ((double)v - m));
       }
-      const double mean = ts_block_sum(ms, sRed) / n, onem = 1.0 + mean;
+      const double mean = block_sum(ms, sRed) / n, onem = 1.0 + mean;
       double fs = 0.0;
       for (int j = tid; j < N; j += TS_THREADS) {
         const float v = ts_row[j];
         if (v > 0.f) fs += ts_f((expm1(-beta * ((double)v - m)) - mean) / onem);
       }
-      fs = ts_block_sum(fs, sRed2) + zeros * ts_f((0.0 - mean) / onem);
+      fs = block_sum(fs, sRed2) + zeros * ts_f((0.0 - mean) / onem);
       diff = log_n_over_perp - fs / n;
     } else {
       diff = log(s) + beta * t / s - log_perp;
@@ -244,7 +229,7 @@ __global__ __launch_bounds__(TS_PAIR_THREADS) void tsne_pair_kernel(const float*
 __device__ __forceinline__ double ts_total_z(const float* __restrict__ zrow, int N, double* sRed) {
   double z = 0.0;
   for (int i = threadIdx.x; i < N; i += TS_THREADS) z += (double)zrow[i];
-  return ts_block_sum(z, sRed);
+  return block_sum(z, sRed);
 }
 
 __global__ __launch_bounds__(TS_THREADS) void tsne_update_kernel(int N, const float* __restrict__ zrow, const float* __restrict__ arow,
@@ -290,7 +275,7 @@ __global__ __launch_bounds__(TS_PAIR_THREADS) void tsne_klrow_kernel(const float
         ps += (double)p;
       }
     });
-    z = wave_sum(z); k = ts_wave_sum(k); ps = ts_wave_sum(ps);
+    z = wave_sum(z); k = wave_sum(k); ps = wave_sum(ps);
     if (lane == 0) { zrow[i] = z; krow[i] = k; prow_sum[i] = ps; }
   }
 }
@@ -302,17 +287,18 @@ __global__ __launch_bounds__(TS_THREADS) void tsne_klsum_kernel(int N, const flo
   const double Z = ts_total_z(zrow, N, sRed);
   double k = 0.0, s = 0.0;
   for (int i = threadIdx.x; i < N; i += TS_THREADS) { k += krow[i]; s += prow_sum[i]; }
-  k = ts_block_sum(k, sRed);
-  s = ts_block_sum(s, sRed);
+  k = block_sum(k, sRed);
+  s = block_sum(s, sRed);
   if (threadIdx.x == 0) *out = k + log(Z) * s;
 }
 
 // ---------------------------------------------------------------- host
-struct TsWs { char* a; char* b; char* c; };          // three arrays of ts_align(8 N) bytes
+struct TsWs { char* a; char* b; char* c; size_t total; };          // three arrays of 8 N bytes
 TsWs ts_carve(void* ws, int N) {
-  char* p = (char*)ws;
-  const size_t n = ts_align((size_t)N * 8);
-  return TsWs{p, p + n, p + 2 * n};
+  SkfWsCarver k(ws);
+  TsWs w{k.take<char>((size_t)N * 8), k.take<char>((size_t)N * 8), k.take<char>((size_t)N * 8), 0};     // (braces: in this order)
+  w.total = k.used;
+  return w;
 }
 
 int ts_pair_grid(int N) {
@@ -332,7 +318,7 @@ int ts_pair_grid(int N) {
 
 extern "C" size_t skf_tsne_workspace_bytes(int N) {
   if (!ts_n_ok(N)) return 0;
-  return 3 * ts_align((size_t)N * 8);
+  return ts_carve(nullptr, N).total;
 }
 
 extern "C" int skf_tsne_affinities_f32(const float* x, int ldx, int N, int d, double perplexity, float* P, int ldp, double* beta,

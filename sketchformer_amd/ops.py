@@ -39,6 +39,48 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _workspace_for(fn, device, *sizes):
+    """The workspace of one call: ask the library's `fn` (a *_workspace_bytes) for these sizes and allocate that -> (ws, nbytes)."""
+    nbytes = getattr(_lib.load(), fn)(*sizes)
+    return _ws(nbytes, device), nbytes
+
+
+def _ragged_offsets(offsets, rows, who, names=("offsets", "N", "flat", "sketch"), limit=True):
+    """`offsets` (N + 1) int64 beside the (P, .) tensor `rows` -> (P, N).  names: the offsets, their count, the rows and one item in
+    the texts; limit=False leaves P < 2^31 to the library (SkfError)."""
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.device != rows.device:
+        raise TypeError("%s must be a contiguous int64 tensor of shape (%s + 1,) on the device of %s" % names[:3])
+    P, N = rows.shape[0], offsets.shape[0] - 1
+    if N < 1 or P < 1:
+        raise ValueError("%s needs at least one %s and one point" % (who, names[3]))
+    if limit and P >= 1 << 31:
+        raise ValueError("%s takes fewer than 2^31 points" % who)
+    return P, N
+
+
+def _ragged(flat, offsets, who, limit=True):
+    """The checks of a ragged batch of sketches, flat (P, 3) float32 + offsets (N + 1) int64, for the operation `who` -> (P, N)."""
+    _p(flat); _p(offsets)                                        # CPU tensors: SkfError before anything is allocated
+    if flat.dtype != torch.float32 or flat.dim() != 2 or flat.shape[1] != 3 or not flat.is_contiguous():
+        raise TypeError("flat must be a contiguous float32 tensor of shape (P, 3)")
+    return _ragged_offsets(offsets, flat, who, limit=limit)
+
+
+def _compacted(out_flat, out_offsets):
+    """-> (the P' = out_offsets[N] rows in use, the offsets); reading P' is one small device-to-host copy that waits for the stream."""
+    kept = int(out_offsets[-1].item())
+    return out_flat[:kept], out_offsets
+
+
+def _centers(centers, beside=None):
+    """The dictionary: centers (K, 2) float64, contiguous and, given beside = (tensor, its name), on that tensor's device -> K."""
+    _p(centers)
+    if centers.dtype != torch.float64 or centers.dim() != 2 or centers.shape[1] != 2 or not centers.is_contiguous() \
+            or (beside is not None and centers.device != beside[0].device):
+        raise TypeError("centers must be a contiguous float64 tensor of shape (K, 2)" + (" on the device of %s" % beside[1] if beside else ""))
+    return centers.shape[0]
+
+
 def new_step_state(device, iterations=0):
     """Device-resident per-step scalars {int64 iterations; f32 lr, alpha; u32 drop_key, pad}."""
     n = _lib.load().skf_step_state_bytes()
@@ -445,8 +487,7 @@ def layernorm_residual_bwd(dout, z, stats, gamma, rate=0.0, site=0, state=None):
     dy = torch.empty_like(dout) if rate > 0 else None
     dg = torch.empty(d, dtype=torch.float32, device=dout.device)
     db = torch.empty(d, dtype=torch.float32, device=dout.device)
-    wsb = _lib.load().skf_layernorm_bwd_workspace_bytes(rows, d)
-    ws = _ws(wsb, dout.device)
+    ws, wsb = _workspace_for("skf_layernorm_bwd_workspace_bytes", dout.device, rows, d)
     _lib.call("skf_layernorm_residual_bwd", _p(dout), _p(z), _p(stats), _p(gamma), _p(dz), _p(dy), _p(dg), _p(db), rows,
               d, rate, site, _p(state), _p(ws), wsb, _stream())
     return dz, (dy if dy is not None else dz), dg, db
@@ -668,8 +709,7 @@ def knn_topk(queries, gallery, k, exclude=None, metric='l2'):
         queries, gallery = row_normalize(queries), row_normalize(gallery)
     idx = torch.empty(Q, k, dtype=torch.int32, device=queries.device)
     dist = torch.empty(Q, k, dtype=torch.float32, device=queries.device)
-    wsb = _lib.load().skf_knn_workspace_bytes(Q, G, k)
-    ws = _ws(wsb, queries.device)
+    ws, _ = _workspace_for("skf_knn_workspace_bytes", queries.device, Q, G, k)
     _lib.call("skf_knn_topk_f32", _p(queries), queries.stride(0), Q, _p(gallery), gallery.stride(0), G, d, k, _p(exclude),
               _p(idx), _p(dist), _p(ws), ws.numel(), _stream())
     return idx, dist
@@ -962,11 +1002,9 @@ def nearest_center(points, centers):
     _p(points); _p(centers)                                      # CPU tensors: SkfError before anything is allocated
     if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 2 or points.stride(1) != 1:
         raise TypeError("points must be a float32 tensor of shape (P, 2) with a unit innermost stride")
-    if centers.dtype != torch.float64 or centers.dim() != 2 or centers.shape[1] != 2 or not centers.is_contiguous():
-        raise TypeError("centers must be a contiguous float64 tensor of shape (K, 2)")
+    P, K = points.shape[0], _centers(centers)
     if centers.device != points.device:
         raise ValueError("points and centers must be on one device")
-    P, K = points.shape[0], centers.shape[0]
     if P < 1 or not 1 <= K <= 4096:
         raise ValueError("nearest_center needs at least one point and 1 <= K <= 4096 centres")
     labels = torch.empty(P, dtype=torch.int32, device=points.device)
@@ -985,24 +1023,13 @@ def sketch_encode(flat, offsets, mode, max_seq_len, centers=None, resolution=Non
     first.  With return_scale also the divisor of every sketch, float32 (N,).  include/skf.h has the definition."""
     if mode not in ENCODE_MODES:
         raise ValueError("mode must be one of %s (got %r)" % (sorted(ENCODE_MODES), mode))
-    _p(flat); _p(offsets)                                        # CPU tensors: SkfError before anything is allocated
-    if flat.dtype != torch.float32 or flat.dim() != 2 or flat.shape[1] != 3 or not flat.is_contiguous():
-        raise TypeError("flat must be a contiguous float32 tensor of shape (P, 3)")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.device != flat.device:
-        raise TypeError("offsets must be a contiguous int64 tensor of shape (N + 1,) on the device of flat")
-    P, N, L, K = flat.shape[0], offsets.shape[0] - 1, int(max_seq_len), 0
-    if N < 1 or P < 1:
-        raise ValueError("sketch_encode needs at least one sketch and one point")
+    (P, N), L, K = _ragged(flat, offsets, "sketch_encode", limit=False), int(max_seq_len), 0
     if L < 2:
         raise ValueError("max_seq_len must be at least 2")
     if mode == 'dict':
         if centers is None:
             raise ValueError("mode 'dict' needs centers")
-        _p(centers)
-        if centers.dtype != torch.float64 or centers.dim() != 2 or centers.shape[1] != 2 or not centers.is_contiguous() \
-                or centers.device != flat.device:
-            raise TypeError("centers must be a contiguous float64 tensor of shape (K, 2) on the device of flat")
-        K = centers.shape[0]
+        K = _centers(centers, beside=(flat, "flat"))
         if not 1 <= K <= 4096:
             raise ValueError("the dictionary must hold 1 <= K <= 4096 centres")
     else:
@@ -1016,8 +1043,7 @@ def sketch_encode(flat, offsets, mode, max_seq_len, centers=None, resolution=Non
     dev = flat.device
     out = torch.empty((N, L, 5) if mode == 'stroke5' else (N, L), dtype=torch.float32 if mode == 'stroke5' else torch.int64, device=dev)
     scale = torch.empty(N, dtype=torch.float32, device=dev) if return_scale else None
-    nbytes = _lib.load().skf_sketch_encode_workspace_bytes(P, N)
-    ws = _ws(nbytes, dev)
+    ws, nbytes = _workspace_for("skf_sketch_encode_workspace_bytes", dev, P, N)
     _lib.call("skf_sketch_encode", _p(flat), P, _p(offsets), N, ENCODE_MODES[mode], _p(centers), K, L, 1 if clamp else 0, _p(out),
               _p(scale), _p(ws), nbytes, _stream())
     return (out, scale) if return_scale else out
@@ -1031,18 +1057,10 @@ def sketch_augment(flat, offsets, rnd, scale_factor, prob, clamp=True):
     first.  -> (out_flat (P', 3) float32, out_offsets (N + 1) int64): the augmented sketches back to back, ready for sketch_encode
     with clamp=False.  Reading P' = out_offsets[N] is one small device-to-host copy that waits for the current stream: sketch_encode
     needs offsets that cover its flat exactly, so the rows come back sliced to P' and never at their capacity P."""
-    _p(flat); _p(offsets); _p(rnd)                               # CPU tensors: SkfError before anything is allocated
-    if flat.dtype != torch.float32 or flat.dim() != 2 or flat.shape[1] != 3 or not flat.is_contiguous():
-        raise TypeError("flat must be a contiguous float32 tensor of shape (P, 3)")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.device != flat.device:
-        raise TypeError("offsets must be a contiguous int64 tensor of shape (N + 1,) on the device of flat")
-    P, N = flat.shape[0], offsets.shape[0] - 1
+    _p(rnd)                                                      # CPU tensors: SkfError before anything is allocated
+    P, N = _ragged(flat, offsets, "sketch_augment")
     if rnd.dtype != torch.float64 or rnd.dim() != 1 or not rnd.is_contiguous() or rnd.device != flat.device:
         raise TypeError("rnd must be a contiguous float64 tensor of shape (2 N + P,) on the device of flat")
-    if N < 1 or P < 1:
-        raise ValueError("sketch_augment needs at least one sketch and one point")
-    if P >= 1 << 31:
-        raise ValueError("sketch_augment takes fewer than 2^31 points")
     if rnd.shape[0] != 2 * N + P:
         raise ValueError("rnd must hold 2 N + P = %d draws (got %d)" % (2 * N + P, rnd.shape[0]))
     scale_factor, prob = float(scale_factor), float(prob)
@@ -1053,12 +1071,10 @@ def sketch_augment(flat, offsets, rnd, scale_factor, prob, clamp=True):
     dev = flat.device
     out_flat = torch.empty(P, 3, dtype=torch.float32, device=dev)
     out_offsets = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    nbytes = _lib.load().skf_sketch_augment_workspace_bytes(P, N)
-    ws = _ws(nbytes, dev)
+    ws, nbytes = _workspace_for("skf_sketch_augment_workspace_bytes", dev, P, N)
     _lib.call("skf_sketch_augment", _p(flat), P, _p(offsets), N, _p(rnd), scale_factor, prob, 1 if clamp else 0, _p(out_flat),
               _p(out_offsets), _p(ws), nbytes, _stream())
-    kept = int(out_offsets[N].item())
-    return out_flat[:kept], out_offsets
+    return _compacted(out_flat, out_offsets)
 
 
 RDP_LDS_POINTS = 512                                             # SKF_RDP_LDS_POINTS of include/skf.h
@@ -1079,23 +1095,15 @@ def rdp_keep(xy, stroke_offsets, epsilon):
     _p(xy); _p(stroke_offsets)                                   # CPU tensors: SkfError before anything is allocated
     if xy.dtype != torch.float32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.stride(1) != 1:
         raise TypeError("xy must be a float32 tensor of shape (P, 2) with a unit innermost stride")
-    if stroke_offsets.dtype != torch.int64 or stroke_offsets.dim() != 1 or not stroke_offsets.is_contiguous() \
-            or stroke_offsets.device != xy.device:
-        raise TypeError("stroke_offsets must be a contiguous int64 tensor of shape (S + 1,) on the device of xy")
-    P, S = xy.shape[0], stroke_offsets.shape[0] - 1
+    P, S = _ragged_offsets(stroke_offsets, xy, "rdp_keep", names=("stroke_offsets", "S", "xy", "polyline"))
     epsilon = _rdp_epsilon(epsilon)
-    if S < 1 or P < 1:
-        raise ValueError("rdp_keep needs at least one polyline and one point")
-    if P >= 1 << 31:
-        raise ValueError("rdp_keep takes fewer than 2^31 points")
     ldp = xy.stride(0) if P > 1 else 2                           # (the row stride of a single row is never used)
     if ldp < 2:                                                  # an expanded or overlapping view: rows the tensor does not own
         raise ValueError("the rows of xy must not overlap (row stride %d < 2)" % ldp)
     if ldp >= 1 << 31:
         raise ValueError("the row stride of xy must be below 2^31")
     keep = torch.empty(P, dtype=torch.uint8, device=xy.device)
-    nbytes = _lib.load().skf_rdp_workspace_bytes(P)
-    ws = _ws(nbytes, xy.device)
+    ws, nbytes = _workspace_for("skf_rdp_workspace_bytes", xy.device, P)
     _lib.call("skf_rdp_f32", _p(xy), ldp, P, _p(stroke_offsets), S, epsilon, _p(keep), _p(ws), nbytes, _stream())
     return keep
 
@@ -1106,25 +1114,14 @@ def stroke3_simplify(flat, offsets, epsilon):
     (N + 1) int64 as for sketch_encode.  -> (out_flat (P', 3) float32, out_offsets (N + 1) int64).  Stroke ends are always kept:
     pen values and the number of strokes do not change.  Reading P' = out_offsets[N] is one small device-to-host copy that waits
     for the current stream."""
-    _p(flat); _p(offsets)                                        # CPU tensors: SkfError before anything is allocated
-    if flat.dtype != torch.float32 or flat.dim() != 2 or flat.shape[1] != 3 or not flat.is_contiguous():
-        raise TypeError("flat must be a contiguous float32 tensor of shape (P, 3)")
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.device != flat.device:
-        raise TypeError("offsets must be a contiguous int64 tensor of shape (N + 1,) on the device of flat")
-    P, N = flat.shape[0], offsets.shape[0] - 1
+    P, N = _ragged(flat, offsets, "stroke3_simplify")
     epsilon = _rdp_epsilon(epsilon)
-    if N < 1 or P < 1:
-        raise ValueError("stroke3_simplify needs at least one sketch and one point")
-    if P >= 1 << 31:
-        raise ValueError("stroke3_simplify takes fewer than 2^31 points")
     dev = flat.device
     out_flat = torch.empty(P, 3, dtype=torch.float32, device=dev)
     out_offsets = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    nbytes = _lib.load().skf_stroke3_simplify_workspace_bytes(P, N)
-    ws = _ws(nbytes, dev)
+    ws, nbytes = _workspace_for("skf_stroke3_simplify_workspace_bytes", dev, P, N)
     _lib.call("skf_stroke3_simplify", _p(flat), P, _p(offsets), N, epsilon, 0, _p(out_flat), _p(out_offsets), _p(ws), nbytes, _stream())
-    kept = int(out_offsets[N].item())
-    return out_flat[:kept], out_offsets
+    return _compacted(out_flat, out_offsets)
 
 
 ALIGN_MAX_LEN = 512                                              # SKF_ALIGN_MAX_LEN of include/skf.h

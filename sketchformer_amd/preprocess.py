@@ -23,6 +23,12 @@ def pack_ragged(data):
     return np.ascontiguousarray(flat), offsets
 
 
+def _device(device):
+    """The device a call runs on: the current one unless the caller names one."""
+    import torch
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
 def device_path_supported(hps, tokenizer):
     """The conditions on the hparams / tokenizer under which DistributedStroke3DataLoader.preprocess takes its block path (and the
     device loader the device): no stroke shuffling, offsets not absolute, and continuous data or one of the two tokenizers."""
@@ -49,7 +55,7 @@ def encode_chunk(data, hps, tokenizer, clamp=True, device=None, stream=None, aug
         raise ValueError("offsets must run from 0 to the number of points without decreasing")
     import torch
     from . import ops
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = _device(device)
     side = torch.cuda.Stream(device=dev) if stream is None else stream
     L = int(hps["max_seq_len"])
     with torch.cuda.device(dev), torch.cuda.stream(side):

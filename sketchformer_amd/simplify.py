@@ -7,13 +7,7 @@ sketch holds one row (dx, dy, pen) per point, the first row's offset counted fro
 """
 import numpy as np
 
-from .preprocess import pack_ragged
-
-
-def _device(device):
-    import torch
-    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-
+from .preprocess import _device, pack_ragged
 
 EXACT_POSITIONS = 1 << 23      # integer sketches: below this, positions and the offsets between any two of them are exact in fp32
 

@@ -7,9 +7,8 @@ rule of include/skf.h as a plain loop, with three switches that make it wrong on
 import numpy as np
 
 from preprocess_reference import host_loader
+from simplify_reference import OFFSETS_SCAN_BLOCK       # noqa: F401  (the block width of the offsets scan both pipelines share)
 from sketchformer_amd import preprocess
-
-OFFSETS_SCAN_BLOCK = 1024                 # OFFS_THREADS of skf_augment.hip: the N counts go through the scan in tiles of this many
 
 
 class _Replay:

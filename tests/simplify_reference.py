@@ -12,7 +12,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "prepare_quickdraw")       # tools/record_prepare_quickdraw_golden.py wrote it
 LDS_POINTS = 512                          # SKF_RDP_LDS_POINTS of include/skf.h: longer polylines run from the workspace
-OFFSETS_SCAN_BLOCK = 1024                 # OFFS_THREADS of skf_simplify.hip: the counts go through the scan in tiles of this many
+OFFSETS_SCAN_BLOCK = 1024                 # OFFS_THREADS of skf_ragged.hip: the counts go through the scan in tiles of this many
 
 
 # ---------------------------------------------------------------- the rule
