@@ -1107,6 +1107,34 @@ int skf_edit_distance_i64(const long long* a, long long lda, const int* len_a, i
 int skf_dtw_f32(const float* xy_a, long long lda, const int* n_a, int Na, int Ta, const float* xy_b, long long ldb, const int* n_b,
                 int Nb, int Tb, int cross, float* out, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Teacher-forced scoring (sequence log-likelihood, rank)
+ * The reference has nothing in this place: its surface stops at predict.  The decoders above produce sequences; this entry answers
+ * the opposite question - how likely is a GIVEN sequence under the logits skf_model_forward left in the 'logits' buffer - with one
+ * read of every logit that counts and none of the others.  skf_softmax_ce is the training kernel (in-place gradient, PAD mask, no
+ * rank, no per-sequence sum); this one only reads.  Nothing here allocates, synchronises with the host or uses an atomic; two
+ * calls on the same inputs agree bit for bit and a sequence's results depend neither on B, nor on its slot, nor on its neighbours.
+ * skf_sequence_score: row b * T + t of logits (pitch ld elements; float32, or bf16 with is_bf16 = 1, widened exactly) is the
+ *   distribution over the token at target position y = target[b * tgt_ld + tgt_off + t].
+ *   Scored length n_b (the `length` of skf_model_beam_decode): with t* the first position whose y == eos, n_b = t* + 1 (the EOS
+ *     itself is scored); without one, n_b = the first position whose y == 0 (PAD); without either, n_b = T.  seq_len[b] = n_b.
+ *   Scored positions, t < n_b:  tok_logp[b, t] = z_y - m - log sum_j exp(z_j - m), m the row maximum, in float32;
+ *     tok_rank[b, t] = #{j : z_j > z_y} + #{j < y : z_j == z_y}: rank 0 is the first-index-argmax hit of
+ *     builders/keras_metrics.py:25 that skf_softmax_ce reports as row_hit.
+ *   Unscored positions, t >= n_b:  tok_logp = 0.0f, tok_rank = -1; their logits rows and their targets are NOT READ (they may hold
+ *     anything, NaN included).
+ *   seq_logp[b] = the float32 sum of the stored tok_logp[b, 0 .. n_b - 1], added one at a time in ascending t from 0.0f (n_b = 0
+ *     gives 0.0f): a float32 host loop over tok_logp gives the same bits.
+ *   Edge rules.  A target outside [0, V) is never used as an index: the position scores -inf with rank V (its row is not read).
+ *     -inf logits are legal: under a finite row maximum a -inf target scores -inf (not NaN) and other -inf entries add 0 to the sum.
+ *     A row that is all -inf, or holds +inf or a NaN, is outside the contract (the position's results are meaningless; nothing
+ *     else is affected).  The maximum is subtracted before every exp: rows around +80 or -80 score like rows around 0.
+ *   Rows whose base and pitch are 16-byte aligned (ld % 4 == 0 in float32, ld % 8 == 0 in bf16) are read 16 bytes per lane, any
+ *     other pitch element by element; the results do not depend on which.
+ *   Limits (SKF_EINVAL): B, T, V >= 1; B * T < 2^31; ld >= V; tgt_off >= 0 and tgt_ld >= tgt_off + T; is_bf16 in {0, 1}; logits
+ *     aligned to its element, target 8-byte and the four outputs (tok_logp, tok_rank (B, T); seq_logp, seq_len (B)) 4-byte aligned. */
+int skf_sequence_score(const void* logits, int is_bf16, int ld, int B, int T, int V, const long long* target, int tgt_ld, int tgt_off,
+                       long long eos, float* tok_logp, int* tok_rank, float* seq_logp, int* seq_len, skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,7 @@ SIGNATURES = {
     "skf_stroke3_simplify": (_I, [_P, _L, _P, _I, _D, _U, _P, _P, _P, _Z, _P]),
     "skf_edit_distance_i64": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
     "skf_dtw_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
+    "skf_sequence_score": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _L, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

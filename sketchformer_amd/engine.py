@@ -123,6 +123,10 @@ SAMPLING_NEEDS_TOKENS = ("sampled decoding is built for token models: a continuo
                          "logits, no categorical distribution over tokens to draw from")
 
 
+SCORING_NEEDS_TOKENS = ("teacher-forced scoring is built for token models: a continuous model has a regression head and three pen "
+                        "logits, no categorical distribution that gives a token sequence a likelihood")
+
+
 def check_sampling(temperature, top_k, top_p):
     """The parameter ranges of the selection rule (include/skf.h: SkfSampling); ValueError outside them."""
     if not float(temperature) > 0.0 or float(temperature) == float("inf"):
@@ -430,6 +434,48 @@ class TrainEngine:
         self.synchronize()
         return (out[:n_valid, :, :n_out.value].cpu().numpy().astype(np.int32), scores[:n_valid].cpu().numpy(),
                 lengths[:n_valid].cpu().numpy())
+
+    def score(self, inp, tar=None, n_valid=None, eos=0):
+        """Teacher-forced scoring (skf_sequence_score; the rule is in include/skf.h): ``forward(inp, tar, training=False)``, then the
+        log-likelihood and the rank of every token tar[:, 1:seq_len] under the 'logits' buffer, fp32 or bf16 model alike.  tar=None
+        scores the input against itself (the autoencoding objective).  A sequence is scored through its first ``eos`` (to its first
+        PAD without one).  The scoring launches follow the forward on the engine's stream and the caller's stream is ordered behind
+        them; there is no host synchronisation.  Returns device tensors for the first n_valid rows: (tok_logp (n, seq_len - 1)
+        float32, tok_rank (n, seq_len - 1) int32, seq_logp (n,) float32, seq_len (n,) int32).  Token models with a reconstruction
+        head only (ValueError otherwise)."""
+        if self.cfg.continuous:
+            raise ValueError(SCORING_NEEDS_TOKENS)
+        if not self.cfg.do_reconstruction:
+            raise ValueError("do_reconstruction is off: the model has no decoder whose logits could be scored")
+        B, L, V = self.cfg.batch, self.cfg.seq_len, self.cfg.vocab_size
+        T = L - 1
+        n_valid = B if n_valid is None else int(n_valid)
+        if not 1 <= n_valid <= B:
+            raise ValueError("n_valid must be in [1, batch = %d]" % B)
+        inp = self._dev_input(inp, clone=True)
+        tar = inp if tar is None else self._dev_input(tar, clone=True)
+        if tar.dim() != 2 or tar.shape[0] != B or tar.shape[1] < L:
+            raise ValueError("tar must hold batch=%d rows of at least seq_len=%d tokens (got %r)" % (B, L, tuple(tar.shape)))
+        # allocated on the caller's stream BEFORE the hand-over; written on the engine's
+        tok_logp = torch.empty(B, T, dtype=torch.float32, device=self.device)
+        tok_rank = torch.empty(B, T, dtype=torch.int32, device=self.device)
+        seq_logp = torch.empty(B, dtype=torch.float32, device=self.device)
+        seq_len = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._enter()
+        try:
+            self._hold(inp, tar, tok_logp, tok_rank, seq_logp, seq_len)
+            _lib.call("skf_model_forward", self.handle, self._p(inp), self._p(tar), self._ld(tar), 0, self._stream())
+            ptr, rows, cols, ld, is16 = C.c_void_p(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            _lib.call("skf_model_buffer_info", self.handle, b"logits", C.byref(ptr), C.byref(rows), C.byref(cols), C.byref(ld),
+                      C.byref(is16))
+            if rows.value != B * T or cols.value != V:
+                raise _lib.SkfError("the 'logits' buffer is (%d, %d), expected (%d, %d)" % (rows.value, cols.value, B * T, V))
+            _lib.call("skf_sequence_score", ptr, is16.value, ld.value, B, T, V, self._p(tar), tar.stride(0), 1, int(eos),
+                      self._p(tok_logp), self._p(tok_rank), self._p(seq_logp), self._p(seq_len), self._stream())
+        finally:
+            self._leave()
+        self._publish()          # the caller's stream waits for the engine's (an event, not the host)
+        return tok_logp[:n_valid], tok_rank[:n_valid], seq_logp[:n_valid], seq_len[:n_valid]
 
     def _decode_embedding(self, embedding, rows=None):
         """The caller's embedding as a float32 device tensor of the shape the decoder starts from (``rows`` of them: the batch

@@ -56,6 +56,45 @@ class DeferredMetrics(Mapping):
         return repr(self._resolved())
 
 
+def score_in_chunks(inp_seq, tar_seq, seq_len, batch, eos, score_chunk):
+    """The host side of ``Transformer.score``, free of the device.  inp_seq: (n, seq_len) model-ready token rows (a single row, or
+    the (n, seq_len, 1) token columns of the file loaders, are accepted); tar_seq: None (= inp_seq) or n rows of seq_len or
+    seq_len + 1 columns - the shape predict / sample / beam_search return - of which the forward consumes the first seq_len.
+    The rows go to ``score_chunk(inp (batch, seq_len), tar (batch, seq_len), m)`` in consecutive chunks of ``batch`` rows, the last one
+    zero-padded, m of them valid; it returns (tok_logp (m, seq_len - 1), tok_rank, seq_logp (m,), seq_len (m,)) host arrays.
+    Returns {'logp': (n,), 'length': (n,), 'token_logp': (n, seq_len - 1), 'rank': (n, seq_len - 1),
+    'perplexity': exp(-logp / max(length, 1)), 'complete': (n,) bool - the row's EOS lies inside the scored window tar[:, 1:seq_len]}.
+    A row that runs past the window is scored on what fits and flagged through 'complete', not rejected."""
+    def rows(x, what, widths):
+        x = np.asarray(x)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim == 3 and x.shape[-1] == 1:
+            x = x[..., 0]
+        if x.ndim != 2 or x.shape[1] not in widths:
+            raise ValueError("%s must hold rows of %s tokens (got shape %r)" % (what, " or ".join(str(w) for w in widths), x.shape))
+        return x.astype(np.int64)
+    L, B = int(seq_len), int(batch)
+    inp = rows(inp_seq, "inp_seq", (L,))
+    tar = inp if tar_seq is None else rows(tar_seq, "tar_seq", (L, L + 1))[:, :L]
+    n = len(inp)
+    if n == 0:
+        raise ValueError("no sequence given")
+    if len(tar) != n:
+        raise ValueError("tar_seq must hold one row per row of inp_seq (got %d and %d)" % (len(tar), n))
+    parts = []
+    for i in range(0, n, B):
+        m = min(B, n - i)
+        pi, pt = np.zeros((B, L), np.int64), np.zeros((B, L), np.int64)
+        pi[:m], pt[:m] = inp[i:i + m], tar[i:i + m]
+        parts.append([np.asarray(a)[:m] for a in score_chunk(pi, pt, m)])
+    token_logp, rank, logp, length = (np.concatenate([p[k] for p in parts], axis=0) for k in range(4))
+    with np.errstate(over="ignore"):
+        perplexity = np.exp(-logp.astype(np.float64) / np.maximum(length, 1))
+    return {'logp': logp, 'length': length, 'token_logp': token_logp, 'rank': rank, 'perplexity': perplexity,
+            'complete': (tar[:, 1:L] == eos).any(axis=1)}
+
+
 class Transformer(BaseModel, TransformerMetricsMixin):
     name = 'sketch-transformer-tf2'
     quick_metrics = ['recon_loss', 'recon_acc', 'class_loss', 'class_acc', 'total_loss']
@@ -460,6 +499,24 @@ class Transformer(BaseModel, TransformerMetricsMixin):
         tlen = None if self.hps['blind_decoder_mask'] else np.sum(x > 0, axis=-1).reshape(-1)
         return self.sample_from_embedding(self._embed_on_device(x), n_samples=n_samples, temperature=temperature, top_k=top_k,
                                           top_p=top_p, seed=seed, expected_len=tlen)
+
+    def score(self, inp_seq, tar_seq=None):
+        """Teacher-forced scoring of any number of sequences (engine.score; the rule is in include/skf.h): how likely tar_seq is
+        under the model that has encoded inp_seq.  tar_seq=None scores every sketch against itself (the autoencoding objective);
+        otherwise row i of tar_seq - seq_len or seq_len + 1 columns, what predict / sample / beam_search return - is scored given
+        row i of inp_seq.  A sequence counts through its EOS (the tokenizer's); see ``score_in_chunks`` for the chunking and the
+        returned dict of host arrays: 'logp', 'length', 'token_logp', 'rank', 'perplexity', 'complete'.  A row's result depends
+        neither on the number of rows, nor on its chunk, nor on its neighbours.  Token models only."""
+        from .. import engine as _engine
+        if self.dataset.hps['use_continuous_data']:
+            raise ValueError(_engine.SCORING_NEEDS_TOKENS)
+        if not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        eos = self._sos_eos()[1]
+
+        def score_chunk(inp, tar, m):
+            return [t.cpu().numpy() for t in self.engine.score(inp, tar, n_valid=m, eos=eos)]
+        return score_in_chunks(inp_seq, tar_seq, self.seq_len, self.engine.cfg.batch, eos, score_chunk)
 
     def load_reference_checkpoint(self, prefix):
         """Weights (+ Adam slots, optimizer.iterations, current_step) from a checkpoint written by the reference's

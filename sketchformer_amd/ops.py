@@ -1185,3 +1185,51 @@ def dtw_distance(xy_a, n_a, xy_b, n_b, cross=False):
     _lib.call("skf_dtw_f32", _p(xy_a), max(xy_a.stride(0), 2 * Ta), _p(n_a), Na, Ta, _p(xy_b), max(xy_b.stride(0), 2 * Tb), _p(n_b), Nb, Tb,
               1 if cross else 0, _p(out), _stream())
     return out
+
+
+def sequence_score(logits, target, eos, tgt_off=0, T=None):
+    """Teacher-forced scoring of given sequences (skf_sequence_score; the rule is in include/skf.h).  logits: float32 or bfloat16,
+    (B, T, V), or (B * T, V) with ``T`` given, unit innermost stride; the row pitch may exceed V as long as it is the same for every
+    row (a view such as TrainEngine.buffer('logits') is taken as it is - nothing is copied).  target: (B, >= tgt_off + T) int64, row b
+    holds the token of position t at column tgt_off + t; eos: the token that ends a sequence.
+    -> (tok_logp (B, T) float32, tok_rank (B, T) int32, seq_logp (B,) float32, seq_len (B,) int32) on the device: log p and rank of
+    every position in front of the sequence's end (0.0 / -1 behind it, where the logits are not read), their sum in ascending
+    order, and the scored length (through the EOS; to the first PAD without one)."""
+    if not torch.is_tensor(logits) or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("logits must be a float32 or bfloat16 tensor (got %s)" % (getattr(logits, "dtype", type(logits)),))
+    if logits.dim() == 3:
+        if T is not None and int(T) != logits.shape[1]:
+            raise ValueError("T=%r does not match logits of shape %r" % (T, tuple(logits.shape)))
+        B, T, V = logits.shape
+        ld = logits.stride(1)
+        if logits.stride(2) != 1 or ld < V or (B > 1 and logits.stride(0) != T * ld):
+            raise ValueError("logits must have a unit innermost stride and one row pitch >= V for all B * T rows")
+    elif logits.dim() == 2:
+        if T is None or int(T) < 1 or logits.shape[0] % int(T):
+            raise ValueError("logits of shape (B * T, V) need T, a divisor of the row count (got T=%r for %d rows)" % (T, logits.shape[0]))
+        T, V = int(T), logits.shape[1]
+        B = logits.shape[0] // T
+        ld = logits.stride(0) if logits.shape[0] > 1 else V
+        if logits.stride(1) != 1 or ld < V:
+            raise ValueError("logits must have a unit innermost stride and a row pitch >= V")
+    else:
+        raise ValueError("logits must have shape (B, T, V), or (B * T, V) with T given")
+    if B < 1 or T < 1 or V < 1:
+        raise ValueError("logits must hold at least one row and one column")
+    tgt_off = int(tgt_off)
+    if not torch.is_tensor(target) or target.dtype != torch.int64 or target.dim() != 2:
+        raise ValueError("target must be an int64 tensor of shape (B, >= tgt_off + T)")
+    if target.device != logits.device:
+        raise ValueError("target must be on the device of logits")
+    if tgt_off < 0 or target.shape[0] != B or target.shape[1] < tgt_off + T:
+        raise ValueError("target must hold B=%d rows of at least tgt_off + T = %d columns (got %r)" % (B, tgt_off + T, tuple(target.shape)))
+    if target.stride(1) != 1 or (B > 1 and target.stride(0) < target.shape[1]):
+        raise ValueError("target must have a unit innermost stride and rows that do not overlap")
+    _p(logits); _p(target)                                       # CPU tensors: SkfError before anything is allocated
+    dev = logits.device
+    f32 = torch.empty(B * (T + 1), dtype=torch.float32, device=dev)      # two allocations for the four results
+    i32 = torch.empty(B * (T + 1), dtype=torch.int32, device=dev)
+    tok_logp, seq_logp, tok_rank, seq_len = f32[:B * T].view(B, T), f32[B * T:], i32[:B * T].view(B, T), i32[B * T:]
+    _lib.call("skf_sequence_score", _p(logits), int(logits.dtype == torch.bfloat16), ld, B, T, V, _p(target),
+              max(target.stride(0), target.shape[1]), tgt_off, int(eos), _p(tok_logp), _p(tok_rank), _p(seq_logp), _p(seq_len), _stream())
+    return tok_logp, tok_rank, seq_logp, seq_len
