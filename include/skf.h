@@ -782,6 +782,45 @@ int skf_model_sample_decode(SkfModel* m, const float* embedding, const int* expe
 int skf_model_beam_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
                           long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths,
                           int* out_len_host, const SkfBeam* beam, skf_stream_t stream);
+/* ---- sketch completion: prefix-forced decoding ----
+ * The rule.  A prefix gives row b a length len[b], 0 <= len[b] <= max_steps, and tokens prefix[b][0 .. len[b]-1]; they become the
+ * output columns 1 .. len[b].  Position s is the step that reads column s and writes column s + 1; it is FORCED for row b iff
+ * s < len[b].  A forced position writes prefix[b][s] to column s + 1 with every effect an emitted token has (the mask byte
+ * token == 0, the sticky EOS flag, its part in the stop test), appends the position's K|V row to every layer's cache, and computes no
+ * logits.  A token outside [0, vocab) is treated as PAD, as the embedding lookup does.
+ *   Sampling: u = skf_sample_uniform(seed, stream_id[b], position) is a function of the absolute position: a forced position
+ *   consumes nothing and shifts nothing.
+ *   Beam search: at a forced position a live beam offers exactly one candidate, (0.0f, prefix token); its other offers are -inf.  The
+ *   merge (skf_beam_advance) is what it was, so the returned scores are log p(continuation | prefix, embedding).  The prefix and the
+ *   length of sketch g are replicated into the W rows of the sketch on the device, like the embedding.
+ *   Stop rule: unchanged, and a forced EOS counts.  If every one of the n_valid rows has an EOS inside its prefix the decode ends
+ *   inside the prefix, and *out_len_host is what stepping through it reports.
+ *   len = 0 everywhere is exactly skf_model_greedy_decode / _sample_decode / _beam_decode.
+ * SkfPrefix: tokens (rows, ld) int64 on the device, len_host `rows` host ints; rows = batch for skf_model_prefix_decode, n = batch /
+ *   beam_width for skf_model_beam_prefix_decode.  stepwise = 0: the cache rows of all forced positions are produced first, layer by
+ *   layer, in num_layers launches over (max len, rows) workgroups (the prefill), and the position loop starts at the shortest
+ *   prefix; rows with a longer one idle through their remaining forced positions.  stepwise = 1: every forced position is one
+ *   position launch, like a free one.  Both give the same bits: outputs, lengths and cache rows.  The beam entry always steps.
+ * skf_model_prefix_decode: skf_model_greedy_decode (sampling == NULL) or skf_model_sample_decode (sampling, stream_ids_host) with
+ *   a prefix.  skf_model_beam_prefix_decode: skf_model_beam_decode with one.
+ *   SKF_EINVAL: prefix == NULL, a bad struct_size, a null tokens / len_host, a length outside [0, max_steps], ld < the largest length,
+ *   and whatever the entry without a prefix refuses.  SKF_EUNSUPPORTED: a continuous model; SKF_MODEL_DECODE_LAYERWISE, or dimensions
+ *   the one-launch position kernel does not serve (prefixes exist on that kernel only).
+ *   The buffers "decode/cache0" .. "decode/cache{N-1}" (B * L, 2 d) hold the self-attention K|V rows of the last reconstruction; like
+ *   "decode/tokens" they are diagnostics and NOT part of the stable interface. */
+typedef struct SkfPrefix {
+  uint32_t struct_size;    /* sizeof(SkfPrefix) */
+  const long long* tokens; /* device (rows, ld) */
+  int32_t ld;
+  const int* len_host;     /* rows host ints, 0 <= len <= max_steps */
+  int32_t stepwise;        /* 0: prefill + skip; 1: step through the forced positions */
+} SkfPrefix;
+int skf_model_prefix_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                            long long eos, int max_steps, void* out, int* out_len_host, const SkfPrefix* prefix,
+                            const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream);
+int skf_model_beam_prefix_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                                 long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths,
+                                 int* out_len_host, const SkfBeam* beam, const SkfPrefix* prefix, skf_stream_t stream);
 /* look up an internal activation by name ("logits", "class_probs", "embedding", "enc_output", ...); skf_model_buffer serves
  * fp32 buffers, skf_model_buffer_info any buffer with its row pitch (elements) and element type (bf16 models keep their
  * activations in bf16) */

@@ -101,6 +101,17 @@ class SkfBeam(C.Structure):
             self.struct_size = C.sizeof(SkfBeam)
 
 
+class SkfPrefix(C.Structure):
+    """include/skf.h: struct SkfPrefix, field for field (skf_model_prefix_decode, skf_model_beam_prefix_decode)."""
+    _fields_ = [("struct_size", C.c_uint32), ("tokens", C.c_void_p), ("ld", C.c_int32), ("len_host", C.POINTER(C.c_int)),
+                ("stepwise", C.c_int32)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(SkfPrefix)
+
+
 BEAM_MAX = 8                                          # SKF_BEAM_MAX
 
 
@@ -261,6 +272,10 @@ SIGNATURES = {
     "skf_beam_finish": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "skf_beam_advance": (_I, [_P, _P, _I, _I, _I, C.c_longlong, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P]),
     "skf_model_beam_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, _P, _P, C.POINTER(_I), C.POINTER(SkfBeam), _P]),
+    "skf_model_prefix_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, C.POINTER(_I), C.POINTER(SkfPrefix),
+                                     C.POINTER(SkfSampling), C.POINTER(_I), _P]),
+    "skf_model_beam_prefix_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, _P, _P, C.POINTER(_I),
+                                          C.POINTER(SkfBeam), C.POINTER(SkfPrefix), _P]),
     "skf_model_apply_gradients": (_I, [_P, _F, _P]),
     "skf_model_buffer": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]),
     "skf_model_buffer_info": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),

@@ -36,12 +36,22 @@ struct SkfDecodeFused {
   int beam, beam_rows;
   const int* anc;                                 // (2, B, Le + 1)
   float* cand_lp; int* cand_tok;                  // (B, W), log p descending, then token ascending
+  // prefix != null (token mode, no attention output; include/skf.h: prefix-forced decoding): position s of row b is forced iff
+  // s < prefix_len[b]; it emits prefix[b][s] and computes no logits (BEAM: its one candidate is (0, that token)).  prefilled: the
+  // cache rows of every forced position exist already (skf_decode_prefill_launch), so a forced row skips the layers as well.
+  const long long* prefix; int prefix_ld;         // (B, prefix_ld) device
+  const int* prefix_len;                          // (B) device
+  int prefilled;
 };
 
 bool skf_decode_fused_supported(int d, int H, int F, int Le, int N, int Vout);
 // the same for the beam instantiation, whose workgroup also keeps the offsets of its history (2 (Le + 1) ints) in LDS
 bool skf_decode_beam_supported(int d, int H, int F, int Le, int N, int Vout);
 int skf_decode_fused_launch(const SkfDecodeFused& p, hipStream_t st);
+// The cache rows 0 .. prefix_len[b]-1 of every layer and row in N launches over (max_len, B) workgroups, behind one small launch that
+// writes the prefix columns, flags and done_step the skipped positions would have left, and *step_dev = min_b prefix_len[b].
+// max_len >= every prefix_len[b] (the grid); the tokens' column 0 (skf_decode_init), dyn and the cross K|V must be in place.
+int skf_decode_prefill_launch(const SkfDecodeFused& p, int max_len, hipStream_t st);
 
 // SkfSampling as the public entries take it: struct_size, temperature > 0, top_k >= 0, 0 < top_p <= 1 (SKF_EINVAL otherwise)
 int skf_sampling_check(const SkfSampling* s);

@@ -15,6 +15,9 @@
 // fixed order (deterministic).
 // The last workgroup to finish a position (ticket counter) does the cross-sample part: "all n_valid samples have emitted
 // an EOS" -> done_step, and advances the device-side step index, so a position is ONE launch (captured once, replayed).
+// Sketch completion (include/skf.h: prefix-forced decoding): where a prefix gives the position's token, the kernel emits it without
+// computing logits; decode_prefill_kernel below produces the K | V cache rows of all such positions at once, layer by layer, from
+// the device functions this kernel is made of, and a forced row then skips its layers as well.
 #include "skf_common.h"
 #include "skf_decode_fused.h"
 #include "skf_sample.h"
@@ -267,6 +270,77 @@ __device__ __forceinline__ void beam_candidates(float* hs, int V, int W, float* 
   }
 }
 
+// The workgroup's LDS areas, the same in the position kernel and in the prefill kernel.
+struct DecLds {
+  float* xs;      // [d]  layer input
+  float* o1;      // [d]  after LN1
+  float* o2;      // [d]  after LN2
+  float* ys;      // [d]  Dense output awaiting its residual
+  float* os;      // [d]  attention output
+  float* qkv;     // [3d]
+  float* hs;      // [max(F, Vout)] FFN hidden / logits
+  float* part;    // [4 NT] GEMV partial sums
+  float* red;     // [16]
+  float* sc;      // [H][LkP] attention scores / probabilities
+};
+
+__device__ __forceinline__ DecLds dec_lds(float* lds, int d, int hs_len) {
+  DecLds a;
+  a.xs = lds; a.o1 = a.xs + d; a.o2 = a.o1 + d; a.ys = a.o2 + d; a.os = a.ys + d; a.qkv = a.os + d;
+  a.hs = a.qkv + 3 * d; a.part = a.hs + hs_len; a.red = a.part + 4 * NT; a.sc = a.red + 16;
+  return a;
+}
+
+// decoder input of one position (builders/layers/transformer.py:325-334, dropout off); token mode.  Ends with a barrier.
+__device__ __forceinline__ void embed_token(const SkfDecodeFused& p, long long tk, int pos_i, float* xs, int d, int tid) {
+  if (tid < d) {
+    if (tk < 0 || tk >= p.vocab) tk = 0;
+    const float v = p.emb_table[(size_t)tk * d + tid];
+    xs[tid] = v * sqrtf((float)d) + p.pos[(size_t)pos_i * d + tid];
+  }
+  __syncthreads();
+}
+
+// The two halves of a decoder layer on either side of its self-attention, shared by the position kernel and the prefill kernel.
+// layer_qkv: [q|k|v] = xs Wqkv into a.qkv, k|v appended to the cache as `cache_row`.  Ends with a barrier (the appended row is read
+// back by the attention: workgroup-scope visibility of the global stores).
+__device__ __forceinline__ void layer_qkv(const SkfDecLayer& w, const DecLds& a, float* __restrict__ cache_row, int d, int tid) {
+  dense(w.qkv, a.xs, a.qkv, 0, a.part, tid);
+  for (int c = tid; c < 2 * d; c += NT) cache_row[c] = a.qkv[d + c];
+  __syncthreads();
+}
+
+// layer_rest: from the self-attention output a.os to the layer's output in a.xs: o-projection ; LN ; cross attention over kv2 (keys
+// >= limit masked) ; o-projection ; LN ; FFN ; LN.  aw2: where the cross-attention weights go, or null.
+template <int DH>
+__device__ __forceinline__ void layer_rest(const SkfDecLayer& w, const DecLds& a, const float* __restrict__ kv2, int limit, int d, int H,
+                                           int Le, int LkP, int tid, float* __restrict__ aw2, size_t aw_hs) {
+  dense(w.o, a.os, a.ys, 0, a.part, tid);
+  add_ln(a.xs, a.ys, w.ln1_g, w.ln1_b, a.o1, d, a.red, tid);
+  dense(w.q2, a.o1, a.qkv, 0, a.part, tid);
+  attend<DH>(a.qkv, kv2, kv2 + d, 2 * d, Le, nullptr, limit, d, H, a.sc, LkP, a.part, a.os, tid, aw2, aw_hs, Le);
+  dense(w.o2, a.os, a.ys, 0, a.part, tid);
+  add_ln(a.o1, a.ys, w.ln2_g, w.ln2_b, a.o2, d, a.red, tid);
+  dense(w.f1, a.o2, a.hs, 1, a.part, tid);
+  dense(w.f2, a.hs, a.ys, 0, a.part, tid);
+  add_ln(a.o2, a.ys, w.ln3_g, w.ln3_b, a.xs, d, a.red, tid);
+}
+
+// cross attention: keys >= limit are masked (models/sketchformer.py:172,279-283)
+__device__ __forceinline__ int cross_limit(const SkfDecodeFused& p, int b, int step) {
+  int limit = 0x7fffffff;
+  if (!p.blind) { limit = p.limit ? p.limit[b] : -1; if (limit < 0) limit = step + 1; }
+  return limit;
+}
+
+// The token a prefix forces on row b at position `step` (include/skf.h: prefix-forced decoding), or -1 where the position is free.
+// A token outside [0, vocab) counts as PAD, as in the embedding lookup.
+__device__ __forceinline__ int forced_token(const SkfDecodeFused& p, int b, int step) {
+  if (!p.prefix || step >= p.prefix_len[b]) return -1;
+  const long long tk = p.prefix[(size_t)b * p.prefix_ld + step];
+  return tk < 0 || tk >= p.vocab ? 0 : (int)tk;
+}
+
 // AW: the instantiation that writes the attention weights; the other one is the decoder without that output.
 // SAMPLE: the token is drawn (temperature / top-k / nucleus, skf_sample.h) instead of maximised; what follows the choice is shared.
 // BEAM: the history is read through the ancestry table and the kernel ends with the row's W best candidates (skf_beam.hip).
@@ -275,16 +349,8 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, b = blockIdx.x;
   const int d = p.d;
-  float* xs = lds;                 // [d]  layer input
-  float* o1 = xs + d;              // [d]  after LN1
-  float* o2 = o1 + d;              // [d]  after LN2
-  float* ys = o2 + d;              // [d]  Dense output awaiting its residual
-  float* os = ys + d;              // [d]  attention output
-  float* qkv = os + d;             // [3d]
-  float* hs = qkv + 3 * d;         // [max(F, Vout)] FFN hidden / logits
-  float* part = hs + p.hs_len;     // [4 NT] GEMV partial sums
-  float* red = part + 4 * NT;      // [16]
-  float* sc = red + 16;            // [H][LkP] attention scores / probabilities
+  const DecLds a = dec_lds(lds, d, p.hs_len);
+  float *const xs = a.xs, *const hs = a.hs, *const part = a.part, *const sc = a.sc;
   const int LkP = p.Le + 1;
   const int step = *p.step_dev;
   // BEAM: where positions 0..step of the hypothesis live, as offsets from slot 0: [Le + 1] K | V rows (floats), [Le + 1] mask bytes
@@ -301,57 +367,57 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   }
   const int n_valid = (int)p.dyn[0];
   const long long eos = p.dyn[1];
-
-  // decoder input of the position (builders/layers/transformer.py:325-334, dropout off)
-  if (tid < d) {
-    float v;
-    if (p.tokens) {
-      long long tk = p.tokens[(size_t)b * p.Ti + step];
-      if (tk < 0 || tk >= p.vocab) tk = 0;
-      v = p.emb_table[(size_t)tk * d + tid];
-    } else {
-      const float* x = p.cont + ((size_t)b * p.Ti + step) * 5;
-      const float* W = p.embd_w;
-      v = x[0] * W[tid] + x[1] * W[d + tid] + x[2] * W[2 * d + tid] + x[3] * W[3 * d + tid] + x[4] * W[4 * d + tid] + p.embd_b[tid];
+  // prefix-forced decoding (include/skf.h): the position's token is given, so it needs no logits; after a prefill (skf_decode_prefill_launch)
+  // its K | V rows exist as well and the layers are skipped too.  Workgroup-uniform.  No prefix: the code below is what it was.
+  const int ftok = AW ? -1 : forced_token(p, b, step);
+  const bool forced = ftok >= 0;
+  if (BEAM || !forced || !p.prefilled) {
+    // decoder input of the position (builders/layers/transformer.py:325-334, dropout off)
+    if (tid < d) {
+      float v;
+      if (p.tokens) {
+        long long tk = p.tokens[(size_t)b * p.Ti + step];
+        if (tk < 0 || tk >= p.vocab) tk = 0;
+        v = p.emb_table[(size_t)tk * d + tid];
+      } else {
+        const float* x = p.cont + ((size_t)b * p.Ti + step) * 5;
+        const float* W = p.embd_w;
+        v = x[0] * W[tid] + x[1] * W[d + tid] + x[2] * W[2 * d + tid] + x[3] * W[3 * d + tid] + x[4] * W[4 * d + tid] + p.embd_b[tid];
+      }
+      xs[tid] = v * sqrtf((float)d) + p.pos[(size_t)step * d + tid];
     }
-    xs[tid] = v * sqrtf((float)d) + p.pos[(size_t)step * d + tid];
-  }
-  __syncthreads();
+    __syncthreads();
 
-  int limit = 0x7fffffff;          // cross attention: keys >= limit are masked (models/sketchformer.py:172,279-283)
-  if (!p.blind) { limit = p.limit ? p.limit[b] : -1; if (limit < 0) limit = step + 1; }
-  const unsigned char* smask = p.selfmask + (size_t)b * p.mask_ld;
-  // attention weights of the position: row `step` of (2N, B, H, attn_rows, Le); block k of layer l at + (2l + k) * blk
-  const size_t aw_hs = (size_t)p.attn_rows * p.Le, aw_blk = (size_t)p.B * p.H * aw_hs;
-  float* aw = AW && step < p.attn_rows ? p.attn + ((size_t)b * p.H * p.attn_rows + step) * p.Le : nullptr;
+    const int limit = cross_limit(p, b, step);
+    const unsigned char* smask = p.selfmask + (size_t)b * p.mask_ld;
+    // attention weights of the position: row `step` of (2N, B, H, attn_rows, Le); block k of layer l at + (2l + k) * blk
+    const size_t aw_hs = (size_t)p.attn_rows * p.Le, aw_blk = (size_t)p.B * p.H * aw_hs;
+    float* aw = AW && step < p.attn_rows ? p.attn + ((size_t)b * p.H * p.attn_rows + step) * p.Le : nullptr;
 
-  for (int l = 0; l < p.N; ++l) {
-    const SkfDecLayer& w = p.layer[l];
-    dense(w.qkv, xs, qkv, 0, part, tid);
-    float* cache = w.cache + (size_t)b * p.Le * 2 * d;             // (Le, 2d): K | V of the positions so far
-    for (int c = tid; c < 2 * d; c += NT) cache[(size_t)step * 2 * d + c] = qkv[d + c];
-    __syncthreads();               // the appended row is read back below: workgroup-scope visibility of the global stores
-    if constexpr (BEAM)
-      attend<DH, true>(qkv, w.cache, w.cache + d, 2 * d, step + 1, p.selfmask, 0x7fffffff, d, p.H, sc, LkP, part, os, tid, nullptr, 0, 0,
-                       koff, moff);
-    else
-      attend<DH>(qkv, cache, cache + d, 2 * d, step + 1, smask, 0x7fffffff, d, p.H, sc, LkP, part, os, tid,
-                 aw ? aw + (size_t)(2 * l) * aw_blk : nullptr, aw_hs, p.Le);
-    dense(w.o, os, ys, 0, part, tid);
-    add_ln(xs, ys, w.ln1_g, w.ln1_b, o1, d, red, tid);
-    dense(w.q2, o1, qkv, 0, part, tid);
-    const float* kv2 = w.kv2 + (size_t)b * p.Le * 2 * d;
-    attend<DH>(qkv, kv2, kv2 + d, 2 * d, p.Le, nullptr, limit, d, p.H, sc, LkP, part, os, tid,
-               aw ? aw + (size_t)(2 * l + 1) * aw_blk : nullptr, aw_hs, p.Le);
-    dense(w.o2, os, ys, 0, part, tid);
-    add_ln(o1, ys, w.ln2_g, w.ln2_b, o2, d, red, tid);
-    dense(w.f1, o2, hs, 1, part, tid);
-    dense(w.f2, hs, ys, 0, part, tid);
-    add_ln(o2, ys, w.ln3_g, w.ln3_b, xs, d, red, tid);
+    for (int l = 0; l < p.N; ++l) {
+      const SkfDecLayer& w = p.layer[l];
+      float* cache = w.cache + (size_t)b * p.Le * 2 * d;             // (Le, 2d): K | V of the positions so far
+      layer_qkv(w, a, cache + (size_t)step * 2 * d, d, tid);
+      if constexpr (BEAM)
+        attend<DH, true>(a.qkv, w.cache, w.cache + d, 2 * d, step + 1, p.selfmask, 0x7fffffff, d, p.H, a.sc, LkP, a.part, a.os, tid, nullptr, 0, 0,
+                         koff, moff);
+      else
+        attend<DH>(a.qkv, cache, cache + d, 2 * d, step + 1, smask, 0x7fffffff, d, p.H, a.sc, LkP, a.part, a.os, tid,
+                   aw ? aw + (size_t)(2 * l) * aw_blk : nullptr, aw_hs, p.Le);
+      layer_rest<DH>(w, a, w.kv2 + (size_t)b * p.Le * 2 * d, limit, d, p.H, p.Le, LkP, tid,
+                     aw ? aw + (size_t)(2 * l + 1) * aw_blk : nullptr, aw_hs);
+    }
   }
-  dense(p.out, xs, hs, 0, part, tid);          // logits of the position (F >= Vout is not assumed: hs holds max(F, Vout))
+  if (!forced) dense(p.out, xs, hs, 0, part, tid);          // logits of the position (F >= Vout is not assumed: hs holds max(F, Vout))
 
   if constexpr (BEAM) {
+    if (forced) {      // a live beam offers exactly one candidate, (0, the prefix token); beam_advance_kernel is what it was
+      if (tid < p.beam) {
+        p.cand_lp[(size_t)b * p.beam + tid] = tid == 0 ? 0.f : -INFINITY;
+        p.cand_tok[(size_t)b * p.beam + tid] = tid == 0 ? ftok : 0;
+      }
+      return;
+    }
     beam_candidates(hs, p.Vout, p.beam, p.cand_lp + (size_t)b * p.beam, p.cand_tok + (size_t)b * p.beam, part, tid);
     return;
   }
@@ -361,7 +427,9 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
     // models/sketchformer.py:285-301: next = argmax (first index on ties, tf.argmax); PAD masks the key in later steps;
     // EOS flags are sticky
     int am;
-    if constexpr (SAMPLE) {
+    if (forced) {
+      am = ftok;
+    } else if constexpr (SAMPLE) {
       am = skf_sample_row(hs, p.Vout, p.temperature, p.top_k, p.top_p,
                           skf_sample_bits24(p.seed, (uint32_t)p.stream_ids[b], (uint32_t)step), part, tid);
     } else {
@@ -415,10 +483,113 @@ __global__ __launch_bounds__(NT) void decode_position_kernel(SkfDecodeFused p) {
   }
 }
 
+// ---- prefill: the K | V cache rows of a known prefix, all positions at once (include/skf.h: prefix-forced decoding)
+// The tokens of a prefix are known in advance, so its positions depend on each other only through the cache rows of the layer
+// below.  Launch l (l = 0 .. N-1) runs one workgroup per (position s, row b) with s < len[b]:
+//   launch 0:      x = embed(prefix column s) * sqrt(d) + pos[s] ; q|k|v of layer 0 ; cache row s of layer 0
+//   launch l >= 1: the rest of layer l-1 (self-attention of q over cache rows 0..s, ..., LN3) ; q|k|v of layer l ; its cache row
+// x and q of the position travel from launch l to launch l + 1 in the position's cache row of layer l + 1, which nobody reads before
+// that launch has replaced them by the layer's k | v: a workgroup touches only its own row, and reads it before it writes it.
+// Nothing follows the last layer's cache row: a forced position needs neither that layer's tail nor the logits.
+// Every (b, s) calls the device functions the position kernel calls at step s, with the same arguments: the rows are bit-equal.
+// Four waves per SIMD = two workgroups per CU: without the bound the allocator stops at 130 VGPRs, two above the 128 that allow it.
+template <int DH>
+__global__ __launch_bounds__(NT, 4) void decode_prefill_kernel(SkfDecodeFused p, int l) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, s = blockIdx.x, b = blockIdx.y;
+  if (s >= p.prefix_len[b] || s >= p.Le) return;
+  const int d = p.d, LkP = p.Le + 1;
+  const DecLds a = dec_lds(lds, d, p.hs_len);
+  float* const row = p.layer[l].cache + ((size_t)b * p.Le + s) * 2 * d;       // x | q of the launch before, k | v from here on
+  if (l == 0) {
+    embed_token(p, p.tokens[(size_t)b * p.Ti + s], s, a.xs, d, tid);          // column s: the start symbol or prefix token s - 1
+  } else {
+    const SkfDecLayer& w = p.layer[l - 1];
+    if (tid < d) { a.xs[tid] = row[tid]; a.qkv[tid] = row[d + tid]; }
+    __syncthreads();
+    const float* cache = w.cache + (size_t)b * p.Le * 2 * d;
+    attend<DH>(a.qkv, cache, cache + d, 2 * d, s + 1, p.selfmask + (size_t)b * p.mask_ld, 0x7fffffff, d, p.H, a.sc, LkP, a.part, a.os, tid,
+               nullptr, 0, p.Le);
+    layer_rest<DH>(w, a, w.kv2 + (size_t)b * p.Le * 2 * d, cross_limit(p, b, s), d, p.H, p.Le, LkP, tid, nullptr, 0);
+  }
+  layer_qkv(p.layer[l], a, row, d, tid);
+  if (l + 1 < p.N && tid < d) {
+    float* next = p.layer[l + 1].cache + ((size_t)b * p.Le + s) * 2 * d;
+    next[tid] = a.xs[tid]; next[d + tid] = a.qkv[tid];
+  }
+}
+
+// What the positions a prefill skips would have left behind.  One workgroup.  Every row's prefix tokens and mask bytes go to their
+// columns; with S0 = the shortest prefix of the B rows, the flags and done_step are those after positions 0 .. S0-1, and *step_dev = S0.
+__global__ __launch_bounds__(256) void decode_prefill_init_kernel(SkfDecodeFused p) {
+  __shared__ int s_min[256], s_last[256];
+  const int tid = threadIdx.x;
+  const int n_valid = (int)p.dyn[0];
+  const long long eos = p.dyn[1];
+  int mn = 0x7fffffff;
+  for (int b = tid; b < p.B; b += 256) { const int n = p.prefix_len[b]; mn = n < mn ? n : mn; }
+  s_min[tid] = mn;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) s_min[tid] = s_min[tid + o] < s_min[tid] ? s_min[tid + o] : s_min[tid];
+    __syncthreads();
+  }
+  int S0 = s_min[0];
+  S0 = S0 < 0 ? 0 : (S0 > p.Le ? p.Le : S0);
+  int last = -1;                // the latest first-EOS position among this thread's rows of the stop test; Le: a row without one
+  for (int b = tid; b < p.B; b += 256) {
+    int n = p.prefix_len[b];
+    n = n > p.Le ? p.Le : n;
+    int first = p.Le;
+    for (int s = 0; s < n; ++s) {
+      const int tk = forced_token(p, b, s);
+      p.tokens[(size_t)b * p.Ti + s + 1] = tk;
+      p.selfmask[(size_t)b * p.mask_ld + s + 1] = tk == 0 ? 1 : 0;
+      if (s < S0 && first == p.Le && (long long)tk == eos) first = s;
+    }
+    if (first < p.Le) p.eos_seen[b] = 1;
+    if (b < n_valid) last = first > last ? first : last;
+  }
+  s_last[tid] = last;
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < 256; ++k) last = s_last[k] > last ? s_last[k] : last;
+    if (last >= 0 && last < p.Le) *p.done_step = last;
+    *p.step_dev = S0;
+  }
+}
+
 }  // namespace
 
 size_t skf_decode_fused_lds_bytes(const SkfDecodeFused& p) {
   return (size_t)(8 * p.d + p.hs_len + 4 * NT + 16 + p.H * (p.Le + 1)) * sizeof(float);
+}
+
+int skf_decode_prefill_launch(const SkfDecodeFused& p, int max_len, hipStream_t st) {
+  if (!p.prefix || !p.prefix_len || !p.tokens || p.beam || p.attn || max_len < 0 || max_len > p.Le) {
+    skf_set_error("%s: the prefill needs token mode, a prefix, and no beams or attention output", __func__);
+    return SKF_EINVAL;
+  }
+  {
+    SkfProfScope ps(st, "decode_prefill_init", 0.0, 0.0);
+    hipLaunchKernelGGL(decode_prefill_init_kernel, dim3(1), dim3(256), 0, st, p);
+    SKF_LAUNCH_CHECK();
+  }
+  if (max_len == 0) return SKF_OK;
+  const int dh = p.d / p.H;
+  const size_t smem = skf_decode_fused_lds_bytes(p);
+  SkfProfScope ps(st, "decode_prefill", 0.0, 0.0);
+#define SKF_DP(DHV)                                                                                                  \
+  {                                                                                                                  \
+    SKF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_prefill_kernel<DHV>),                            \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));                              \
+    for (int l = 0; l < p.N; ++l)                                                                                    \
+      hipLaunchKernelGGL((decode_prefill_kernel<DHV>), dim3(max_len, p.B), dim3(NT), smem, st, p, l);                \
+  }
+  if (dh == 16) SKF_DP(16) else if (dh == 32) SKF_DP(32) else SKF_DP(64)
+#undef SKF_DP
+  SKF_LAUNCH_CHECK();
+  return SKF_OK;
 }
 
 bool skf_decode_fused_supported(int d, int H, int F, int Le, int N, int Vout) {

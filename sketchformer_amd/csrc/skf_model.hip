@@ -278,6 +278,8 @@ extern "C" int skf_model_create(const SkfConfig* cfg, SkfModel** out) {
     const size_t B = cfg->batch, L1 = cfg->seq_len + 1;
     if (!cfg->continuous) M->reg("decode/tokens", A.img, B, 2 * L1, 2 * L1, 0);
     M->reg("decode/ancestry", A.anc, B, L1, L1, 0);
+    for (size_t l = 0; l < A.cache.size(); ++l)      // the self-attention K|V rows of the last reconstruction (see skf_model_prefix_decode)
+      M->reg("decode/cache" + std::to_string(l), A.cache[l], B * cfg->seq_len, 2 * (size_t)cfg->d_model, 2 * (size_t)cfg->d_model, 0);
   }
   if (!decode_areas_ok(M->bf16 ? M->p16.dca : M->plan.dca, M->bf16 ? M->p16.bytes : M->plan.bytes)) {
     skf_set_error("skf_model_create: internal error, the %s plan's decode areas are not distinct allocations", M->bf16 ? "bf16" : "fp32");
@@ -364,7 +366,35 @@ extern "C" int skf_model_encode(SkfModel* m, const void* inp, skf_stream_t strea
 }
 
 namespace {
-// The four reconstruction entries.  `entry` names the caller in the error text; sampled: skf_model_sample_decode (tokens are drawn);
+// SkfPrefix as the completion entries take it (`rows` prefixes).  Decided from the configuration and the arguments alone, in front of
+// everything that needs a bound model (a model that is not bound yet is told the same).
+int prefix_check(const char* entry, const SkfModel* m, const SkfPrefix* pf, int rows, int max_steps) {
+#define SKF_PFX_CHECK(cond, msg) \
+  do { if (!(cond)) { skf_set_error("%s: %s (%s)", entry, msg, #cond); return SKF_EINVAL; } } while (0)
+  SKF_PFX_CHECK(m, "null model");
+  SKF_PFX_CHECK(pf, "null SkfPrefix");
+  if (m->cfg.continuous) {
+    skf_set_error("%s: a prefix is a sequence of tokens forced on the one-launch position kernel: continuous (stroke-5) prefixes are not built",
+                  entry);
+    return SKF_EUNSUPPORTED;
+  }
+  SKF_PFX_CHECK(max_steps > 0 && max_steps <= m->cfg.seq_len, "max_steps must be in [1, seq_len]");
+  if (pf->struct_size != sizeof(SkfPrefix)) {
+    skf_set_error("%s: SkfPrefix.struct_size is %u, this library's SkfPrefix has %zu bytes (set struct_size = sizeof(SkfPrefix))", entry,
+                  pf->struct_size, sizeof(SkfPrefix));
+    return SKF_EINVAL;
+  }
+  SKF_PFX_CHECK(pf->tokens && pf->len_host, "null prefix tokens or lengths");
+  SKF_PFX_CHECK(rows > 0 && max_steps > 0, "no rows or no positions");
+  for (int r = 0; r < rows; ++r) {
+    SKF_PFX_CHECK(pf->len_host[r] >= 0 && pf->len_host[r] <= max_steps, "a prefix length must be in [0, max_steps]");
+    SKF_PFX_CHECK(pf->len_host[r] <= pf->ld, "ld must not be smaller than the longest prefix");
+  }
+#undef SKF_PFX_CHECK
+  return SKF_OK;
+}
+
+// The reconstruction entries.  `entry` names the caller in the error text; sampled: skf_model_sample_decode (tokens are drawn);
 // rq: skf_model_beam_decode hands in its beam members (out = the tokens of rq.bm_out), the rest of the request is filled here.
 int decode_entry(const char* entry, SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
                  long long eos, int max_steps, void* out, int* out_len_host, float* attn_weights, bool sampled,
@@ -376,6 +406,10 @@ int decode_entry(const char* entry, SkfModel* m, const float* embedding, const i
   SKF_ENTRY_CHECK(n_valid > 0 && n_valid <= m->cfg.batch, "n_valid must be in [1, batch]");
   SKF_ENTRY_CHECK(max_steps > 0 && max_steps <= m->cfg.seq_len, "max_steps must be in [1, seq_len]");
   SKF_ENTRY_CHECK(m->cfg.do_reconstruction, "the model was built without a decoder (do_reconstruction = 0)");
+  if (rq.pfx && attn_weights) {      // (no public entry takes both)
+    skf_set_error("%s: the attention weights of a completion are not built", entry);
+    return SKF_EUNSUPPORTED;
+  }
   SKF_ENTRY_CHECK(!attn_weights || m->cfg.blind_decoder_mask || expected_len_host,
                   "attention weights of a non-blind decoder need expected_len (with nattn = i + 1 the cached rows differ from the "
                   "reference's last pass)");
@@ -393,14 +427,14 @@ int decode_entry(const char* entry, SkfModel* m, const float* embedding, const i
   rq.smp = sampled ? sampling : nullptr; rq.stream_ids_host = stream_ids_host;
   return run_decode(m, rq, (hipStream_t)stream);
 }
-}  // namespace
 
-extern "C" int skf_model_beam_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
-                                     long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths,
-                                     int* out_len_host, const SkfBeam* beam, skf_stream_t stream) {
+// skf_model_beam_decode, and with `prefix` skf_model_beam_prefix_decode
+int beam_entry(const char* entry, SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+               long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths, int* out_len_host,
+               const SkfBeam* beam, const SkfPrefix* prefix, skf_stream_t stream) {
   // what depends on the configuration alone is answered first (a model that is not bound yet is told the same)
 #define SKF_BEAM_CHECK(cond, msg) \
-  do { if (!(cond)) { skf_set_error("%s: %s (%s)", __func__, msg, #cond); return SKF_EINVAL; } } while (0)
+  do { if (!(cond)) { skf_set_error("%s: %s (%s)", entry, msg, #cond); return SKF_EINVAL; } } while (0)
   SKF_BEAM_CHECK(m, "null model");
   SKF_TRY(skf_beam_check(beam));
   const SkfConfig& c = m->cfg;
@@ -415,11 +449,38 @@ extern "C" int skf_model_beam_decode(SkfModel* m, const float* embedding, const 
   SKF_BEAM_CHECK(c.blind_decoder_mask || expected_len_host, "beam search of a non-blind decoder needs expected_len");
   SKF_BEAM_CHECK(embedding && out_tokens && out_scores && out_lengths, "null embedding or output");
 #undef SKF_BEAM_CHECK
+  if (prefix) SKF_TRY(prefix_check(entry, m, prefix, c.batch / beam->beam_width, max_steps));
   const BeamOut bo{out_tokens, out_scores, out_lengths};
   DecodeRequest rq;
-  rq.bm = beam; rq.bm_out = &bo;
-  return decode_entry(__func__, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out_tokens, out_len_host, nullptr, false,
+  rq.bm = beam; rq.bm_out = &bo; rq.pfx = prefix;
+  return decode_entry(entry, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out_tokens, out_len_host, nullptr, false,
                       nullptr, nullptr, stream, rq);
+}
+}  // namespace
+
+extern "C" int skf_model_beam_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                                     long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths,
+                                     int* out_len_host, const SkfBeam* beam, skf_stream_t stream) {
+  return beam_entry(__func__, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out_tokens, out_scores, out_lengths,
+                    out_len_host, beam, nullptr, stream);
+}
+
+extern "C" int skf_model_beam_prefix_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                                            long long eos, int max_steps, long long* out_tokens, float* out_scores, int* out_lengths,
+                                            int* out_len_host, const SkfBeam* beam, const SkfPrefix* prefix, skf_stream_t stream) {
+  if (!prefix) { skf_set_error("%s: null SkfPrefix", __func__); return SKF_EINVAL; }
+  return beam_entry(__func__, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out_tokens, out_scores, out_lengths,
+                    out_len_host, beam, prefix, stream);
+}
+
+extern "C" int skf_model_prefix_decode(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid, long long sos,
+                                       long long eos, int max_steps, void* out, int* out_len_host, const SkfPrefix* prefix,
+                                       const SkfSampling* sampling, const int* stream_ids_host, skf_stream_t stream) {
+  SKF_TRY(prefix_check(__func__, m, prefix, m ? m->cfg.batch : 0, max_steps));
+  DecodeRequest rq;
+  rq.pfx = prefix;
+  return decode_entry(__func__, m, embedding, expected_len_host, n_valid, sos, eos, max_steps, out, out_len_host, nullptr,
+                      sampling != nullptr, sampling, stream_ids_host, stream, rq);
 }
 
 extern "C" int skf_model_greedy_decode_attn(SkfModel* m, const float* embedding, const int* expected_len_host, int n_valid,

@@ -14,6 +14,11 @@
 // instantiation of the one-launch kernel plus beam_advance_kernel (always: there are no beams on the layer-by-layer path), and the
 // hypotheses are gathered through the last ancestry table into bm_out.
 //
+// pfx (optional, token mode, the one-launch kernel only; checked by the caller): sketch completion (skf_model_prefix_decode,
+// skf_model_beam_prefix_decode; the rule is in include/skf.h).  The prefix and its lengths go to areas of the plan (replicated like the
+// embedding under beam search), the position kernel forces them, and unless pfx->stepwise (or beams) asks for one position launch per
+// forced position, skf_decode_prefill_launch produces their cache rows first and the position loop starts at the shortest prefix.
+//
 // A bf16-trained model decodes the same way, in fp32 on the MASTER weights (only the embedding it starts from comes from the bf16
 // encoder), and only through the one-launch-per-position kernel.  What differs between the two plans is in the view below.
 #include "skf_model_internal.h"
@@ -80,6 +85,10 @@ struct DecodeRun {
   int* limit = nullptr;                      // per-sample key limit of the cross attention (non-blind only)
   SkfBeamState bs{};
   int* stream_ids = nullptr;
+  long long* pfx_tok = nullptr;              // (B, Le) the prefix on the device
+  int* pfx_len = nullptr;
+  int pfx_min = 0, pfx_max = 0;              // the shortest and the longest prefix of the B rows
+  bool prefill = false;
   bool fused = false, use_graph = false;
   SkfDecodeFused fp{};
 
@@ -141,6 +150,25 @@ int DecodeRun::decode_setup() {
     M->dec_stream_host.resize(B);
     for (int b = 0; b < B; ++b) M->dec_stream_host[b] = rq.stream_ids_host ? rq.stream_ids_host[b] : b;
     SKF_HIP(hipMemcpyAsync(stream_ids, M->dec_stream_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  if (rq.pfx) {
+    const int rows = rq.bm ? nsk : B;
+    pfx_tok = M->at<long long>(A.pfx_tok); pfx_len = M->at<int>(A.pfx_len);
+    M->dec_pfx_len_host.assign(rq.pfx->len_host, rq.pfx->len_host + rows);
+    pfx_min = pfx_max = M->dec_pfx_len_host[0];
+    for (int v : M->dec_pfx_len_host) { pfx_min = v < pfx_min ? v : pfx_min; pfx_max = v > pfx_max ? v : pfx_max; }
+    if (pfx_max > 0)
+      SKF_HIP(hipMemcpy2DAsync(pfx_tok, (size_t)Le * 8, rq.pfx->tokens, (size_t)rq.pfx->ld * 8, (size_t)pfx_max * 8, rows,
+                               hipMemcpyDeviceToDevice, s));
+    if (rq.bm) {                                            // one prefix per sketch: in place, and the lengths through the area's second half
+      if (pfx_max > 0) SKF_TRY(skf_beam_replicate(pfx_tok, pfx_tok, nsk, W, (size_t)2 * Le, s));
+      SKF_HIP(hipMemcpyAsync(pfx_len + B, M->dec_pfx_len_host.data(), (size_t)nsk * sizeof(int), hipMemcpyHostToDevice, s));
+      SKF_HIP(hipMemsetAsync(pfx_len, 0, (size_t)B * sizeof(int), s));         // (rows behind n W are not at work)
+      SKF_TRY(skf_beam_replicate(pfx_len, pfx_len + B, nsk, W, 1, s));
+    } else {
+      SKF_HIP(hipMemcpyAsync(pfx_len, M->dec_pfx_len_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    prefill = !rq.bm && !rq.pfx->stepwise && pfx_max > 0;
   }
   // pre_decoder and the cross-attention K/V of every layer: once
   if (V.emb)
@@ -239,6 +267,9 @@ int DecodeRun::fill_fused_params() {
     if (rq.bm) {
       fp.beam = W; fp.beam_rows = nsk * W; fp.anc = bs.anc; fp.cand_lp = bs.cand_lp; fp.cand_tok = bs.cand_tok;
     }
+    if (rq.pfx) {
+      fp.prefix = pfx_tok; fp.prefix_ld = Le; fp.prefix_len = pfx_len; fp.prefilled = prefill ? 1 : 0;
+    }
     SKF_HIP(hipMemsetAsync(fp.ticket, 0, sizeof(int), s));
   }
   // the captured step has constant arguments, no weight output and the greedy selection: with weights requested or with
@@ -275,8 +306,16 @@ int DecodeRun::issue_position() {
 }
 
 int DecodeRun::decode_positions() {
-  int done = -1, steps_run = 0;
-  for (int i = 0; i < rq.max_steps; ++i) {
+  int done = -1, steps_run = 0, first = 0;
+  if (prefill) {       // the cache rows of every forced position; the loop starts behind the prefix all rows share
+    SKF_TRY(skf_decode_prefill_launch(fp, pfx_max, s));
+    first = steps_run = pfx_min;
+    if (first > 0) {   // the stop test of the positions skipped
+      SKF_HIP(hipMemcpyAsync(&done, done_step, sizeof(int), hipMemcpyDeviceToHost, s));
+      SKF_HIP(hipStreamSynchronize(s));
+    }
+  }
+  for (int i = first; i < rq.max_steps && done < 0; ++i) {
     SKF_TRY(issue_position());
     steps_run = i + 1;
     if ((i & 7) == 7 || i + 1 == rq.max_steps) {            // the reference syncs every token; every 8th is enough here
@@ -304,6 +343,12 @@ int DecodeRun::decode_positions() {
 
 int run_decode(SkfModel* M, const DecodeRequest& rq, hipStream_t s) {
   DecodeRun R(M, rq, s);
+  if (rq.pfx && !rq.bm && R.V.layerwise &&
+      ((M->flags & SKF_MODEL_DECODE_LAYERWISE) || !skf_decode_fused_supported(R.d, R.H, R.F, R.Le, R.N, R.Vout))) {
+    skf_set_error("a prefix is served by the one-launch position kernel only: not with SKF_MODEL_DECODE_LAYERWISE, nor at dimensions "
+                  "that kernel does not take (d <= 512, <= 8 layers, head size 16 / 32 / 64)");
+    return SKF_EUNSUPPORTED;
+  }
   if (!R.V.layerwise)
     SKF_CHECK_ARG(skf_decode_fused_supported(R.d, R.H, R.F, R.Le, R.N, R.Vout), "greedy decode of a bf16 model needs the one-launch decoder (d <= 512, <= 8 layers)");
   SKF_TRY(R.decode_setup());

@@ -71,6 +71,9 @@ struct DecodeAreas {
   // beam search (skf_beam.hip), rows g W + k: two ancestry tables (2, B, L + 1) ints; the W <= 8 candidates of a row, (B, 8) log p
   // then (B, 8) tokens; [B] scores, [B] finished flags, [B] lengths
   size_t anc = 0, cand = 0, beam = 0;
+  // prefix-forced decoding: the prefix tokens (B, L) int64; [B] lengths, then [B] the lengths of a beam decode's sketches on their way
+  // to the rows (the prefill keeps its intermediate rows in the caches themselves)
+  size_t pfx_tok = 0, pfx_len = 0;
 };
 
 struct EncAct { size_t x_in, qkv, o, z1, st1, astats, x1, h, z2, st2, x2, hbits, img[2], img_o, img_qkv, img_of; };   // img: pre-split ffn weight images (forward, backward); img_o: Wo^T; img_qkv: this layer's Wqkv (read by the PREVIOUS layer's feed-forward launch)
@@ -259,6 +262,7 @@ struct SkfModel {
   hipGraphExec_t g_fb = nullptr, g_opt = nullptr, g_dec = nullptr;   // g_dec: one greedy-decode step
   long long dec_dyn_host[2] = {0, 0};
   std::vector<int> dec_stream_host;  // stream ids of a sampled decode on their way to the device
+  std::vector<int> dec_pfx_len_host; // prefix lengths of a completion on their way to the device
   float g_opt_scale = 0.f;
   skf_model_detail::SideSched sched;                   // the side stream and everything that orders the two streams
   hipEvent_t inputs_staged = nullptr;                         // recorded behind the staging copies of every call (skf_model_wait_inputs_staged)
@@ -339,8 +343,8 @@ int run_backward(SkfModel* M, hipStream_t s);
 int issue_embed_sorts(SkfModel* M, hipStream_t s);
 
 // ------------------------------------------------------------------ skf_model_decode.hip
-// One reconstruction call.  Optional: attn (attention weights), smp + stream_ids_host (a sampled decode), bm + bm_out (beam search);
-// see run_decode.
+// One reconstruction call.  Optional: attn (attention weights), smp + stream_ids_host (a sampled decode), bm + bm_out (beam search),
+// pfx (a prefix to continue: sketch completion); see run_decode.
 struct BeamOut { long long* tokens; float* scores; int* lengths; };
 struct DecodeRequest {
   const float* embedding = nullptr;
@@ -355,6 +359,7 @@ struct DecodeRequest {
   const int* stream_ids_host = nullptr;
   const SkfBeam* bm = nullptr;
   const BeamOut* bm_out = nullptr;
+  const SkfPrefix* pfx = nullptr;            // checked by the caller (prefix_check)
 };
 int run_decode(SkfModel* M, const DecodeRequest& rq, hipStream_t s);
 

@@ -134,6 +134,9 @@ DecodeAreas take_decode_areas(Bump& b, const SkfConfig& c, bool own_cross) {
   A.anc = b.take(2 * B * (L + 1) * sizeof(int));
   A.cand = b.take(2 * B * SKF_BEAM_MAX * sizeof(float));
   A.beam = b.take(3 * B * sizeof(int));
+  if (!c.continuous) {
+    A.pfx_tok = b.take(B * L * 8); A.pfx_len = b.take(2 * B * sizeof(int));
+  }
   return A;
 }
 
@@ -149,6 +152,7 @@ bool decode_areas_ok(const DecodeAreas& A, size_t plan_bytes) {
     o.push_back(A.cache[i]);
   }
   for (size_t v : {A.img, A.mask, A.flags, A.limit, A.dyn, A.anc, A.cand, A.beam}) o.push_back(v);
+  if (A.pfx_tok) for (size_t v : {A.pfx_tok, A.pfx_len}) o.push_back(v);      // (token models)
   if (o[0] == 0 || o.back() + 64 > plan_bytes || (!A.kv2.empty() && A.kv2.size() != A.cache.size())) return false;
   for (size_t i = 1; i < o.size(); ++i)
     if (o[i] <= o[i - 1]) return false;

@@ -152,6 +152,56 @@ def check_beam(beam_width, length_alpha, vocab_size=None, batch=None):
         raise ValueError("length_alpha must be a finite number >= 0 (got %r)" % (length_alpha,))
 
 
+COMPLETION_NEEDS_TOKENS = ("sketch completion is built for token models: a prefix is a sequence of tokens, and continuous (stroke-5) "
+                           "prefixes are not built")
+
+
+def check_prefix(prefix, prefix_len, rows, max_steps, vocab_size, eos=0):
+    """The prefix of a completion (include/skf.h: prefix-forced decoding) as the C entries take it: ``(tokens, lens)`` with tokens a
+    (rows, ld) int64 array - or device tensor when ``prefix`` is one - and lens (rows,) int32, 0 <= lens <= max_steps, ld >= 1.
+    prefix: at most ``rows`` rows of at least max(len) tokens; prefix_len: one length per given row, or None = each row's tokens up to
+    (not including) its first ``eos`` or PAD (0).  Rows beyond the given ones take row 0's prefix and length, so that a short batch
+    does not pull the shortest prefix - where the position loop starts - down to 0.  ValueError for a length outside [0, max_steps]
+    or beyond the prefix's columns, and for a host-side prefix with a token outside [0, vocab_size) among the forced ones (a device
+    tensor is trusted, like every device input; the kernels treat such a token as PAD)."""
+    on_device = torch.is_tensor(prefix) and prefix.is_cuda
+    host = prefix.detach().cpu().numpy() if torch.is_tensor(prefix) else np.asarray(prefix)
+    if host.ndim != 2 or not 1 <= host.shape[0] <= rows:
+        raise ValueError("prefix must be a 2-D array of 1 .. %d rows (got shape %r)" % (rows, tuple(host.shape)))
+    if not np.issubdtype(host.dtype, np.integer):
+        raise ValueError("prefix must hold integer tokens (got dtype %s)" % host.dtype)
+    host = host.astype(np.int64)
+    n, width = host.shape
+    if prefix_len is None:
+        stop = (host == int(eos)) | (host == 0)
+        lens = np.where(stop.any(axis=1), stop.argmax(axis=1), width).astype(np.int64)
+    else:
+        lens = np.asarray(prefix_len).astype(np.int64).reshape(-1)
+        if len(lens) != n:
+            raise ValueError("prefix_len must give one length per prefix row (%d rows, %d lengths)" % (n, len(lens)))
+    if (lens < 0).any() or (lens > max_steps).any():
+        raise ValueError("a prefix length must be in [0, max_steps = %d] (got %d .. %d)" % (max_steps, lens.min(), lens.max()))
+    if (lens > width).any():
+        raise ValueError("a prefix length exceeds the prefix's %d columns (got %d)" % (width, lens.max()))
+    forced = np.arange(width)[None, :] < lens[:, None]
+    if not on_device and forced.any():
+        lo, hi = int(host[forced].min()), int(host[forced].max())
+        if lo < 0 or hi >= vocab_size:
+            raise ValueError("prefix token out of range: values span [%d, %d], valid range is [0, %d)" % (lo, hi, vocab_size))
+    ld = max(width, 1)
+    all_lens = np.full(rows, lens[0], dtype=np.int32)
+    all_lens[:n] = lens
+    if on_device:
+        tokens = prefix.new_zeros((rows, ld), dtype=torch.int64)
+        tokens[:n, :width] = prefix
+        tokens[n:, :width] = prefix[0]
+    else:
+        tokens = np.zeros((rows, ld), dtype=np.int64)
+        tokens[:n, :width] = host
+        tokens[n:, :width] = host[0]
+    return tokens, all_lens
+
+
 class TrainEngine:
     """One replica of the sketch-transformer-tf2 train step on one GPU."""
 
@@ -345,18 +395,39 @@ class TrainEngine:
         finally:
             self._leave()
 
+    def _prefix(self, prefix, prefix_len, prefill, rows, max_steps, eos):
+        """check_prefix, then the prefix on the device and the SkfPrefix that points at it -> (SkfPrefix, what must stay alive)."""
+        if self.cfg.continuous:
+            raise ValueError(COMPLETION_NEEDS_TOKENS)
+        tokens, lens = check_prefix(prefix, prefix_len, rows, max_steps, self.cfg.vocab_size, eos)
+        dev = torch.as_tensor(tokens).to(self.device).contiguous()
+        arr = (C.c_int * rows)(*lens.tolist())
+        pf = _lib.SkfPrefix(tokens=dev.data_ptr(), ld=int(dev.shape[1]), len_host=arr, stepwise=0 if prefill else 1)
+        return pf, (dev, arr)
+
     def greedy_decode(self, embedding=None, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None,
-                      with_attn_weights=False):
+                      with_attn_weights=False, prefix=None, prefix_len=None, prefill=True):
         """predict_from_embedding (models/sketchformer.py:255-311) with a K/V cache.  embedding: (B,d) array / tensor
         or None (= the model's own 'embedding' buffer, i.e. right after ``encode``).  Returns the reconstruction as a
         host array: (n_valid, T) int32 tokens incl. the SOS column, or (n_valid, T, 5) float32 stroke-5 rows.
         with_attn_weights: return ``(recon, weights)`` instead, weights = the reference's res['attn_weights']
         (builders/layers/transformer.py:328-344): {'decoder_layer{i}_block1': (n_valid, H, T-1, T-1),
         'decoder_layer{i}_block2': (n_valid, H, T-1, seq_len)} float32, the last decoder pass over recon[:, :T-1]
-        (skf_model_greedy_decode_attn).  A non-blind decoder needs expected_len for it (ValueError otherwise)."""
+        (skf_model_greedy_decode_attn).  A non-blind decoder needs expected_len for it (ValueError otherwise).
+        prefix, prefix_len: sketch completion (skf_model_prefix_decode; the rule is in include/skf.h, the arguments in
+        ``check_prefix``): the first prefix_len[b] tokens of row b are given and the decoder goes on from there; the result holds
+        them in columns 1 .. prefix_len[b].  prefill=True produces the cache rows of the given positions in num_layers launches
+        before the position loop, False steps through them one launch each; the results are the same bits.  Token models only,
+        and not together with with_attn_weights (ValueError)."""
         B, L = self.cfg.batch, self.cfg.seq_len
         n_valid = B if n_valid is None else int(n_valid)
         max_steps = L if max_steps is None else int(max_steps)
+        if prefix is not None:
+            if with_attn_weights:
+                raise ValueError("the attention weights of a completion are not built: with_attn_weights and prefix exclude each other")
+            pf, keep = self._prefix(prefix, prefix_len, prefill, B, max_steps, eos)
+            return self._decode_call("skf_model_prefix_decode", embedding, expected_len, n_valid, sos, eos, max_steps, C.byref(pf),
+                                     None, None)[0]
         if with_attn_weights and not self.cfg.blind_decoder_mask and expected_len is None:
             raise ValueError("attention weights of a non-blind decoder need expected_len: with nattn = i + 1 the rows decoded "
                              "earlier were masked differently from the reference's last pass")
@@ -375,12 +446,13 @@ class TrainEngine:
         return res, weights
 
     def sample_decode(self, embedding=None, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None,
-                      temperature=1.0, top_k=0, top_p=1.0, seed=0, stream_ids=None):
+                      temperature=1.0, top_k=0, top_p=1.0, seed=0, stream_ids=None, prefix=None, prefix_len=None, prefill=True):
         """greedy_decode with every token drawn instead of maximised (skf_model_sample_decode; the selection rule is in
         include/skf.h): logits / temperature, then the top_k largest (0 = off; ties at the threshold all stay), then the nucleus
         of mass top_p (1 = off), then an inverse-CDF draw in index order with u = skf_sample_uniform(seed, stream_ids[b], position).
         stream_ids: one integer per batch row (default 0 .. B-1); a row's draws depend on its stream id, not on its batch slot.
-        Token models only (ValueError for a continuous one).  Returns (n_valid, T) int32 incl. the SOS column, like greedy_decode."""
+        Token models only (ValueError for a continuous one).  Returns (n_valid, T) int32 incl. the SOS column, like greedy_decode.
+        prefix, prefix_len, prefill: as in greedy_decode; a position keeps its uniform whether or not positions before it were given."""
         B, L = self.cfg.batch, self.cfg.seq_len
         if self.cfg.continuous:
             raise ValueError(SAMPLING_NEEDS_TOKENS)
@@ -396,6 +468,10 @@ class TrainEngine:
             arr[:len(v)] = v
             sid = (C.c_int * B)(*arr.tolist())
         smp = _lib.SkfSampling(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xffffffff)
+        if prefix is not None:
+            pf, keep = self._prefix(prefix, prefix_len, prefill, B, max_steps, eos)
+            return self._decode_call("skf_model_prefix_decode", embedding, expected_len, n_valid, sos, eos, max_steps, C.byref(pf),
+                                     C.byref(smp), sid)[0]
         return self._decode_call("skf_model_sample_decode", embedding, expected_len, n_valid, sos, eos, max_steps, C.byref(smp), sid)[0]
 
     def beam_decode(self, embedding, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None, beam_width=4,
@@ -405,7 +481,21 @@ class TrainEngine:
         expected_len: one length per sketch, required by a non-blind decoder.  Returns (tokens (n_valid, W, T) int32 incl. the SOS
         column, scores (n_valid, W) float32: the sums of log p, lengths (n_valid, W) int32: the position of a hypothesis's EOS, or
         the positions decoded when it has none); the hypotheses of a sketch are ordered by score / ((5 + length) / 6)^length_alpha,
-        best first.  Token models only (ValueError for a continuous one)."""
+        best first.  Token models only (ValueError for a continuous one).  ``beam_complete`` is the same search behind a prefix."""
+        return self._beam_search(embedding, expected_len, n_valid, sos, eos, max_steps, beam_width, length_alpha, None, None)
+
+    def beam_complete(self, embedding, prefix, prefix_len=None, expected_len=None, n_valid=None, sos=0, eos=0, max_steps=None,
+                      beam_width=4, length_alpha=0.0):
+        """beam_decode behind a prefix (skf_model_beam_prefix_decode; the rule is in include/skf.h): one prefix per sketch, given like
+        greedy_decode's (``check_prefix``); every hypothesis starts with its sketch's prefix and the scores are
+        log p(continuation | prefix, embedding).  Beams always step through the prefix: there is no prefill under an ancestry table.
+        Same returns as beam_decode."""
+        if prefix is None:
+            raise ValueError("beam_complete needs a prefix; beam_decode searches from the start symbol")
+        return self._beam_search(embedding, expected_len, n_valid, sos, eos, max_steps, beam_width, length_alpha, prefix, prefix_len)
+
+    def _beam_search(self, embedding, expected_len, n_valid, sos, eos, max_steps, beam_width, length_alpha, prefix, prefix_len):
+        """beam_decode (prefix None) and beam_complete: checks, buffers, the C entry, the host copies"""
         B, L = self.cfg.batch, self.cfg.seq_len
         if self.cfg.continuous:
             raise ValueError(BEAM_NEEDS_TOKENS)
@@ -425,10 +515,17 @@ class TrainEngine:
         lengths = torch.zeros(n, W, dtype=torch.int32, device=self.device)
         n_out = C.c_int(0)
         bm = _lib.SkfBeam(beam_width=W, length_alpha=float(length_alpha))
+        pf = None
+        if prefix is not None:
+            pf, keep = self._prefix(prefix, prefix_len, False, n, max_steps, eos)
         self._enter()
         try:
-            _lib.call("skf_model_beam_decode", self.handle, self._p(e), lim, n_valid, int(sos), int(eos), max_steps, self._p(out),
-                      self._p(scores), self._p(lengths), C.byref(n_out), C.byref(bm), self._stream())
+            if pf is not None:
+                _lib.call("skf_model_beam_prefix_decode", self.handle, self._p(e), lim, n_valid, int(sos), int(eos), max_steps,
+                          self._p(out), self._p(scores), self._p(lengths), C.byref(n_out), C.byref(bm), C.byref(pf), self._stream())
+            else:
+                _lib.call("skf_model_beam_decode", self.handle, self._p(e), lim, n_valid, int(sos), int(eos), max_steps, self._p(out),
+                          self._p(scores), self._p(lengths), C.byref(n_out), C.byref(bm), self._stream())
         finally:
             self._leave()
         self.synchronize()

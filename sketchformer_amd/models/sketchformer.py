@@ -500,6 +500,128 @@ class Transformer(BaseModel, TransformerMetricsMixin):
         return self.sample_from_embedding(self._embed_on_device(x), n_samples=n_samples, temperature=temperature, top_k=top_k,
                                           top_p=top_p, seed=seed, expected_len=tlen)
 
+    def complete_from_embedding(self, emb, prefix, prefix_len=None, expected_len=None, mode='greedy', n_samples=1, temperature=1.0,
+                                top_k=0, top_p=1.0, seed=0, beam_width=4, length_alpha=0.0, prefill=True):
+        """Sketch completion: the decoder continues the first prefix_len[i] tokens of ``prefix`` row i from embedding i (the rule
+        is in include/skf.h: prefix-forced decoding).  emb: any number n of embeddings, a host array or a device tensor (n, E);
+        prefix: (n, >= max(prefix_len)) tokens WITHOUT the start symbol; prefix_len=None: each row's tokens before its first EOS or
+        PAD.  mode: 'greedy'; 'sample' (n_samples draws per sketch with temperature / top_k / top_p / seed, random streams as in
+        sample_from_embedding); 'beam' (the beam_width most likely continuations, ordered like beam_search_from_embedding's).  The
+        rows are decoded in chunks like sample_from_embedding / beam_search_from_embedding, and every column after a row's first
+        EOS is 0, so a row depends neither on n, nor on its chunk, nor on its neighbours.  expected_len: per embedding, non-blind
+        models only (required for 'beam').  prefill: engine.greedy_decode's - the cache rows of the prefixes in num_layers launches
+        (it pays when the rows of a chunk share a long prefix) or, False, one position launch per prefix token (the better setting
+        for ragged prefixes: the position loop starts at a chunk's SHORTEST prefix); the results are the same bits; beams always step.
+        Returns {'recon': (n, seq_len + 1) int32 ['sample': (n, n_samples, seq_len + 1); 'beam': (n, W, seq_len + 1)] with the
+        prefix in columns 1 .. prefix_len, 'prefix_len': (n,) int32, 'class': as the mode's own method returns it, and for
+        'beam' also 'score' (n, W) float32 = log p(continuation | prefix, embedding) and 'length' (n, W) int32}."""
+        import torch
+        from .. import engine as _engine
+        if not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        if self.dataset.hps['use_continuous_data']:
+            raise ValueError(_engine.COMPLETION_NEEDS_TOKENS)
+        if mode not in ('greedy', 'sample', 'beam'):
+            raise ValueError("mode must be 'greedy', 'sample' or 'beam' (got %r)" % (mode,))
+        eng = self.engine
+        if mode == 'sample':
+            _engine.check_sampling(temperature, top_k, top_p)
+        if mode == 'beam':
+            _engine.check_beam(beam_width, length_alpha, eng.cfg.vocab_size, eng.cfg.batch)
+        n_samples = int(n_samples) if mode == 'sample' else 1
+        if n_samples < 1:
+            raise ValueError("n_samples must be >= 1")
+        if not torch.is_tensor(emb):
+            emb = torch.as_tensor(np.asarray(emb, dtype=np.float32))
+        emb = emb.to(eng.device, dtype=torch.float32)
+        if emb.dim() == (1 if self.hps['lowerdim'] else 2):       # one embedding: (E,) - or (L, d) without a bottleneck
+            emb = emb[None]
+        n = emb.shape[0]
+        if n == 0:
+            raise ValueError("no embedding given")
+        sos, eos = self._sos_eos()
+        prefix = np.asarray(prefix.cpu() if torch.is_tensor(prefix) else prefix)
+        if prefix.ndim == 1:
+            prefix = prefix[None]
+        if prefix.ndim != 2 or prefix.shape[0] != n:
+            raise ValueError("prefix must hold one row of tokens per embedding")
+        # the whole set at once: ranges, and the derived lengths (the chunks below pass explicit lengths)
+        prefix, plen = _engine.check_prefix(prefix, prefix_len, n, self.seq_len, eng.cfg.vocab_size, eos)
+        if self.hps['blind_decoder_mask']:
+            expected_len = None                                   # "will be ignored if blind_decoder_mask=True"
+        elif expected_len is None:
+            if mode == 'beam':
+                raise ValueError("beam search of a non-blind decoder needs expected_len")
+        else:
+            expected_len = np.asarray(expected_len).astype(np.int32).reshape(-1)
+            if len(expected_len) != n:
+                raise ValueError("expected_len must hold one length per embedding")
+
+        def lim(i, m, rep=1):
+            return None if expected_len is None else np.repeat(expected_len, rep)[i:i + m]
+
+        out = {'prefix_len': plen.astype(np.int32)}
+        if mode == 'beam':
+            W = int(beam_width)
+            recon, (score, length), cls = self._beam_chunks(emb, lambda chunk, i, m: eng.beam_complete(
+                chunk, prefix[i:i + m], plen[i:i + m], expected_len=lim(i, m), n_valid=m, sos=sos, eos=eos, beam_width=W,
+                length_alpha=length_alpha), eng.cfg.batch // W, W)
+            ended = np.cumsum(recon[:, :, 1:] == eos, axis=2) > 0
+            recon[:, :, 2:][ended[:, :, :-1]] = 0
+            out.update(recon=recon, score=score, length=length)
+            out['class'] = cls
+            return out
+        rows = emb.repeat_interleave(n_samples, dim=0)
+        rp, rl = np.repeat(prefix, n_samples, axis=0), np.repeat(plen, n_samples)
+        if mode == 'sample':
+            def decode(chunk, i, m):
+                return eng.sample_decode(chunk, expected_len=lim(i, m, n_samples), n_valid=m, sos=sos, eos=eos, temperature=temperature,
+                                         top_k=top_k, top_p=top_p, seed=seed, stream_ids=np.arange(i, i + m), prefix=rp[i:i + m],
+                                         prefix_len=rl[i:i + m], prefill=prefill)
+        else:
+            def decode(chunk, i, m):
+                return eng.greedy_decode(chunk, expected_len=lim(i, m), n_valid=m, sos=sos, eos=eos, prefix=rp[i:i + m],
+                                         prefix_len=rl[i:i + m], prefill=prefill)
+        recon, cls = self._decode_in_chunks(rows, decode)
+        ended = np.cumsum(recon[:, 1:] == eos, axis=1) > 0        # from the first EOS on (column 0 is the start symbol)
+        recon[:, 2:][ended[:, :-1]] = 0
+        if mode == 'sample':
+            recon = recon.reshape(n, n_samples, self.seq_len + 1)
+            cls = None if cls is None else cls.reshape(n, n_samples)
+        out.update(recon=recon)
+        out['class'] = cls
+        return out
+
+    def complete(self, partial_seq, **kw):
+        """complete_from_embedding on the embeddings of partial_seq (any number of model-ready token sequences: the part of a sketch
+        drawn so far, closed by EOS): the embeddings go from the encoder to the decoder on the device, the prefix of a row is its
+        tokens behind the start symbol and before its EOS, and a non-blind model decodes with the partial's length as expected_len, like predict.  kw: mode,
+        n_samples, temperature, top_k, top_p, seed, beam_width, length_alpha, prefill."""
+        from .. import engine as _engine
+        if not self.hps['do_reconstruction']:
+            raise ValueError("do_reconstruction is off")
+        if self.dataset.hps['use_continuous_data']:
+            raise ValueError(_engine.COMPLETION_NEEDS_TOKENS)
+        if not self.hps['lowerdim']:
+            raise ValueError("complete needs lowerdim > 0 (the bottleneck embedding); without one, pass the (n, L, d) encoder "
+                             "outputs to complete_from_embedding")
+        for k in ('prefix', 'prefix_len', 'expected_len'):
+            if k in kw:
+                raise TypeError("complete() derives %s from partial_seq; use complete_from_embedding to set it" % k)
+        x = np.asarray(partial_seq)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim == 3 and x.shape[-1] == 1:
+            x = x[..., 0]
+        tlen = None if self.hps['blind_decoder_mask'] else np.sum(x > 0, axis=-1).reshape(-1)
+        # a model-ready row is [SOS] body [EOS] PAD...: the start symbol is the decoder's column 0, the prefix what follows it
+        sos = self._sos_eos()[0]
+        prefix = np.zeros_like(x)
+        for i, row in enumerate(x):
+            body = row[1:] if len(row) and row[0] == sos else row
+            prefix[i, :len(body)] = body
+        return self.complete_from_embedding(self._embed_on_device(x), prefix[:, :self.seq_len], prefix_len=None, expected_len=tlen, **kw)
+
     def score(self, inp_seq, tar_seq=None):
         """Teacher-forced scoring of any number of sequences (engine.score; the rule is in include/skf.h): how likely tar_seq is
         under the model that has encoded inp_seq.  tar_seq=None scores every sketch against itself (the autoencoding objective);
