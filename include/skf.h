@@ -1174,6 +1174,43 @@ int skf_dtw_f32(const float* xy_a, long long lda, const int* n_a, int Na, int Ta
 int skf_sequence_score(const void* logits, int is_bf16, int ld, int B, int T, int V, const long long* target, int tgt_ld, int tgt_off,
                        long long eos, float* tok_logp, int* tok_rank, float* seq_logp, int* seq_len, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Order-free shape distances (Chamfer, Hausdorff)
+ * The reference has nothing in this place.  The alignment distances above compare sequences - the same ink in another stroke order
+ * is far away - and the raster overlap is tied to a resolution and a line width.  This entry measures how far the INK of one sketch
+ * lies from the ink of another: per pair the mean and the maximum, both ways, of the distance from the samples of one sketch to the
+ * nearest primitive of the other; the Chamfer and the Hausdorff distance follow from the four numbers.  One workgroup keeps sketch a
+ * resident in LDS against a block of rows of b and computes both directions where both are resident; the (samples x primitives)
+ * table never exists.  Nothing here allocates, synchronises with the host or uses a floating-point atomic; two calls on the same
+ * inputs agree bit for bit and a pair's result does not depend on the rest of the batch.
+ * skf_shape_distance_f32.  A sketch is what skf_sketch_points writes: xy (T, 2) fp32 absolute positions, pen (T) bytes (1 = the pen
+ *   lifts after this point) and n points, clamped to [0, T] inside the kernel and never trusted as an index; what lies behind n is
+ *   never read.  An empty sketch (n = 0) stands for the single point (0, 0) with its pen lifted, as for skf_dtw_f32.
+ *   Primitives of a sketch: every point i < n is a dot p[i]; every i > 0 with pen[i-1] == 0 is in addition the segment a = p[i-1] to
+ *     b = p[i], with e = b - a, len2 = ex * ex + ey * ey, inv = len2 > 0 ? 1.0f / len2 : 0.0f (a correctly rounded division).
+ *   Samples of a sketch, for samples_per_segment = S in [1, 16]: every point p[i], used exactly; every segment adds the S - 1
+ *     interior samples a + t * e, t = (float)j / (float)S, j = 1 .. S - 1.  count = n + (S - 1) * segments, or 1 for an empty sketch.
+ *   Distance of a sample s to a sketch: d2 = the minimum over the sketch's primitives of
+ *     dot:      qx * qx + qy * qy, q = s - p;
+ *     segment:  px = sx - ax, py = sy - ay; dot = px * ex + py * ey; t = min(max(dot * inv, 0), 1); rx = px - t * ex, ry = py - t * ey;
+ *               rx * rx + ry * ry;
+ *     then d = sqrt(d2), correctly rounded.  Every operation is rounded to fp32 on its own, no fused multiply-add; the minimum is
+ *     exact, so the order of the primitives plays no part.
+ *   Directed results a -> b: max_ab = the largest d over the samples of a (exact);
+ *     mean_ab = (float)(((double)Q / 16777216.0) / (double)count_a), Q = the int64 sum over the samples of a of
+ *     (long long)floor((double)d * 16777216.0): an exact, order-free fixed-point sum (the device of skf_sample.h's masses).
+ *   out holds four fp32 per pair: (mean_ab, mean_ba, max_ab, max_ba).  Chamfer = 0.5f * (mean_ab + mean_ba) and
+ *     Hausdorff = max(max_ab, max_ba) are taken by the caller.  A float32 numpy restatement matches all four BIT FOR BIT.
+ *   Contract (stated, not checked): the coordinates are finite, |c| <= 2^20, and no segment is so short that len2 underflows to a
+ *     subnormal whose reciprocal is infinite.  A NaN spoils the results of its own pairs only.
+ *   cross == 0: Na == Nb, out is (Na, 4) and pairs row i of a with row i of b.  cross == 1: out is (Na, Nb, 4) row-major.
+ *   lda, ldb: floats from row to row of xy; ldpa, ldpb: bytes from row to row of pen.
+ *   Limits (SKF_EINVAL): Na, Nb >= 1; 1 <= Ta, Tb <= SKF_ALIGN_MAX_LEN; lda >= 2 Ta, ldb >= 2 Tb, ldpa >= Ta, ldpb >= Tb; xy_a, xy_b,
+ *     n_a, n_b 4-byte and out 16-byte aligned; S in [1, 16]; cross in {0, 1}; cross == 0 with Na != Nb; cross == 1 with
+ *     Na * Nb * 4 >= 2^31. */
+int skf_shape_distance_f32(const float* xy_a, long long lda, const unsigned char* pen_a, long long ldpa, const int* n_a, int Na, int Ta,
+                           const float* xy_b, long long ldb, const unsigned char* pen_b, long long ldpb, const int* n_b, int Nb, int Tb,
+                           int samples_per_segment, int cross, float* out, skf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,6 +305,7 @@ SIGNATURES = {
     "skf_edit_distance_i64": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
     "skf_dtw_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
     "skf_sequence_score": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _L, _P, _P, _P, _P, _P]),
+    "skf_shape_distance_f32": (_I, [_P, _L, _P, _L, _P, _I, _I, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

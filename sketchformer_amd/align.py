@@ -3,7 +3,11 @@ distance computed on the device (skf_align.hip through ops.edit_distance / ops.d
 unit-cost Levenshtein distance (the token error rate once divided by the longer length), point rows by dynamic time warping
 under the Euclidean distance.  Both are also the classical sketch-retrieval baselines: a (Q, G) matrix of either, ranked by
 ``rank_by_distance``, goes into retrieval.retrieval_scores like a ranking of embeddings.  The reference has neither; it looks at
-reconstructions (metrics/samples.py).  DESIGN.md section 3n."""
+reconstructions (metrics/samples.py).  DESIGN.md section 3n.
+
+Beside them the two order-free distances between the ink of two sketches, ``sketch_chamfer`` and ``sketch_hausdorff``
+(skf_chamfer.hip through ops.shape_distance): the mean and the worst distance from one drawing to the nearest ink of the other.
+They do not see in which order or direction the strokes were drawn.  DESIGN.md section 3s."""
 import numpy as np
 
 
@@ -76,6 +80,39 @@ def sketch_dtw(a, b, kind='stroke3', tokenizer=None, cross=False, normalize=True
     ca, cb = na.clamp(min=1), nb.clamp(min=1)
     steps = (ca[:, None] + cb[None, :]) if cross else (ca + cb)
     return d.to(torch.float64) / steps.to(torch.float64)
+
+
+def _shape_parts(a, b, kind, tokenizer, cross, samples_per_segment, center, lengths_a, lengths_b):
+    """(mean a->b, mean b->a, max a->b, max b->a) per pair (ops.shape_distance) of sketches in any form raster.points takes"""
+    from . import ops, raster
+    xa, pa, na, ba = raster.points(a, kind, tokenizer, lengths_a)
+    xb, pb, nb, bb = raster.points(b, kind, tokenizer, lengths_b, device=xa.device)
+    if center:                                                     # the bounding-box centre, float32, on the device
+        xa = xa - ((ba[:, :2] + ba[:, 2:]) * 0.5)[:, None, :]
+        xb = xb - ((bb[:, :2] + bb[:, 2:]) * 0.5)[:, None, :]
+    return ops.shape_distance(xa, pa, na, xb, pb, nb, samples_per_segment=samples_per_segment, cross=cross)
+
+
+def sketch_chamfer(a, b, kind='stroke3', tokenizer=None, cross=False, samples_per_segment=4, center=False, lengths_a=None,
+                   lengths_b=None, return_parts=False):
+    """The Chamfer distance between the ink of sketches a and b, each in any form raster.points takes (as for sketch_dtw): the mean
+    distance from the samples of one sketch - its points and samples_per_segment - 1 positions inside every segment - to the nearest
+    dot or segment of the other, averaged over both directions.  It does not depend on the order or the direction of the strokes,
+    on a resolution or on a line width.  float32 (Na,) for the pairs, (Na, Nb) with cross=True.  center: each sketch is moved so that
+    the centre of its bounding box lies at the origin first (sketches start at their first pen position: retrieval needs this; an
+    original and its reconstruction share a frame and do not).  return_parts: the (..., 4) tensor of ops.shape_distance instead.
+    An empty sketch stands for the single point (0, 0).  Device tensors out."""
+    parts = _shape_parts(a, b, kind, tokenizer, cross, samples_per_segment, center, lengths_a, lengths_b)
+    return parts if return_parts else 0.5 * (parts[..., 0] + parts[..., 1])
+
+
+def sketch_hausdorff(a, b, kind='stroke3', tokenizer=None, cross=False, samples_per_segment=4, center=False, lengths_a=None,
+                     lengths_b=None, return_parts=False):
+    """The Hausdorff distance between the ink of sketches a and b: the largest distance from a sample of one sketch to the nearest
+    dot or segment of the other, over both directions.  Arguments and shapes as for sketch_chamfer."""
+    import torch
+    parts = _shape_parts(a, b, kind, tokenizer, cross, samples_per_segment, center, lengths_a, lengths_b)
+    return parts if return_parts else torch.maximum(parts[..., 2], parts[..., 3])
 
 
 def rank_by_distance(D, k, exclude_rows=None):

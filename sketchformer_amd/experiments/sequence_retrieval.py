@@ -1,8 +1,11 @@
 """sequence-retrieval: the classical baselines of sketch retrieval - rank the sketches of one split against those of another by
-an alignment distance between the sequences themselves, the token edit distance or dynamic time warping over the pen positions,
-and score the ranking by class label exactly as sketch-retrieval scores the learned embedding (mAP@k, precision@k, recall@1).
-Every (query, gallery) pair is one dynamic program on the device (sketchformer_amd/align.py); the gallery walks through in blocks
-so the distance matrix is built a slab at a time.  Uses model.dataset only; writes one .npz with the keys of retrieval.npz."""
+a distance between the drawings themselves and score the ranking by class label exactly as sketch-retrieval scores the learned
+embedding (mAP@k, precision@k, recall@1).  distance=edit / dtw: an alignment distance between the sequences, the token edit
+distance or dynamic time warping over the pen positions, one dynamic program per (query, gallery) pair.  distance=chamfer /
+hausdorff: an order-free distance between the ink, the mean or the worst nearest-ink distance with samples_per_segment samples
+per segment, every sketch centred on its bounding box first (a sketch starts at its first pen position).  All on the device
+(sketchformer_amd/align.py); the gallery walks through in blocks so the distance matrix is built a slab at a time.  Uses
+model.dataset only; writes one .npz with the keys of retrieval.npz."""
 import os
 
 import numpy as np
@@ -19,7 +22,7 @@ class SequenceRetrieval(Experiment):
     @classmethod
     def specific_default_hparams(cls):
         return hp.HParams(distance='dtw', gallery_set='test', query_set='valid', top_k=100, n_queries=256, n_gallery=4096,
-                          gallery_block=1024, target_file='sequence_retrieval.npz')
+                          gallery_block=1024, target_file='sequence_retrieval.npz', samples_per_segment=4)
 
     @staticmethod
     def _subsample(n_rows, n):
@@ -32,8 +35,8 @@ class SequenceRetrieval(Experiment):
         import torch
         from .. import align
         h = self.hps
-        if h['distance'] not in ('edit', 'dtw'):
-            raise ValueError("sequence-retrieval: distance must be 'edit' or 'dtw' (got %r)" % (h['distance'],))
+        if h['distance'] not in ('edit', 'dtw', 'chamfer', 'hausdorff'):
+            raise ValueError("sequence-retrieval: distance must be 'edit', 'dtw', 'chamfer' or 'hausdorff' (got %r)" % (h['distance'],))
         continuous = bool(model.dataset.hps['use_continuous_data'])
         if continuous and h['distance'] == 'edit':
             raise ValueError("sequence-retrieval: distance=edit compares token ids; a continuous (stroke-5) dataset has none")
@@ -58,11 +61,15 @@ class SequenceRetrieval(Experiment):
             chosen = query_rows = self._subsample(len(query_x), int(h['n_queries']))
             query_x, query_y = query_x[chosen], query_y[chosen]
         block = max(1, int(h['gallery_block']))
+        kind = dict(kind='stroke5') if continuous else dict(kind='tokens', tokenizer=tokenizer)
         slabs = []
         for at in range(0, len(gallery_x), block):
             g = gallery_x[at:at + block]
             if h['distance'] == 'edit':
                 slabs.append(align.token_edit_distance(query_x, g, tokenizer, cross=True).to(torch.float32))
+            elif h['distance'] in ('chamfer', 'hausdorff'):
+                fn = align.sketch_chamfer if h['distance'] == 'chamfer' else align.sketch_hausdorff
+                slabs.append(fn(query_x, g, cross=True, samples_per_segment=int(h['samples_per_segment']), center=True, **kind))
             elif continuous:
                 slabs.append(align.sketch_dtw(query_x, g, kind='stroke5', cross=True, normalize=False))
             else:

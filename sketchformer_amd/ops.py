@@ -1187,6 +1187,44 @@ def dtw_distance(xy_a, n_a, xy_b, n_b, cross=False):
     return out
 
 
+SHAPE_GALLERY_BLOCK = 8                                          # SD_GALLERY_BLOCK of skf_chamfer.hip: rows of b per workgroup
+SHAPE_MAX_SAMPLES = 16
+
+
+def shape_distance(xy_a, pen_a, n_a, xy_b, pen_b, n_b, samples_per_segment=4, cross=False):
+    """Order-free distances between the ink of sketches (skf_shape_distance_f32; the rule is in include/skf.h): xy (N, T, 2)
+    float32, pen (N, T) uint8 and n (N,) int32 as sketch_points returns them (points and pen bytes contiguous in a row; the row
+    strides are free), T <= 512.  Every sketch is sampled at its points and at samples_per_segment - 1 interior positions of every
+    segment; a sample's distance to the other sketch is that to its nearest dot or segment.  -> float32 (Na, 4), or with
+    cross=True (Na, Nb, 4): (mean a->b, mean b->a, max a->b, max b->a).  Chamfer = half the sum of the first two, Hausdorff = the
+    larger of the last two.  An empty sketch stands for the single point (0, 0).  Bit-equal to a float32 numpy restatement."""
+    for xy, pen, name in ((xy_a, pen_a, "a"), (xy_b, pen_b, "b")):
+        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[2] != 2:
+            raise TypeError("xy_%s must be a float32 tensor of shape (N, T, 2)" % name)
+        if xy.stride(2) != 1 or (xy.shape[1] > 1 and xy.stride(1) != 2) or (xy.shape[0] > 1 and xy.stride(0) < 2 * xy.shape[1]):
+            raise ValueError("xy_%s must hold contiguous (x, y) points in rows that do not overlap" % name)
+        if pen.dtype != torch.uint8 or tuple(pen.shape) != tuple(xy.shape[:2]) or pen.device != xy.device:
+            raise TypeError("pen_%s must be a uint8 tensor of shape (N, T) on the device of xy_%s" % (name, name))
+        if (pen.shape[1] > 1 and pen.stride(1) != 1) or (pen.shape[0] > 1 and pen.stride(0) < pen.shape[1]):
+            raise ValueError("pen_%s must hold contiguous bytes in rows that do not overlap" % name)
+    if xy_b.device != xy_a.device:
+        raise ValueError("xy_a and xy_b must be on one device")
+    S = int(samples_per_segment)
+    if S != samples_per_segment or S < 1 or S > SHAPE_MAX_SAMPLES:
+        raise ValueError("samples_per_segment must be an integer in [1, %d] (got %r)" % (SHAPE_MAX_SAMPLES, samples_per_segment))
+    (Na, Ta), (Nb, Tb) = xy_a.shape[:2], xy_b.shape[:2]
+    _align_lengths(n_a, "n_a", Na, xy_a.device); _align_lengths(n_b, "n_b", Nb, xy_a.device)
+    _align_check(Na, Nb, Ta, Tb, cross)
+    if cross and Na * Nb * 4 >= 1 << 31:
+        raise ValueError("a cross matrix holds fewer than 2^31 floats (got %d x %d x 4): walk the gallery in slabs" % (Na, Nb))
+    _p(xy_a); _p(pen_a); _p(xy_b); _p(pen_b); _p(n_a); _p(n_b)   # CPU tensors: SkfError before anything is allocated
+    out = torch.empty((Na, Nb, 4) if cross else (Na, 4), dtype=torch.float32, device=xy_a.device)
+    _lib.call("skf_shape_distance_f32", _p(xy_a), max(xy_a.stride(0), 2 * Ta), _p(pen_a), max(pen_a.stride(0), Ta), _p(n_a), Na, Ta,
+              _p(xy_b), max(xy_b.stride(0), 2 * Tb), _p(pen_b), max(pen_b.stride(0), Tb), _p(n_b), Nb, Tb, S, 1 if cross else 0,
+              _p(out), _stream())
+    return out
+
+
 def sequence_score(logits, target, eos, tgt_off=0, T=None):
     """Teacher-forced scoring of given sequences (skf_sequence_score; the rule is in include/skf.h).  logits: float32 or bfloat16,
     (B, T, V), or (B * T, V) with ``T`` given, unit innermost stride; the row pitch may exceed V as long as it is the same for every
