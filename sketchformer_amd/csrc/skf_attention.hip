@@ -135,25 +135,22 @@ __global__ __launch_bounds__(256, MAXT <= 13 ? 4 : 1) void attn_fwd_kernel(AttnP
     }
   }
   {
+    // Ms[], Tf[] and last_valid[] from two ballots per pass of 256 keys: a wave holds the 64 keys of four tiles
     int lv = -1;
-    auto mask_key = [&](int key, unsigned char mb) {
+    auto mask_keys = [&](int key0 /* first key of the wave in this pass */, unsigned char mb) {
+      const int key = key0 + lane;
       float mv = -INFINITY;
       if (key < p.Lk) mv = (p.key_mask && mb) ? -1e9f : 0.f;
-      Ms[key] = mv;
-      if (mv == 0.f) lv = key;             // keys ascend within a thread
+      if (key < nkt * 16) Ms[key] = mv;
+      const unsigned long long open = __ballot(mv == 0.f), masked = __ballot(key < nkt * 16 && mv != 0.f);
+      if (open) lv = key0 + 63 - __builtin_clzll(open);      // keys ascend from pass to pass
+      const int t = (key0 >> 4) + (lane & 3);                // lane l < 4: the wave's tile l
+      if (lane < 4 && t < nkt) Tf[t] = ((unsigned)(masked >> (16 * (lane & 3))) & 0xffffu) != 0u;
     };
-    if (tid < nkt * 16) mask_key(tid, mk0);
+    mask_keys(64 * wave, mk0);
     if constexpr (MAXT * 16 > 256)
-      for (int key = tid + 256; key < nkt * 16; key += 256) mask_key(key, kmp[min(key, last_key)]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lv = max(lv, __shfl_xor(lv, o, 64));
+      for (int key0 = 64 * wave + 256; key0 < nkt * 16; key0 += 256) mask_keys(key0, kmp[min(key0 + lane, last_key)]);
     if (lane == 0) last_valid[wave] = lv;
-  }
-  __syncthreads();
-  if (tid < nkt) {
-    int f = 0;
-    for (int k = 0; k < 16; ++k) f |= Ms[tid * 16 + k] != 0.f;
-    Tf[tid] = f;
   }
   __syncthreads();
 

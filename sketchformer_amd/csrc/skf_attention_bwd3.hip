@@ -50,7 +50,7 @@ constexpr int PB = RMAX * RP;                 // bytes per plane (6656)
 // LDS map (bytes): 12 planes [K0 K1 K2 V0 V1 V2 Q0 Q1 Q2 G0 G1 G2] (G = dO / sum), then -max, -delta/sum per query row, control words
 constexpr int K_OFF = 0, V_OFF = 3 * PB, Q_OFF = 6 * PB, G_OFF = 9 * PB;
 constexpr int NMX_OFF = 12 * PB, NDL_OFF = NMX_OFF + RMAX * 4, KBITS_OFF = NDL_OFF + RMAX * 4, CTL_OFF = KBITS_OFF + 16 * 4;
-constexpr int SMEM_BYTES = CTL_OFF + 16;      // 81,616 <= 81,920 = half of a CU's LDS
+constexpr int SMEM_BYTES = CTL_OFF + 16 + 32;      // 81,648 <= 81,920 = half of a CU's LDS (control words, then the key-mask scan's per-wave words)
 constexpr float kLog2e = 1.44269504088896340736f, kLn2 = 0.69314718055994530942f;
 
 __device__ __forceinline__ f32x4 mfma_x(b3_u32x4 a, b3_u32x4 b, f32x4 c) {
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(512, 4) void attn_bwd3_kernel(AttnParams p) {
   if ((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem != sbase) __builtin_trap();
   // NMX_OFF: -max of the base-2 logits of a query row; NDL_OFF: -rowsum(dO o O) / sum
   unsigned* Kbits = reinterpret_cast<unsigned*>(smem + KBITS_OFF);   // [16] bit i of word t: key 16 t + i is padded (key mask)
-  int* ctl = reinterpret_cast<int*>(smem + CTL_OFF);   // [0] last un-padded key, [1] bit t: query tile t has a non-zero dO row, [2] item ticket,
-                                                       // [3] bit t: key tile t holds a padded key or reaches past Lk
+  int* ctl = reinterpret_cast<int*>(smem + CTL_OFF);   // [1] bit t: query tile t has a non-zero dO row, [2] item ticket
+  int* kscan = ctl + 4;                                // per wave w < 4: [w] bit t: key tile t (of the wave's four) holds a padded key, [4 + w] its last un-padded key or -1
   const SkfSplitSel sel = skf_split_sel();
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -151,16 +151,24 @@ __global__ __launch_bounds__(512, 4) void attn_bwd3_kernel(AttnParams p) {
   // ---------------- which key tiles are visited: the key mask first (one byte per thread: Lk <= 208 < 512), so that the rows of a
   // head are only REQUESTED where somebody will read them - on QuickDraw-shaped batches (58 % padding) the launch is a burst of
   // row loads followed by little arithmetic, and the burst is what it costs
+  // All of it is a function of the four ballots of the mask bytes: wave w < 4 (keys 64 w .. 64 w + 63) leaves its four Kbits words,
+  // the flags of its four tiles and its last un-padded key with plain stores; one barrier; every thread combines the four waves'
+  // words.  (The atomicOr / atomicMax form this replaces - sixteen lanes per Kbits word, every key on the two control words - needed
+  // the words cleared behind a barrier of its own first.)
   const unsigned char mb = p.key_mask ? p.key_mask[(size_t)b * p.key_mask_ld + min(tid, p.Lk - 1)] : (unsigned char)0;
-  if (tid < 16) Kbits[tid] = 0u;
-  if (tid == 32) { ctl[0] = -1; ctl[1] = 0; ctl[2] = 8; ctl[3] = (p.Lk & 15) ? 1 << (nkt - 1) : 0; }
-  __syncthreads();
-  if (tid < p.Lk) {
-    if (mb) { atomicOr(&Kbits[tid >> 4], 1u << (tid & 15)); atomicOr(reinterpret_cast<unsigned*>(&ctl[3]), 1u << (tid >> 4)); }
-    else atomicMax(&ctl[0], tid);
+  if (tid == 256) { ctl[1] = 0; ctl[2] = 8; }
+  if (wave < 4) {
+    const unsigned long long padded = __ballot(tid < p.Lk && mb != 0), open = __ballot(tid < p.Lk && mb == 0);
+    const unsigned word = (unsigned)(padded >> (16 * (lane & 3))) & 0xffffu;      // lane l < 4: the wave's tile l
+    if (lane < 4) Kbits[4 * wave + lane] = word;
+    const unsigned tiles = (unsigned)__ballot(lane < 4 && word != 0u);             // bit l: tile l of the wave holds a padded key
+    if (lane == 0) { kscan[wave] = (int)(tiles << (4 * wave)); kscan[4 + wave] = open ? 64 * wave + 63 - __builtin_clzll(open) : -1; }
   }
   __syncthreads();
-  const int lastk = ctl[0];
+  const b3_u32x4 kw = *reinterpret_cast<const b3_u32x4*>(kscan), lw = *reinterpret_cast<const b3_u32x4*>(kscan + 4);
+  // (both wave-uniform: scalar registers from here on)
+  const unsigned k_masked = __builtin_amdgcn_readfirstlane((kw[0] | kw[1]) | (kw[2] | kw[3])) | ((p.Lk & 15) ? 1u << (nkt - 1) : 0u);   // the tail tile reaches past Lk
+  const int lastk = __builtin_amdgcn_readfirstlane(max(max((int)lw[0], (int)lw[1]), max((int)lw[2], (int)lw[3])));                      // -1: a fully padded sample
   // skipping fully look-ahead-masked tiles is exact only if key 0 is visible; trailing all-padding key tiles have P == 0 exactly
   // unless some row may see no key at all (see skf_attention.hip)
   const bool can_skip = CAUSAL && !(Kbits[0] & 1u);
@@ -232,7 +240,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd3_kernel(AttnParams p) {
     }
   }
   __syncthreads();
-  const unsigned q_live = (unsigned)ctl[1], k_masked = (unsigned)ctl[3];
+  const unsigned q_live = (unsigned)ctl[1];
 
   // ---------------- the queue.  Items in falling order of cost: key tiles ascend (under the look-ahead mask key tile t is seen by
   // the query tiles >= t), query tiles descend (tile t sees t + 1 key tiles), a pass-B item (12 MFMAs per pair) before the
