@@ -1114,6 +1114,58 @@ size_t skf_stroke3_simplify_workspace_bytes(long long P, int N);
 int skf_stroke3_simplify(const float* flat, long long P, const long long* offsets, int N, double epsilon, unsigned flags,
                          float* out_flat, long long* out_offsets, void* workspace, size_t workspace_bytes, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Arc-length resampling of polylines
+ * The step Google's recipe for the simplified QuickDraw files runs in front of the simplification above (every stroke resampled
+ * at a spacing of one pixel), and the classical cure for comparing drawings of different vertex density (a fixed number of points
+ * equally spaced along the path, in front of skf_dtw_f32).  The reference has neither.  The specification is the project's own
+ * host restatement (tests/resample_reference.py) and the results are BIT-EQUAL to it: every sum below is an integer sum and every
+ * floating-point operation a single IEEE-rounded one, so a parallel evaluation and a sequential one agree.
+ * The rule.  A polyline of n points p_0 .. p_{n-1}, absolute (x, y) in fp32.
+ *   Segment lengths: dx = x_{i+1} - x_i, dy likewise, in fp32; c_i = sqrtf(dx * dx + dy * dy) in fp32, every operation rounded on
+ *     its own (no fused multiply-add), the square root correctly rounded: the cost of skf_dtw_f32.
+ *     q_i = (int64) rint((double) c_i * 2^16): lengths are integers in units of 2^-16 from here on.
+ *   Arc-length table: C_0 = 0, C_{i+1} = C_i + q_i in int64; total = C_{n-1}.
+ *   Spacing mode: s = rint(spacing * 2^16), s >= 1.  Targets T_m = m * s for every m >= 0 with T_m < total; the end point follows
+ *     them.  The polyline gives ceil(total / s) + 1 rows: 1 row for total == 0 (a single point, or all points coincident).
+ *   Count mode, n_out >= 2 rows: with total = a * (n_out - 1) + r, 0 <= r < n_out - 1: T_m = m * a + (m * r) / (n_out - 1) (integer
+ *     division) for m = 0 .. n_out - 2: floor(m * total / (n_out - 1)) without a wide product.  The end point follows.  total == 0
+ *     gives n_out copies of p_0.
+ *   The sample at a target T: the segment is the i with C_i <= T < C_{i+1} (unique; a segment with q_i == 0 is never chosen);
+ *     u = (double)(T - C_i) / (double) q_i; x = (float)((double) x_i + u * ((double) x_{i+1} - (double) x_i)), y likewise: the
+ *     division, the multiply and the add are each rounded to fp64 on their own, then once to fp32.
+ *   The end point is p_{n-1} copied bit for bit; the first row is p_0 bit for bit whenever there are two rows or more (u = 0).
+ * Coordinates.  total cannot overflow int64 while every |x|, |y| <= SKF_RESAMPLE_MAX_COORD = 2^14: then c_i < 2^16, q_i < 2^32, and
+ *   fewer than 2^31 of them add up to less than 2^63.  Stated, not checked here (ops.polyline_resample and simplify.resample_lines
+ *   refuse larger coordinates on the host); inputs must be finite.  Whatever the inputs hold, no kernel leaves its buffers.
+ * Nothing here allocates, synchronises with the host or uses an atomic; every output element has one writer per launch; two calls
+ * on the same inputs agree bit for bit and a polyline's result does not depend on the rest of the batch.  Polyline length is not
+ * limited.  xy (P, 2) fp32, ldp floats from row to row; stroke_offsets (S + 1 int64, on the device) as for skf_rdp_f32: the caller
+ * checks them, the kernels clamp every range to [0, P] and never trust an offset as an index.
+ * skf_polyline_resample_count: the measure launch (one wavefront per polyline: q_i, a wave scan with a carry from one tile of 64
+ *   points to the next, C for every point into the workspace, the polyline's row count) and the counts -> offsets scan.  Afterwards
+ *   out_offsets (S + 1 int64) holds the offsets of the resampled polylines, out_offsets[S] = the number of output rows P', and
+ *   the workspace holds C.  An empty polyline gives no row.  A polyline's count saturates at 2^31 - 1: P' >= 2^31 - 1 means that
+ *   the result does not fit and must not be emitted.
+ * skf_polyline_resample_emit: the emit launch.  Same xy, ldp, P, stroke_offsets, S, spacing and the workspace exactly as _count
+ *   left it; out_offsets as _count wrote them.  Row out_offsets[s] + m of out_xy (out_rows, 2) receives sample m of polyline s: one
+ *   lane per row, consecutive lanes consecutive targets, the segment found by binary search over the polyline's slice of C.
+ *   out_rows is the capacity: rows at or past it are not written, nor is any row a polyline does not own.
+ * skf_polyline_resample_n: count mode in one call, out_xy (S, n_out, 2) dense.  An EMPTY polyline gives n_out rows (0, 0): the
+ *   single point (0, 0) that stands for an empty sketch in skf_dtw_f32 and skf_shape_distance_f32.
+ * Limits (SKF_EINVAL): S >= 1, 1 <= P < 2^31, ldp >= 2, spacing finite, below 7e13 and rint(spacing * 2^16) >= 1,
+ *   2 <= n_out <= SKF_RESAMPLE_MAX_N, 1 <= out_rows < 2^31 (so P' < 2^31), xy not 4-byte, the offsets and out_xy not 8-byte
+ *   aligned, a workspace below skf_polyline_resample_workspace_bytes(P, S) bytes (0 = bad sizes) or not 16-byte aligned. */
+#define SKF_RESAMPLE_MAX_N 65536
+#define SKF_RESAMPLE_MAX_COORD 16384
+size_t skf_polyline_resample_workspace_bytes(long long P, int S);
+int skf_polyline_resample_count(const float* xy, int ldp, long long P, const long long* stroke_offsets, int S, double spacing,
+                                long long* out_offsets, void* workspace, size_t workspace_bytes, skf_stream_t stream);
+int skf_polyline_resample_emit(const float* xy, int ldp, long long P, const long long* stroke_offsets, int S, double spacing,
+                               const long long* out_offsets, float* out_xy, long long out_rows, void* workspace,
+                               size_t workspace_bytes, skf_stream_t stream);
+int skf_polyline_resample_n(const float* xy, int ldp, long long P, const long long* stroke_offsets, int S, int n_out, float* out_xy,
+                            void* workspace, size_t workspace_bytes, skf_stream_t stream);
+
 /* ------------------------------------------------------------------ Sequence alignment (token edit distance, point DTW)
  * The reference has nothing in this place: it judges a reconstruction by eye (metrics/samples.py) and its README's retrieval has
  * no classical baseline.  What is compared here is what the model emits: the ids that models/sketchformer.py `predict` returns

@@ -64,16 +64,43 @@ def token_edit_distance(a, b, tokenizer, cross=False, normalize=False):
     return d.to(torch.float64) / longer.clamp(min=1).to(torch.float64)
 
 
-def sketch_dtw(a, b, kind='stroke3', tokenizer=None, cross=False, normalize=True, lengths_a=None, lengths_b=None):
+def _resampled_rows(xy, n, n_out):
+    """Point rows xy (N, T, 2) with n (N,) points each -> ((N, n_out, 2), int32 (N,) all n_out): every row's pen path resampled to
+    n_out points equally spaced along its arc length (ops.polyline_resample_n).  An empty row becomes n_out rows (0, 0), the single
+    point that stands for it in the alignment."""
+    import torch
+    from . import ops
+    N, T = xy.shape[0], xy.shape[1]
+    n = n.clamp(0, T).to(torch.int64)
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=xy.device)
+    offsets[1:] = torch.cumsum(n, 0)
+    live = torch.arange(T, device=xy.device)[None, :] < n[:, None]
+    packed = xy[live]                                              # (P, 2): the rows back to back, what lies behind n left out
+    if packed.shape[0] == 0:
+        out = torch.zeros(N, int(n_out), 2, dtype=torch.float32, device=xy.device)
+    else:
+        out = ops.polyline_resample_n(packed, offsets, n_out)
+    return out, torch.full((N,), int(n_out), dtype=torch.int32, device=xy.device)
+
+
+def sketch_dtw(a, b, kind='stroke3', tokenizer=None, cross=False, normalize=True, lengths_a=None, lengths_b=None, resample=None):
     """Dynamic time warping between the pen positions of sketches a and b, each in any form raster.points takes ('stroke3' with
     lengths_a / lengths_b or as ragged lists, 'stroke5', 'tokens' with the tokenizer): float32 (Na,) for the pairs, (Na, Nb) with
     cross=True.  An empty sketch stands for the single point (0, 0), the dummy row of the host decoders.  normalize: divided by
     max(n_a, 1) + max(n_b, 1) (an upper bound on the length of the alignment path), float64: a mean distance per step that does
-    not grow with the length of the sketches.  Device tensors out."""
+    not grow with the length of the sketches.  resample=n (2 <= n <= 512): every sketch's sequence of pen positions, taken as ONE
+    path - pen-up moves included, the sequence that is aligned without it - is first resampled to n points equally spaced along
+    its arc length (the rule of include/skf.h, coordinates within +-2^14), so that two drawings of one curve with different vertex
+    densities are close; every sketch then counts n points.  Device tensors out."""
     import torch
     from . import ops, raster
     xa, _, na, _ = raster.points(a, kind, tokenizer, lengths_a)
     xb, _, nb, _ = raster.points(b, kind, tokenizer, lengths_b, device=xa.device)
+    if resample is not None:
+        if not 2 <= int(resample) <= ops.ALIGN_MAX_LEN:
+            raise ValueError("resample must be in [2, %d] (got %r)" % (ops.ALIGN_MAX_LEN, resample))
+        xa, na = _resampled_rows(xa, na, int(resample))
+        xb, nb = _resampled_rows(xb, nb, int(resample))
     d = ops.dtw_distance(xa, na, xb, nb, cross=cross)
     if not normalize:
         return d

@@ -3,7 +3,9 @@ a distance between the drawings themselves and score the ranking by class label 
 embedding (mAP@k, precision@k, recall@1).  distance=edit / dtw: an alignment distance between the sequences, the token edit
 distance or dynamic time warping over the pen positions, one dynamic program per (query, gallery) pair.  distance=chamfer /
 hausdorff: an order-free distance between the ink, the mean or the worst nearest-ink distance with samples_per_segment samples
-per segment, every sketch centred on its bounding box first (a sketch starts at its first pen position).  All on the device
+per segment, every sketch centred on its bounding box first (a sketch starts at its first pen position).  resample_points=n
+(distance=dtw only; 0 = off) resamples every sketch's pen path to n points equally spaced along it before the alignment, so that
+the vertex density of a drawing plays no part.  All on the device
 (sketchformer_amd/align.py); the gallery walks through in blocks so the distance matrix is built a slab at a time.  Uses
 model.dataset only; writes one .npz with the keys of retrieval.npz."""
 import os
@@ -22,7 +24,7 @@ class SequenceRetrieval(Experiment):
     @classmethod
     def specific_default_hparams(cls):
         return hp.HParams(distance='dtw', gallery_set='test', query_set='valid', top_k=100, n_queries=256, n_gallery=4096,
-                          gallery_block=1024, target_file='sequence_retrieval.npz', samples_per_segment=4)
+                          gallery_block=1024, target_file='sequence_retrieval.npz', samples_per_segment=4, resample_points=0)
 
     @staticmethod
     def _subsample(n_rows, n):
@@ -70,10 +72,8 @@ class SequenceRetrieval(Experiment):
             elif h['distance'] in ('chamfer', 'hausdorff'):
                 fn = align.sketch_chamfer if h['distance'] == 'chamfer' else align.sketch_hausdorff
                 slabs.append(fn(query_x, g, cross=True, samples_per_segment=int(h['samples_per_segment']), center=True, **kind))
-            elif continuous:
-                slabs.append(align.sketch_dtw(query_x, g, kind='stroke5', cross=True, normalize=False))
             else:
-                slabs.append(align.sketch_dtw(query_x, g, kind='tokens', tokenizer=tokenizer, cross=True, normalize=False))
+                slabs.append(align.sketch_dtw(query_x, g, cross=True, normalize=False, resample=int(h['resample_points']) or None, **kind))
         D = torch.cat(slabs, dim=1)
         k = max(1, min(int(h['top_k']), len(gallery_x) - (1 if same else 0)))
         # one split on both sides: leave-one-out, query j is gallery row chosen[j]

@@ -1124,6 +1124,77 @@ def stroke3_simplify(flat, offsets, epsilon):
     return _compacted(out_flat, out_offsets)
 
 
+RESAMPLE_MAX_N = 65536                                           # SKF_RESAMPLE_MAX_N of include/skf.h
+RESAMPLE_MAX_COORD = 16384                                       # SKF_RESAMPLE_MAX_COORD: beyond it the arc length may overflow int64
+
+
+def _resample_args(xy, stroke_offsets, who):
+    """The checks the resampling entry points share -> (P, S, ldp)"""
+    _p(xy); _p(stroke_offsets)                                   # CPU tensors: SkfError before anything is allocated
+    if xy.dtype != torch.float32 or xy.dim() != 2 or xy.shape[1] != 2 or xy.stride(1) != 1:
+        raise TypeError("xy must be a float32 tensor of shape (P, 2) with a unit innermost stride")
+    P, S = _ragged_offsets(stroke_offsets, xy, who, names=("stroke_offsets", "S", "xy", "polyline"))
+    ldp = xy.stride(0) if P > 1 else 2                           # (the row stride of a single row is never used)
+    if ldp < 2:                                                  # an expanded or overlapping view: rows the tensor does not own
+        raise ValueError("the rows of xy must not overlap (row stride %d < 2)" % ldp)
+    if ldp >= 1 << 31:
+        raise ValueError("the row stride of xy must be below 2^31")
+    return P, S, ldp
+
+
+def _resample_spacing(spacing):
+    spacing = float(spacing)
+    if not (spacing < 7e13 and spacing * 65536.0 > 0.5):         # (false for a NaN); rint(0.5) is 0
+        raise ValueError("spacing must be finite, below 7e13, with rint(spacing * 2^16) >= 1 (got %r)" % spacing)
+    return spacing
+
+
+def polyline_resample_offsets(xy, stroke_offsets, spacing, return_workspace=False):
+    """The count phase of polyline_resample alone (skf_polyline_resample_count): -> out_offsets (S + 1) int64 on the device, the
+    offsets of the resampled polylines, out_offsets[S] = the number of rows polyline_resample would return.  Nothing is read back.
+    return_workspace: also (workspace, its size), holding the arc-length tables the emit phase reads."""
+    P, S, ldp = _resample_args(xy, stroke_offsets, "polyline_resample")
+    spacing = _resample_spacing(spacing)
+    out_offsets = torch.empty(S + 1, dtype=torch.int64, device=xy.device)
+    ws, nbytes = _workspace_for("skf_polyline_resample_workspace_bytes", xy.device, P, S)
+    _lib.call("skf_polyline_resample_count", _p(xy), ldp, P, _p(stroke_offsets), S, spacing, _p(out_offsets), _p(ws), nbytes, _stream())
+    return (out_offsets, ws, nbytes) if return_workspace else out_offsets
+
+
+def polyline_resample(xy, stroke_offsets, spacing):
+    """S polylines resampled along their arc length at `spacing` (skf_polyline_resample_count / _emit), bit-equal to the host
+    restatement of the rule in include/skf.h.  xy (P, 2) float32 absolute points with a unit innermost stride (the row stride is
+    free), |x|, |y| <= 2^14 and finite (the caller's contract: nothing is read back to check it; simplify.resample_lines checks on
+    the host); stroke_offsets (S + 1) int64 on the same device, non-decreasing from 0 to P.  -> (out_xy (P', 2) float32, out_offsets
+    (S + 1) int64): a polyline of arc length L gives ceil(L / spacing) + 1 rows, its ends bit for bit; an empty one gives none.
+    Two phases with one 8-byte read-back of P' = out_offsets[S] between them, which waits for the current stream: the rows cannot be
+    allocated before their number is known."""
+    P, S, ldp = _resample_args(xy, stroke_offsets, "polyline_resample")
+    out_offsets, ws, nbytes = polyline_resample_offsets(xy, stroke_offsets, spacing, return_workspace=True)
+    rows = int(out_offsets[-1].item())
+    if rows >= (1 << 31) - 1:
+        raise ValueError("polyline_resample: the result needs 2^31 rows or more; cut the batch or use a larger spacing")
+    out_xy = torch.empty(rows, 2, dtype=torch.float32, device=xy.device)
+    if rows:
+        _lib.call("skf_polyline_resample_emit", _p(xy), ldp, P, _p(stroke_offsets), S, float(spacing), _p(out_offsets), _p(out_xy), rows,
+                  _p(ws), nbytes, _stream())
+    return out_xy, out_offsets
+
+
+def polyline_resample_n(xy, stroke_offsets, n_out):
+    """S polylines resampled to n_out points each, equally spaced along the arc length (skf_polyline_resample_n), bit-equal to the
+    host restatement.  Arguments as for polyline_resample; 2 <= n_out <= 65536.  -> (S, n_out, 2) float32: the ends bit for bit, a
+    polyline of arc length 0 as n_out copies of its first point, an empty one as n_out rows (0, 0).  No read-back."""
+    P, S, ldp = _resample_args(xy, stroke_offsets, "polyline_resample_n")
+    n_out = int(n_out)
+    if not 2 <= n_out <= RESAMPLE_MAX_N:
+        raise ValueError("n_out must be in [2, %d] (got %d)" % (RESAMPLE_MAX_N, n_out))
+    out = torch.empty(S, n_out, 2, dtype=torch.float32, device=xy.device)
+    ws, nbytes = _workspace_for("skf_polyline_resample_workspace_bytes", xy.device, P, S)
+    _lib.call("skf_polyline_resample_n", _p(xy), ldp, P, _p(stroke_offsets), S, n_out, _p(out), _p(ws), nbytes, _stream())
+    return out
+
+
 ALIGN_MAX_LEN = 512                                              # SKF_ALIGN_MAX_LEN of include/skf.h
 
 

@@ -77,21 +77,137 @@ def simplify_sketches(sketches, epsilon, device=None):
     return out
 
 
-def simplify_lines(lines, epsilon, device=None):
-    """A list of (n, 2) absolute polylines -> the kept points of each, in their own dtype.  The rule sees the points as float32."""
+RESAMPLE_MAX_COORD = 16384     # SKF_RESAMPLE_MAX_COORD of include/skf.h: beyond it the arc length of a batch may overflow int64
+RESAMPLE_ROW_BUDGET = 1 << 24  # resampled rows one device call may produce (128 MiB of points, 96 MiB of RDP state beside them)
+
+
+def _pack_lines(lines):
+    """-> (the polylines as (n, 2) arrays, offsets int64, xy float32 (P, 2))"""
     lines = [np.asarray(l).reshape(-1, 2) for l in lines]
     lens = np.fromiter((len(l) for l in lines), dtype=np.int64, count=len(lines))
-    if lens.sum() == 0:
-        return [l.copy() for l in lines]
     offsets = np.zeros(len(lines) + 1, dtype=np.int64)
     np.cumsum(lens, out=offsets[1:])
-    xy = np.ascontiguousarray(np.concatenate([l for l in lines if len(l)], axis=0), dtype=np.float32)
+    parts = [l for l in lines if len(l)]
+    xy = np.ascontiguousarray(np.concatenate(parts, axis=0), dtype=np.float32) if parts else np.zeros((0, 2), np.float32)
+    return lines, offsets, xy
+
+
+def _check_resample(xy, spacing, n_points):
+    """The host-side refusals of the resampling helpers, before anything goes to the device."""
+    if (spacing is None) == (n_points is None):
+        raise ValueError("give exactly one of spacing and n_points")
+    if spacing is not None:
+        spacing = float(spacing)
+        if not (spacing < 7e13 and spacing * 65536.0 > 0.5):     # (false for a NaN)
+            raise ValueError("spacing must be finite, below 7e13, with rint(spacing * 2^16) >= 1 (got %r)" % spacing)
+    else:
+        n_points = int(n_points)
+        if not 2 <= n_points <= 65536:
+            raise ValueError("n_points must be in [2, 65536] (got %d)" % n_points)
+    if len(xy) and not (np.abs(xy) <= RESAMPLE_MAX_COORD).all():     # (false for a NaN or an infinity too)
+        raise ValueError("coordinates must be finite and within +-%d to be resampled (the arc length is summed in int64 units of "
+                         "2^-16)" % RESAMPLE_MAX_COORD)
+    return spacing, n_points
+
+
+def _cut_by_rows(out_offsets, budget):
+    """[(first, last + 1)] runs of polylines whose resampled rows stay within `budget` a run; a polyline that alone exceeds it is
+    a run of its own.  out_offsets: the host copy of what the count phase wrote."""
+    if budget < 1:
+        raise ValueError("the row budget must be at least 1")
+    S, cuts, a = len(out_offsets) - 1, [], 0
+    while a < S:
+        b = int(np.searchsorted(out_offsets, out_offsets[a] + budget, side="right")) - 1
+        b = min(max(b, a + 1), S)
+        cuts.append((a, b))
+        a = b
+    return cuts
+
+
+def _resampled_runs(xy_d, offsets, spacing, row_budget):
+    """Yields (a, b, out_xy, out_offsets) per run of polylines a .. b - 1: the whole batch is measured once (8 bytes a point), the
+    offsets come back to the host, and every run is resampled by a call of its own whose output stays within the row budget."""
+    import torch
+    from . import ops
+    dev = xy_d.device
+    total = ops.polyline_resample_offsets(xy_d, torch.from_numpy(offsets).to(dev), spacing).cpu().numpy()
+    for a, b in _cut_by_rows(total, row_budget):
+        lo, hi = int(offsets[a]), int(offsets[b])
+        if hi == lo:
+            continue
+        part = torch.from_numpy(offsets[a:b + 1] - lo).to(dev)
+        out_xy, out_offsets = ops.polyline_resample(xy_d[lo:hi], part, spacing)
+        yield a, b, out_xy, out_offsets
+
+
+def resample_lines(lines, spacing=None, n_points=None, device=None, row_budget=None):
+    """A list of (n, 2) absolute polylines -> each resampled along its arc length, float32: with `spacing` a point every `spacing`
+    units and the end point (ceil(length / spacing) + 1 rows; an empty polyline stays empty), with `n_points` that many points
+    equally spaced (an empty polyline gives n_points rows (0, 0)).  The rule of include/skf.h (Arc-length resampling), bit-equal
+    to its host restatement; the ends are kept bit for bit.  Coordinates must be finite and within +-2^14: ValueError otherwise,
+    before anything is copied to the device.  row_budget: the resampled rows one device call may produce (RESAMPLE_ROW_BUDGET):
+    the batch is cut by the counts of a first pass over all of it."""
+    lines, offsets, xy = _pack_lines(lines)
+    spacing, n_points = _check_resample(xy, spacing, n_points)
+    if len(xy) == 0:
+        return [np.zeros((0 if n_points is None else n_points, 2), np.float32) for _ in lines]
     import torch
     from . import ops
     dev = _device(device)
+    budget = RESAMPLE_ROW_BUDGET if row_budget is None else int(row_budget)
+    out = [np.zeros((0, 2), np.float32)] * len(lines)
     with torch.cuda.device(dev):
-        keep = ops.rdp_keep(torch.from_numpy(xy).to(dev), torch.from_numpy(offsets).to(dev), epsilon).cpu().numpy().astype(bool)
-    return [l[keep[offsets[i]:offsets[i + 1]]] for i, l in enumerate(lines)]
+        xy_d = torch.from_numpy(xy).to(dev)
+        if n_points is not None:
+            if budget < 1:
+                raise ValueError("the row budget must be at least 1")
+            step = max(1, budget // n_points)
+            for a in range(0, len(lines), step):
+                b = min(a + step, len(lines))
+                lo, hi = int(offsets[a]), int(offsets[b])
+                if hi == lo:
+                    rows = np.zeros((b - a, n_points, 2), np.float32)
+                else:
+                    rows = ops.polyline_resample_n(xy_d[lo:hi], torch.from_numpy(offsets[a:b + 1] - lo).to(dev), n_points).cpu().numpy()
+                out[a:b] = list(rows)
+        else:
+            for a, b, out_xy, out_offsets in _resampled_runs(xy_d, offsets, spacing, budget):
+                rows, offs = out_xy.cpu().numpy(), out_offsets.cpu().numpy()
+                out[a:b] = [rows[offs[i]:offs[i + 1]] for i in range(b - a)]
+    return out
+
+
+def simplify_lines(lines, epsilon, device=None, resample_spacing=None, row_budget=None):
+    """A list of (n, 2) absolute polylines -> the kept points of each, in their own dtype.  The rule sees the points as float32.
+    resample_spacing: every polyline is first resampled along its arc length at that spacing (resample_lines' rule and limits) and
+    the resampled points go straight into the simplification on the device, under the new offsets; only the kept points come back,
+    as float32.  The batch is cut so that one device call resamples at most row_budget rows (RESAMPLE_ROW_BUDGET), by the counts of
+    a first pass over all of it: memory is bounded whatever the batch holds."""
+    lines, offsets, xy = _pack_lines(lines)
+    if resample_spacing is None:
+        if len(xy) == 0:
+            return [l.copy() for l in lines]
+        import torch
+        from . import ops
+        dev = _device(device)
+        with torch.cuda.device(dev):
+            keep = ops.rdp_keep(torch.from_numpy(xy).to(dev), torch.from_numpy(offsets).to(dev), epsilon).cpu().numpy().astype(bool)
+        return [l[keep[offsets[i]:offsets[i + 1]]] for i, l in enumerate(lines)]
+    spacing, _ = _check_resample(xy, resample_spacing, None)
+    out = [np.zeros((0, 2), np.float32)] * len(lines)
+    if len(xy) == 0:
+        return out
+    import torch
+    from . import ops
+    dev = _device(device)
+    budget = RESAMPLE_ROW_BUDGET if row_budget is None else int(row_budget)
+    with torch.cuda.device(dev):
+        for a, b, out_xy, out_offsets in _resampled_runs(torch.from_numpy(xy).to(dev), offsets, spacing, budget):
+            keep = ops.rdp_keep(out_xy, out_offsets, epsilon).to(torch.bool)
+            kept = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(keep, 0)])[out_offsets]
+            rows, offs = out_xy[keep].cpu().numpy(), kept.cpu().numpy()
+            out[a:b] = [rows[offs[i]:offs[i + 1]] for i in range(b - a)]
+    return out
 
 
 def quickdraw_lines(drawing):
