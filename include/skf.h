@@ -1166,6 +1166,74 @@ int skf_polyline_resample_emit(const float* xy, int ldp, long long P, const long
 int skf_polyline_resample_n(const float* xy, int ldp, long long P, const long long* stroke_offsets, int S, int n_out, float* out_xy,
                             void* workspace, size_t workspace_bytes, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Stroke edits (permute, reverse, drop)
+ * New sketches built out of the strokes of old ones: the strokes in any order, forwards or backwards, some left out or repeated,
+ * the pen jumps between them recomputed.  It is what the reference loader's shuffle_stroke option does on the host through
+ * polylines and back, and what a study of stroke order, stroke direction and stroke importance multiplies a batch with.  The
+ * specification is the project's own host restatement (tests/strokes_reference.py) and the results are BIT-EQUAL to it.
+ * The rule.  flat (P, 3) fp32 rows (dx, dy, pen) and offsets (N + 1 int64) as for skf_sketch_encode.
+ *   Strokes: within a sketch a stroke is a maximal run of rows that ends at a row with pen == 1, or at the sketch's last row
+ *     (skf_stroke3_simplify's definition).  An empty sketch has no strokes; a stroke is never empty.
+ *   Absolute positions: A_j is the sequential fp32 running sum of dx and of dy, one add per point, from (0, 0)
+ *     (skf_stroke3_simplify's rule).
+ *   The stroke table: sketch_strokes (N + 1 int64): sketch s owns the global strokes sketch_strokes[s] .. sketch_strokes[s + 1] - 1,
+ *     T = sketch_strokes[N] <= P; stroke_rows (T + 1 int64): the first flat row of every stroke, stroke_rows[T] = the number of
+ *     rows; stroke_ends (T, 4) fp32: A of the stroke's first row and of its last row, (x, y, x, y).
+ *   An edit describes M output sketches: src (M int32) names the source sketch of each, sel_offsets (M + 1 int64) delimits its
+ *     selection list in sel (Q int32).  An entry k >= 0 selects stroke k of the source sketch, drawn as stored; ~k (= -k - 1)
+ *     selects the same stroke drawn backwards.  Strokes may repeat, a list may be empty, M may be smaller or larger than N.  An
+ *     entry that names no stroke - src outside [0, N), or k at or past the source's stroke count - is ABSENT: it gives no rows,
+ *     and the entries around it join as if it had not been listed.
+ *   Output rows: a selected stroke with the source rows a .. b gives b - a + 1 rows.  E = the position where the previous
+ *     present entry of the same list ended, (0, 0) for the first.
+ *     Forward: the first row is A_a - E, one fp32 subtraction per coordinate; the rows a + 1 .. b follow with dx, dy copied bit for
+ *       bit; the stroke ends at A_b.
+ *     Backward: the first row is A_b - E; then for i = b down to a + 1 a row (-dx_i, -dy_i): a sign flip of the stored bits, so a
+ *       stored +0 becomes -0; the stroke ends at A_a.
+ *     Pen: 1 on the stroke's last output row, 0 on the others: the identity edit differs from its input only in the pen of an
+ *       unterminated final stroke (and in pen values other than 0 and 1, which end no stroke).
+ *     No fused multiply-add anywhere (there is no product to fuse; the file is compiled like its neighbours all the same).
+ *   Consequences.  E and the stroke ends come from the source's A, not from re-summing output rows, so a stroke's rows depend on
+ *     nothing but its own sketch and the entry in front of it.  Inside a stroke nothing is rounded.  On integer-valued data below
+ *     2^24 (raw QuickDraw) every sum is exact and the identity edit returns its input bit for bit.  On other data a jump - the
+ *     first row of a stroke - can differ from the stored offset by one fp32 rounding (A_a - A_{a-1} need not give back dx_a), and
+ *     a stored -0 in a stroke's first row comes back as +0.
+ * Nothing here allocates, synchronises with the host or uses an atomic; every output element has one writer per launch; two calls
+ * on the same inputs agree bit for bit.  Every range read from offsets, sketch_strokes, stroke_rows, src, sel_offsets or sel is
+ * clamped before it is used as an index: no input can take a kernel out of its buffers.  The caller checks that offsets and
+ * sel_offsets are non-decreasing from 0 to P and to Q (lists that overlap would give an entry two writers).
+ * skf_stroke_table: one wavefront per sketch counts its strokes with ballots over tiles of 64 rows, the counts -> offsets scan
+ *   writes sketch_strokes, and a second launch writes stroke_rows and stroke_ends: a stroke's rank within the sketch is a popcount
+ *   below the lane plus the tile carry, the positions come from one lane's sequential walk.  stroke_rows has room for P + 1
+ *   entries and stroke_ends for P rows; the entries 0 .. T of stroke_rows and the rows 0 .. T - 1 of stroke_ends are written.
+ *   flags: none defined, must be 0.
+ * skf_stroke_edit_count: the table's sketch_strokes (N + 1), stroke_rows (T + 1) and T as the caller read it back; src,
+ *   sel_offsets, sel as above.  One wavefront per output sketch gives every entry its stroke (or none), its length and, through a
+ *   wave scan over the list in tiles of 64 entries with a carry, its first output row; the counts -> offsets scan follows.
+ *   Afterwards out_offsets (M + 1 int64) holds the offsets of the output sketches, out_offsets[M] = the number of output rows
+ *   P', and the workspace holds what _emit reads.  A sketch's count saturates at 2^31 - 1: P' >= 2^31 - 1 means that the result does
+ *   not fit and must not be emitted.
+ * skf_stroke_edit_emit: the same arguments and the workspace exactly as _count left it, plus flat and stroke_ends (T, 4);
+ *   out_offsets as _count wrote them.  A wavefront takes 64 entries at a time: every lane gathers one entry's header, then every
+ *   lane writes one row of out_flat (out_rows, 3) at a time, consecutive lanes consecutive rows, the owning entry found by binary
+ *   search over the 64 starts on chip.  out_rows is the capacity: rows at or past it are not written, nor is any row no stroke
+ *   owns.
+ * Limits (SKF_EINVAL): N, M >= 1, 1 <= P < 2^31, 0 <= Q < 2^31, 0 <= T <= P, 1 <= out_rows < 2^31, flags != 0, a pointer not
+ *   aligned to its element, a workspace below skf_stroke_table_workspace_bytes(P, N) / skf_stroke_edit_workspace_bytes(P, N, M, Q)
+ *   bytes (0 = bad sizes) or not 16-byte aligned; its contents carry nothing from one call to the next, other than from _count to
+ *   _emit.  sel may be null when Q == 0, stroke_ends when T == 0. */
+size_t skf_stroke_table_workspace_bytes(long long P, int N);
+int skf_stroke_table(const float* flat, long long P, const long long* offsets, int N, unsigned flags, long long* sketch_strokes,
+                     long long* stroke_rows, float* stroke_ends, void* workspace, size_t workspace_bytes, skf_stream_t stream);
+size_t skf_stroke_edit_workspace_bytes(long long P, int N, int M, long long Q);
+int skf_stroke_edit_count(long long P, const long long* sketch_strokes, int N, const long long* stroke_rows, long long T,
+                          const int* src, const long long* sel_offsets, int M, const int* sel, long long Q, unsigned flags,
+                          long long* out_offsets, void* workspace, size_t workspace_bytes, skf_stream_t stream);
+int skf_stroke_edit_emit(const float* flat, long long P, const long long* sketch_strokes, int N, const long long* stroke_rows,
+                         const float* stroke_ends, long long T, const int* src, const long long* sel_offsets, int M, const int* sel,
+                         long long Q, unsigned flags, const long long* out_offsets, float* out_flat, long long out_rows,
+                         void* workspace, size_t workspace_bytes, skf_stream_t stream);
+
 /* ------------------------------------------------------------------ Sequence alignment (token edit distance, point DTW)
  * The reference has nothing in this place: it judges a reconstruction by eye (metrics/samples.py) and its README's retrieval has
  * no classical baseline.  What is compared here is what the model emits: the ids that models/sketchformer.py `predict` returns

@@ -1195,6 +1195,83 @@ def polyline_resample_n(xy, stroke_offsets, n_out):
     return out
 
 
+def stroke_table(flat, offsets):
+    """The strokes of a ragged batch of stroke-3 sketches (skf_stroke_table; the rule is in include/skf.h).  flat (P, 3) float32
+    and offsets (N + 1) int64 as for sketch_encode.  -> (sketch_strokes (N + 1) int64: sketch s owns the global strokes
+    sketch_strokes[s] .. sketch_strokes[s + 1] - 1; stroke_rows (T + 1) int64: the first flat row of every stroke, then P;
+    stroke_ends (T, 4) float32: the absolute position of the stroke's first and last row).  Reading T = sketch_strokes[N] is one
+    8-byte device-to-host copy that waits for the current stream."""
+    P, N = _ragged(flat, offsets, "stroke_table")
+    dev = flat.device
+    sketch_strokes = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    stroke_rows = torch.empty(P + 1, dtype=torch.int64, device=dev)
+    stroke_ends = torch.empty(P, 4, dtype=torch.float32, device=dev)
+    ws, nbytes = _workspace_for("skf_stroke_table_workspace_bytes", dev, P, N)
+    _lib.call("skf_stroke_table", _p(flat), P, _p(offsets), N, 0, _p(sketch_strokes), _p(stroke_rows), _p(stroke_ends), _p(ws), nbytes,
+              _stream())
+    T = min(int(sketch_strokes[-1].item()), P)
+    return sketch_strokes, stroke_rows[:T + 1], stroke_ends[:T]
+
+
+def _stroke_edit_args(flat, offsets, src, sel_offsets, sel, table):
+    """The checks of stroke_edit -> (P, N, M, Q, T, table)"""
+    P, N = _ragged(flat, offsets, "stroke_edit")
+    dev = flat.device
+    for t, name, dtype in ((src, "src", torch.int32), (sel_offsets, "sel_offsets", torch.int64), (sel, "sel", torch.int32)):
+        _p(t)                                                    # CPU tensors: SkfError before anything is allocated
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
+            raise TypeError("%s must be a contiguous %s vector on the device of flat" % (name, str(dtype).replace("torch.", "")))
+    M, Q = src.shape[0], sel.shape[0]
+    if M < 1:
+        raise ValueError("stroke_edit needs at least one output sketch")
+    if sel_offsets.shape[0] != M + 1:
+        raise ValueError("sel_offsets must hold M + 1 = %d entries (got %d)" % (M + 1, sel_offsets.shape[0]))
+    if Q >= 1 << 31:
+        raise ValueError("stroke_edit takes fewer than 2^31 selected strokes")
+    if table is None:
+        table = stroke_table(flat, offsets)
+    sketch_strokes, stroke_rows, stroke_ends = table
+    T = stroke_rows.shape[0] - 1
+    for t, name, dtype, shape in ((sketch_strokes, "sketch_strokes", torch.int64, (N + 1,)), (stroke_rows, "stroke_rows", torch.int64, (T + 1,)),
+                                  (stroke_ends, "stroke_ends", torch.float32, (T, 4))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise TypeError("table: %s must be a contiguous %s tensor of shape %r on the device of flat, as stroke_table returns it"
+                            % (name, str(dtype).replace("torch.", ""), shape))
+    if T < 0 or T > P:
+        raise ValueError("table: stroke_rows must hold between 1 and P + 1 entries")
+    return P, N, M, Q, T, table
+
+
+def stroke_edit(flat, offsets, src, sel_offsets, sel, table=None):
+    """New sketches out of the strokes of old ones (skf_stroke_edit_count / _emit; the rule is in include/skf.h), bit-equal to the
+    host restatement.  flat (P, 3) float32 and offsets (N + 1) int64 as for sketch_encode; src (M,) int32: the source sketch of
+    every output sketch; sel_offsets (M + 1) int64, non-decreasing from 0 to Q; sel (Q,) int32: k >= 0 = stroke k of the source
+    as stored, ~k = the same stroke drawn backwards; an entry that names no stroke gives no rows.  table: what stroke_table(flat,
+    offsets) returned, to edit one batch several times.  -> (out_flat (P', 3) float32, out_offsets (M + 1) int64), (0, 3) when
+    nothing is selected.  Two phases with one 8-byte read-back of P' = out_offsets[M] between them, which waits for the current
+    stream (and one more inside stroke_table when no table is given).  sel_offsets that do not run from 0 to Q without
+    decreasing are refused (ValueError): the check runs on the device and travels with that read-back."""
+    P, N, M, Q, T, (sketch_strokes, stroke_rows, stroke_ends) = _stroke_edit_args(flat, offsets, src, sel_offsets, sel, table)
+    dev = flat.device
+    out_offsets = torch.empty(M + 1, dtype=torch.int64, device=dev)
+    ws, nbytes = _workspace_for("skf_stroke_edit_workspace_bytes", dev, P, N, M, Q)
+    _lib.call("skf_stroke_edit_count", P, _p(sketch_strokes), N, _p(stroke_rows), T, _p(src), _p(sel_offsets), M, _p(sel) if Q else None, Q,
+              0, _p(out_offsets), _p(ws), nbytes, _stream())
+    # the lists must run from 0 to Q without decreasing (overlapping lists would give an entry two writers); checked on the device
+    # and read back with the row count: -1 in its place
+    ordered = (sel_offsets[1:] >= sel_offsets[:-1]).all() & (sel_offsets[0] == 0) & (sel_offsets[-1] == Q)
+    rows = int(torch.where(ordered, out_offsets[-1], -1).item())
+    if rows < 0:
+        raise ValueError("sel_offsets must run from 0 to the number of selected strokes (%d) without decreasing" % Q)
+    if rows >= (1 << 31) - 1:
+        raise ValueError("stroke_edit: the result needs 2^31 rows or more; cut the edit into several calls")
+    out_flat = torch.empty(rows, 3, dtype=torch.float32, device=dev)
+    if rows:
+        _lib.call("skf_stroke_edit_emit", _p(flat), P, _p(sketch_strokes), N, _p(stroke_rows), _p(stroke_ends), T, _p(src), _p(sel_offsets),
+                  M, _p(sel), Q, 0, _p(out_offsets), _p(out_flat), rows, _p(ws), nbytes, _stream())
+    return out_flat, out_offsets
+
+
 ALIGN_MAX_LEN = 512                                              # SKF_ALIGN_MAX_LEN of include/skf.h
 
 
