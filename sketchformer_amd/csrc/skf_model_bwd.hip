@@ -190,6 +190,8 @@ int run_backward(SkfModel* M, hipStream_t s) {
   const bool bott = has_bott(c), cls = has_cls(c), recon = do_recon(c);
   float* enc_out = M->at<float>(P.enc[N - 1].x2);
   const float* pre = bott ? M->at<float>(P.pre) : enc_out;      // pre_decoder (see run_forward)
+  // token mode, two streams: the decoder embedding gradient runs on the side stream (at the end of the decoder loop)
+  const bool dec_emb_on_side = recon && M->sched.side && !c.continuous && P.emb_sort_bytes;
   if (recon) {
   // From the output layer to the decoder embedding every (B * Ld)-row gradient is exactly zero behind a sample's last trained position
   // (skf_row_blocks.hip): the split-arithmetic GEMMs walk the live row blocks only.  Not in continuous mode (its pen-state
@@ -231,7 +233,13 @@ int run_backward(SkfModel* M, hipStream_t s) {
     const bool lead = row_owner_takes_ln(M, w.ln1, ln_oproj_partial_bytes(M, Md), Md, &w.mha1.o, &w.mha2.q);
     if (!lead) SKF_TRY(dense_dgrad(M, w.mha2.q, dq2, d, Md, G, d, 1, nullptr, 0, s));
     SKF_TRY(dense_wgrad(M, w.mha2.kv, pre, L.E, dkv2, 2 * d, Me, s));
-    // (the last layer of the loop runs it on the main stream: its reader follows too soon to gain anything)
+    // (the last layer of the loop runs it on the main stream.  A deferred input gradient leaves with its layer's whole group at the end
+    //  of the layer, and for this layer the reader - the expander backward - follows that point too soon to gain anything.  That is a
+    //  limit of the group mechanism, not of the data: dkv2 is ready as soon as the cross-attention backward above ends.  Letting it
+    //  leave right there - with the five weight gradients queued so far as a group of its own, its ready event riding on the
+    //  cross-attention backward - was built and measured: the 45-us launch left the main stream and the step got 0.012 ms LONGER
+    //  (5 of 6 interleaved rounds): that group then runs beside this layer's self-attention backward and the next fused feed-forward
+    //  launches, which slow down by more than the move saved.  Taken out again; profiles/side_stream_moves_ab.txt)
     if (i == 0) {
       SKF_TRY(M->sched.before_read(M, dpre, s));   // the side-stream writers of the layers above have finished accumulating
       SKF_TRY(dense_dgrad(M, w.mha2.kv, dkv2, 2 * d, Me, dpre, L.E, i != N - 1, nullptr, 0, s));
@@ -250,28 +258,52 @@ int run_backward(SkfModel* M, hipStream_t s) {
     hipEvent_t ready = nullptr;      // not held: the group's event rides on this layer's last launch
     SKF_TRY(with_ready_event(M, !hold, &ready, [&] { return dense_dgrad(M, w.mha1.qkv, dqkv, 3 * d, Md, G2, d, 1, nullptr, 0, s); }));
     float* t = G; G = G2; G2 = t;
+    // Token mode, two streams: the decoder embedding gradient reads G, the input gradient that the launch above has just written, and
+    // only the bucket's reduction - side stream - consumes its result.  It leaves with layer 0's group, as its last launch (behind the
+    // ready event that rides on the launch above), and the group registers G as read by the side stream (before_write) - the
+    // encoder-side backward below keeps out of that buffer.
+    if (i == 0 && dec_emb_on_side) {
+      const float* dx0 = G;
+      char* sorted = M->at<char>(P.emb_sort[1]);
+      float* dtable = M->G(L.dec_emb);
+      const int V = c.vocab_size;
+      M->sched.queue_launch(dx0, [M, sorted, dtable, dx0, B, Ld, V, d, rate, N](hipStream_t on) {
+        return skf_embed_bwd_sorted(sorted, B, Ld, dx0, V, d, dtable, rate, site_dec_embed(N), M->state, on);
+      });
+    }
     if (hold) SKF_TRY(M->sched.hold(M, s));
     else SKF_TRY(M->sched.issue(M, s, ready));
   }
   M->ctx.clear_live();
-  hipEvent_t dec_emb_done = nullptr;
-  // decoder embedding
+  // The step metrics, left here by run_forward: nothing on the device reads M->metrics during the step, so the launch goes to the side
+  // stream.  It reads the token loss sums (main stream) and the class loss sums (side stream, in front of the K|V projections): the
+  // side stream has waited for the ready event of layer 0's group, recorded behind the whole decoder backward and so behind the token
+  // cross-entropy, and is in order behind its own class cross-entropy - no event of its own.  Here and not behind the output layer's
+  // group, which would do for the order: from there to this point the side stream is busy without a break, and whatever is put in
+  // front pushes every layer's weight gradients towards the next fused feed-forward launch (profiles/side_stream_moves_ab.txt).
+  // The step's final join (flush_wgrads) puts the main stream behind this launch: the step still ends with the metrics complete, and
+  // the next step's loss launches - the token loss on the main stream behind that join, the class loss on the in-order side stream -
+  // cannot overtake this read of the four sums, however many steps the host queues without synchronising.
+  if (M->ctx.metrics_deferred) {
+    M->ctx.metrics_deferred = false;
+    SKF_TRY(metrics_update(M, M->sched.side));
+  }
+  // decoder embedding (the continuous form and the unsorted one stay on the main stream: they use small_ws / a memset)
   if (c.continuous) {
     SKF_TRY(skf_embed_continuous_bwd(M->at<float>(P.tar), Le, B, Ld, G, d, M->G(L.dec_embd.w), M->G(L.dec_embd.b), rate,
                                      site_dec_embed(N), M->state, M->at<char>(P.small_ws), P.small_ws_bytes, s));
+  } else if (dec_emb_on_side) {
+    // (issued with layer 0's group above)
+  } else if (P.emb_sort_bytes) {
+    SKF_TRY(skf_embed_bwd_sorted(M->at<char>(P.emb_sort[1]), B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N), M->state, s));
   } else {
-    if (P.emb_sort_bytes) {
-      // the bucket's reduction (side stream) waits for this launch's own signal
-      SKF_TRY(with_ready_event(M, M->n_buckets == 2, &dec_emb_done, [&] {
-        return skf_embed_bwd_sorted(M->at<char>(P.emb_sort[1]), B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N), M->state, s);
-      }));
-    } else {
-      SKF_HIP(hipMemsetAsync(M->G(L.dec_emb), 0, (size_t)c.vocab_size * d * sizeof(float), s));
-      SKF_TRY(skf_embed_bwd(tar, Le, B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N), M->state, s));
-    }
+    SKF_HIP(hipMemsetAsync(M->G(L.dec_emb), 0, (size_t)c.vocab_size * d * sizeof(float), s));
+    SKF_TRY(skf_embed_bwd(tar, Le, B, Ld, G, c.vocab_size, d, M->G(L.dec_emb), rate, site_dec_embed(N), M->state, s));
   }
-  // every gradient of [decoder embedding .. output layer] is issued: first bucket of the flat buffer
-  if (M->n_buckets == 2) SKF_TRY(flush_wgrads(M, s, 0, false, true, dec_emb_done));
+  // every gradient of [decoder embedding .. output layer] is issued: first bucket of the flat buffer.  With the embedding gradient on
+  // the side stream, the reduction and bucket_ready[0] follow it and layer 0's group on that in-order stream, and the group's ready
+  // event was recorded behind every main-stream launch of the bucket (the LayerNorm partials): no hand-over.
+  if (M->n_buckets == 2) SKF_TRY(flush_wgrads(M, s, 0, false, true, dec_emb_on_side));
   SKF_TRY(M->sched.before_read(M, dpre, s));     // the deferred K/V-projection input gradients (side stream) are complete
   }   // recon
   const int E = L.E, Ua = L.Ua, U = c.lowerdim, NB = c.class_buffer_layers;
@@ -323,6 +355,11 @@ int run_backward(SkfModel* M, hipStream_t s) {
       SKF_TRY(dense_dgrad(M, L.bott_e, demb, U, B, M->at<float>(P.dpooled), d, 0, nullptr, 0, s));
       dpool = M->at<float>(P.dpooled);
     }
+    // The side stream's decoder embedding gradient reads G behind layer 0's weight gradients, long after the main stream is here
+    // (even as the FIRST launch of that group it held the pooling backward up for 16 us: profiles/side_stream_moves_ab.txt).  So the
+    // encoder-side gradient alternates between G2 - free, its last reader was layer 0's self-attention LayerNorm backward on this
+    // stream - and the plan's third buffer, and the main stream never waits for that read.
+    if (dec_emb_on_side) { G = G2; G2 = M->at<float>(P.gC); }
     SKF_TRY(M->sched.before_write(M, G, s));
     if (defer_sums) {
       SKF_TRY(skf_pool_bwd_partials(M->at<float>(P.u), M->P(L.bott_v), enc_out, M->at<float>(P.pool_a), dpool, B, Le, Ua, d, G, pvp, s));

@@ -21,7 +21,27 @@ int classify_fwd(SkfModel* M, bool training, hipStream_t s) {
   return dense_fwd(M, L.cls, fc, c.batch, M->at<float>(P.cls_logits), 0, s);
 }
 
+// The step metrics from the loss and hit sums of the two heads; absent heads contribute 0 rows: their loss is 0 in total_loss
+// (sum(all_losses), models/sketchformer.py:345)
+int metrics_update(SkfModel* M, hipStream_t s) {
+  const SkfConfig& c = M->cfg;
+  const Plan& P = M->plan;
+  const bool recon = do_recon(c);
+  const float* recon_scalar = recon && c.continuous ? M->at<float>(P.cont_scal) + 3 : nullptr;
+  return skf_metrics_update(M->at<float>(P.recon_loss), M->at<float>(P.recon_hit), recon ? c.batch * (c.seq_len - 1) : 0, c.recon_weight,
+                            M->at<float>(P.cls_loss), M->at<float>(P.cls_hit), has_cls(c) ? c.batch : 0, c.class_weight, recon_scalar,
+                            M->metrics, s);
+}
+
 namespace {
+// The class cross-entropy of a step with a loss: loss and hit sums, probabilities, and d(logits) in place of the logits
+int class_ce_with_grad(SkfModel* M, hipStream_t s) {
+  const SkfConfig& c = M->cfg;
+  const Plan& P = M->plan;
+  return skf_softmax_ce(M->at<float>(P.cls_logits), c.n_classes, c.batch, c.n_classes, M->at<long long>(P.labels), 1, 1, 0, 0,
+                        c.class_weight / (float)c.batch, M->at<float>(P.cls_loss), M->at<float>(P.cls_hit), M->at<float>(P.cls_probs), 1, s);
+}
+
 // The feed-forward block as one launch per direction (skf_ffn_fused.hip) where that kernel exists (d_model 128, dff 512, split
 // arithmetic) unless SKF_MODEL_FFN_LAUNCHES asks for the separate launches.  Its pre-split weight images are rebuilt from the fp32
 // masters at the start of every forward (one or two launches for all layers: whoever changed the weights - the optimizer, a
@@ -199,7 +219,11 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
     if (c.attn_version == 2)   // SelfAttnV2: o = embeding_layer(o) (builders/layers/transformer.py:128-129)
       SKF_TRY(dense_fwd(M, L.bott_e, M->at<float>(P.pooled), B, M->at<float>(P.emb), 0, s));
   }
-  if (cls) SKF_TRY(classify_fwd(M, training, s));
+  // The train step with a side stream and a decoder: the class head, its cross-entropy and the metrics launch have no main-stream
+  // consumer before the classifier backward and go to the side stream (below).  Without a decoder there is no decoder-input event
+  // and the side stream does nothing during the forward: the heads stay here, like everywhere without a side stream or a loss.
+  const bool heads_on_side = with_loss && recon && M->sched.side;
+  if (cls && !heads_on_side) SKF_TRY(classify_fwd(M, training, s));
   if (encoder_only || !recon) {
     if (encoder_only || !with_loss) {   // encode_from_seq / predict_class (models/sketchformer.py:162-168,223-228): class probabilities only
       if (!cls) return SKF_OK;
@@ -242,6 +266,18 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
     SKF_CHECK_ARG(dec_in_ready && kv_done && kv_first, "event allocation failed");
     if (!dec_in_recorded) SKF_HIP(hipEventRecord(dec_in_ready, s));
     SKF_HIP(hipStreamWaitEvent(M->sched.side, dec_in_ready, 0));
+    // The class head and its cross-entropy (train step): dec_in_ready rides on the expander launch (or is recorded above), which
+    // follows the pooling / embedding launches on the main stream, so the embedding is visible behind this wait.  In FRONT of the K|V
+    // projections, not behind the first one: the two launches take ~21 us and the first projection then still ends ~50 us before the
+    // first cross-attention asks for it (profiles/side_stream_moves_ab.txt), and this way one argument orders the main stream's
+    // readers in every structure - the main stream waits for kv_first (recorded below, behind these launches on the in-order side
+    // stream) in front of the first layer's cross-attention, one layer included, long before the classifier backward reads dcls, the
+    // class-buffer activations, cls_loss or cls_hit.  What they overwrite belongs to the previous step, whose final join put both
+    // streams behind its last reader.
+    if (cls && heads_on_side) {
+      SKF_TRY(classify_fwd(M, training, M->sched.side));
+      SKF_TRY(class_ce_with_grad(M, M->sched.side));
+    }
     for (int i = 0; i < N; ++i) {
       SKF_TRY(dense_fwd(M, L.dec[i].mha2.kv, pre, Me, M->at<float>(P.dec[i].kv2), 0, M->sched.side));
       if (i == 0 && kv_first != kv_done) SKF_HIP(hipEventRecord(kv_first, M->sched.side));
@@ -295,25 +331,19 @@ int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool 
   const long long* labels = M->at<long long>(P.labels);
   if (with_loss) {
     // tar_real = tar[:, 1:]  -> target offset 1 within rows of stride L
-    const float* recon_scalar = nullptr;
     if (recon) {
       if (c.continuous) {
         SKF_TRY(skf_continuous_loss(M->at<float>(P.logits), tarf, Le, Ld, 1, Md, c.recon_weight, M->at<float>(P.recon_loss),
                                     M->at<float>(P.recon_hit), M->at<float>(P.row_mask), M->at<float>(P.cont_scal), 1, s));
-        recon_scalar = M->at<float>(P.cont_scal) + 3;
       } else {
         SKF_TRY(skf_softmax_ce(M->at<float>(P.logits), c.vocab_size, Md, c.vocab_size, tar, Le, Ld, 1, 1,
                                c.recon_weight / (float)Md, M->at<float>(P.recon_loss), M->at<float>(P.recon_hit), nullptr, 1, s));
       }
     }
-    if (cls)
-      SKF_TRY(skf_softmax_ce(M->at<float>(P.cls_logits), c.n_classes, B, c.n_classes, labels, 1, 1, 0, 0,
-                             c.class_weight / (float)B, M->at<float>(P.cls_loss), M->at<float>(P.cls_hit),
-                             M->at<float>(P.cls_probs), 1, s));
-    // absent heads contribute 0 rows: their loss is 0 in total_loss (sum(all_losses), models/sketchformer.py:345)
-    SKF_TRY(skf_metrics_update(M->at<float>(P.recon_loss), M->at<float>(P.recon_hit), recon ? Md : 0, c.recon_weight,
-                               M->at<float>(P.cls_loss), M->at<float>(P.cls_hit), cls ? B : 0, c.class_weight, recon_scalar,
-                               M->metrics, s));
+    if (cls && !heads_on_side) SKF_TRY(class_ce_with_grad(M, s));
+    // (two streams: run_backward issues it on the side stream, behind the first wait that orders that stream after the token loss)
+    if (heads_on_side) M->ctx.metrics_deferred = true;
+    else SKF_TRY(metrics_update(M, s));
   } else if (cls) {
     SKF_TRY(skf_softmax_ce(M->at<float>(P.cls_logits), c.n_classes, B, c.n_classes, labels, 1, 1, 0, 0, 0.f,
                            M->at<float>(P.cls_loss), M->at<float>(P.cls_hit), M->at<float>(P.cls_probs), 0, s));

@@ -16,6 +16,7 @@
 #include <vector>
 #include <map>
 #include <algorithm>
+#include <functional>
 #include "skf_common.h"
 #include "skf_attention_params.h"
 #include "skf_decode_fused.h"
@@ -178,8 +179,9 @@ struct SideSched {
   long side_seq = 0, side_waited = 0;
   std::map<const void*, SideEvent> pending_readers;    // buffer -> completion event of its last side-stream reader
   std::map<const void*, SideEvent> pending_writers;    // buffers a side-stream dgrad still writes
-  // kind 0: dW = X^T dY (+ bias grad); kind 1: an input gradient nobody on the main stream needs soon (dx (+)= dY W^T)
-  struct Queued { DenseP w; const float* x; int ldx; const float* dy; int lddy; int rows; int kind = 0; float* dx = nullptr; int lddx = 0; int accumulate = 0; const int* blocks32 = nullptr; };
+  // kind 0: dW = X^T dY (+ bias grad); kind 1: an input gradient nobody on the main stream needs soon (dx (+)= dY W^T);
+  // kind 2: one launch `run` that reads `dy` and whose result only the side stream consumes (the decoder embedding gradient)
+  struct Queued { DenseP w; const float* x; int ldx; const float* dy; int lddy; int rows; int kind = 0; float* dx = nullptr; int lddx = 0; int accumulate = 0; const int* blocks32 = nullptr; std::function<int(hipStream_t)> run; };
   std::vector<Queued> wq;               // the current layer's group, not yet issued
   std::vector<Queued> wq_held;          // the PREVIOUS layer's group, held back until the next layer's first kernel is queued (hold)
 
@@ -196,6 +198,7 @@ struct SideSched {
   void begin_backward() { wq.clear(); wq_held.clear(); pending_readers.clear(); pending_writers.clear(); rewind_events(); }
   void queue_wgrad(const DenseP& w, const float* x, int ldx, const float* dy, int lddy, int rows, const int* blocks32) { wq.push_back(Queued{w, x, ldx, dy, lddy, rows, 0, nullptr, 0, 0, blocks32}); }
   void queue_dgrad(const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate) { wq.push_back(Queued{w, nullptr, 0, dy, lddy, rows, 1, dx, lddx, accumulate}); }
+  void queue_launch(const float* reads, std::function<int(hipStream_t)> run) { Queued q{}; q.dy = reads; q.kind = 2; q.run = std::move(run); wq.push_back(std::move(q)); }
   bool holding() const { return !wq_held.empty(); }
   int hold(SkfModel* M, hipStream_t s);           // the queued group becomes the held one
   // The queued group goes out (behind the held one); ready_recorded: an event that already marks "the main stream is here" (the
@@ -230,6 +233,7 @@ struct StepCtx {
   bool lists_built = false;             // this step's lists are in P.live16 / P.live32 (issued, not necessarily complete)
   bool masks_staged = false;            // the padding masks of this call were written by its staging launch (stage_inputs)
   bool ffn_fused = false;               // the feed-forward blocks run as one launch per direction (skf_ffn_fused.hip); set per forward
+  bool metrics_deferred = false;        // train step, two streams, with a decoder: run_forward left skf_metrics_update to run_backward (side stream)
   hipEvent_t last_ready = nullptr;      // ffn_ln_bwd: the event attached to its fused launch (valid until the caller's next main-stream launch)
 
   void reset() { *this = StepCtx(); }
@@ -329,7 +333,7 @@ void* hbits_of(SkfModel* M, size_t off, int rows);
 int dense_fwd_relu_bits(SkfModel* M, const DenseP& w, const float* x, int rows, float* y, void* bits, hipStream_t s);
 int dense_fwd_ld(SkfModel* M, const DenseP& w, const float* x, int ldx, int rows, float* y, int ldy, int act, hipStream_t s);
 int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const float* dy, int lddy, int rows, hipStream_t s);
-int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_queued = true, hipEvent_t main_here = nullptr);
+int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_queued = true, bool side_behind_main = false);
 int dense_dgrad(SkfModel* M, const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate,
                 const float* relu_src, int ld_relu, hipStream_t s, const void* relu_bits = nullptr);
 int dense_dgrad_deferred(SkfModel* M, const DenseP& w, const float* dy, int lddy, int rows, float* dx, int lddx, int accumulate,
@@ -337,6 +341,7 @@ int dense_dgrad_deferred(SkfModel* M, const DenseP& w, const float* dy, int lddy
 
 // ------------------------------------------------------------------ skf_model_fwd.hip, skf_model_bwd.hip
 int classify_fwd(SkfModel* M, bool training, hipStream_t s);
+int metrics_update(SkfModel* M, hipStream_t s);
 int forward_preamble(SkfModel* M, bool with_backward, bool encoder_only, hipStream_t s, hipEvent_t masks_ready = nullptr);
 int run_forward(SkfModel* M, bool training, bool with_loss, hipStream_t s, bool encoder_only = false);
 int run_backward(SkfModel* M, hipStream_t s);

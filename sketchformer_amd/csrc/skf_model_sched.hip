@@ -147,7 +147,7 @@ int SideSched::issue(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool
   std::vector<const Queued*> prob_q;
   for (const auto& q : group) {
     const DenseP& w = q.w;
-    if (q.kind == 1) continue;
+    if (q.kind != 0) continue;
     if ((double)w.in * w.out * q.rows <= 33554432.0) {
       // batch-sized problems (classifier, class buffers, SelfAttnV2 projection): one small-GEMM launch, no split-K slab
       SKF_TRY(dense_wgrad_on(M, w, q.x, q.ldx, q.dy, q.lddy, q.rows, ws));
@@ -179,6 +179,10 @@ int SideSched::issue(SkfModel* M, hipStream_t s, hipEvent_t ready_recorded, bool
     SKF_TRY(M->red.add(d, skf_splitk_reduce_blocks(w.in, w.out)));
   }
   M->red.side_used = true;                                         // (the slabs are reduced by the batched launch either way)
+  // the single launches that leave with the group (the decoder embedding gradient) go last: in front they would push the weight
+  // gradients towards the next fused feed-forward launch of the main stream (see issue_held)
+  for (const auto& q : group)
+    if (q.kind == 2) SKF_TRY(q.run(ws));
   if (on_main) return SKF_OK;                                  // same stream as every later reader / writer of the operands: nothing to track
   SKF_HIP(hipEventRecord(done, side));
   const long done_seq = ++side_seq;
@@ -207,7 +211,7 @@ int dense_wgrad(SkfModel* M, const DenseP& w, const float* x, int ldx, const flo
 }
 // Reduce the split-K partials of the wgrads issued since the last flush (one batched launch on the side stream) and
 // mark gradient bucket `bucket` complete.  final = the main stream waits for the side stream (before the optimizer).
-int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_queued, hipEvent_t main_here) {
+int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_queued, bool side_behind_main) {
   if (issue_queued) SKF_TRY(M->sched.issue(M, s));      // (false: reduce what has been issued; queued / held groups stay where they are)
   const size_t begin = M->red.begin(), end = M->red.end();
   hipStream_t ready_on = s;
@@ -230,10 +234,14 @@ int flush_wgrads(SkfModel* M, hipStream_t s, int bucket, bool final, bool issue_
         return skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->red.blocks(), s);
       }));
     } else {
-      hipEvent_t em = main_here ? main_here : M->sched.take_event();      // (main_here: already the completion signal of the main stream's last launch)
-      SKF_CHECK_ARG(em, "event allocation failed");
-      if (!main_here) SKF_HIP(hipEventRecord(em, s));
-      SKF_HIP(hipStreamWaitEvent(side, em, 0));
+      // (side_behind_main: the last group's ready event was recorded behind every main-stream launch of the bucket, and the side
+      //  stream, in order, is behind that group: nothing to hand over)
+      if (!side_behind_main) {
+        hipEvent_t em = M->sched.take_event();
+        SKF_CHECK_ARG(em, "event allocation failed");
+        SKF_HIP(hipEventRecord(em, s));
+        SKF_HIP(hipStreamWaitEvent(side, em, 0));
+      }
       SKF_TRY(skf_splitk_reduce_batch(M->at<SkfReduceDesc>(M->plan.descs) + begin, (int)(end - begin), M->red.blocks(), side));
       ready_on = side;
     }

@@ -1263,7 +1263,7 @@ static int embed_bwd_sorted_launch(const void* ws, int B, int L, const void* dx,
   const int* order = w.order;
   SkfProfScope ps((hipStream_t)stream, dx_bf16 ? "embed_bwd_sorted_bf16" : "embed_bwd_sorted", 0.0,
                   (dx_bf16 ? 2.0 : 4.0) * rows * d + 4.0 * (double)vocab * d);
-  // tail audit (both): parked by run_backward around skf_embed_bwd_sorted (two buckets); the bf16 entry point has no parker; one launch each
+  // tail audit (both): nobody parks (the fp32 step's decoder-side call runs inside SideSched::issue's shield); one launch each
   if (dx_bf16)
     SKF_LAUNCH_TAIL(embed_bwd_sorted_kernel<skf_bf16>, dim3((unsigned)maxc), dim3(256), (size_t)3 * d * sizeof(float), (hipStream_t)stream,
                        hdr, chunks, order, (const skf_bf16*)dx, d, dtable, rate, site, (const SkfStepState*)step_state, w.partial, w.done);
