@@ -1166,6 +1166,50 @@ int skf_polyline_resample_emit(const float* xy, int ldp, long long P, const long
 int skf_polyline_resample_n(const float* xy, int ldp, long long P, const long long* stroke_offsets, int S, int n_out, float* out_xy,
                             void* workspace, size_t workspace_bytes, skf_stream_t stream);
 
+/* ------------------------------------------------------------------ Path flattening (lines and cubic Bezier segments -> polylines)
+ * The door for vector drawings that are not polylines: SVG paths (sketchformer_amd/svg.py parses them on the host into lines and
+ * cubics; quadratics and arcs arrive as cubics) become polylines under a stated error bound, and go straight into skf_rdp_f32 and
+ * skf_polyline_resample_*.  The reference samples a path by its length through svgpathtools (utils/skt_tools.py: read_svg); the
+ * specification here is the project's own host restatement (tests/flatten_reference.py) and the results are BIT-EQUAL to it.
+ * Inputs.  ctrl (G, 4, 2) fp64: the control points p0 .. p3 of G segments, absolute (x, y).  kind (G int32): 1 = cubic; 0 = line,
+ *   of which only p0 and p3 count; ANY OTHER VALUE IS TREATED AS 0.  path_offsets (S + 1 int64, on the device): subpath s owns the
+ *   segments [path_offsets[s], path_offsets[s + 1]); the caller checks them, the kernels clamp every range to [0, G] and never
+ *   trust an offset as an index.  tol > 0, in the units of ctrl; the host forms c = (16 / 9) * tol^2 once in fp64 (16.0 / 9.0,
+ *   tol * tol, then their product: three roundings).
+ * Pieces per segment, n.  A line has n = 1.  A cubic: ax = (x0 - 2 x1) + x2, bx = (x1 - 2 x2) + x3, ay and by likewise;
+ *   dd = max(ax * ax + ay * ay, bx * bx + by * by), every fp64 operation rounded on its own, a NaN on either side giving a NaN.
+ *   n is the smallest integer in [1, SKF_FLATTEN_MAX_N] with (double)(n * n) * (double)(n * n) * c >= dd, and SKF_FLATTEN_MAX_N if
+ *   there is none (so for a NaN or an infinite dd).  n^4 is exact in fp64 up to 2^13 and the test is monotone in n: how n is
+ *   searched for does not change it.  It is the bound of uniform subdivision, 0.75 * M / n^2 <= tol with M = max(|a|, |b|), the
+ *   second differences of the control polygon, without a square root or a division.
+ * Rows.  A subpath with at least one segment gives 1 + sum(n) rows: first (float) p0 of its first segment; then segment k gives n
+ *   rows, j = 1 .. n.  For j < n: t = (double) j / (double) n and de Casteljau with lerp(a, b) = a + t * (b - a), six lerps a
+ *   coordinate in the order q0 = lerp(p0, p1), q1 = lerp(p1, p2), q2 = lerp(p2, p3), r0 = lerp(q0, q1), r1 = lerp(q1, q2),
+ *   s = lerp(r0, r1): every operation rounded to fp64 on its own (no fused multiply-add), then s is cast once to fp32.  Row n is
+ *   (float) p3, copied and not evaluated: a join repeats no row and skips none, whether or not p3 of one segment equals p0 of the
+ *   next (only the first segment's p0 is ever read as a row).  An empty subpath gives no row.
+ * Nothing here allocates, synchronises with the host or uses an atomic; every output element has one writer per launch; two calls
+ * on the same inputs agree bit for bit and a subpath's rows do not depend on the rest of the batch.  Subpath length is not limited.
+ * skf_path_flatten_count: the count launch (one wavefront per subpath: n per segment, a wave scan with a carry from one tile of 64
+ *   segments to the next, the inclusive running sum of n for every segment into the workspace, the subpath's row count) and the
+ *   counts -> offsets scan.  Afterwards out_offsets (S + 1 int64) holds the offsets of the flattened subpaths, out_offsets[S] = the
+ *   number of output rows P'.  A subpath's count saturates at 2^31 - 1: P' >= 2^31 - 1 means that the result does not fit and must
+ *   not be emitted.
+ * skf_path_flatten_emit: the emit launch.  Same ctrl, kind, G, path_offsets, S, tol and the workspace exactly as _count left it;
+ *   out_offsets as _count wrote them.  Row out_offsets[s] + m of out_xy (out_rows, 2) receives row m of subpath s: one lane per
+ *   row, consecutive lanes consecutive rows, the segment found by binary search over the subpath's slice of the running sums.
+ *   out_rows is the capacity: rows at or past it are not written, nor is any row a subpath does not own.
+ * Limits (SKF_EINVAL): a null pointer, S >= 1, 1 <= G < 2^31, tol finite and > 0, 1 <= out_rows < 2^31 (so P' < 2^31), ctrl,
+ *   path_offsets, out_offsets and out_xy not 8-byte, kind not 4-byte aligned, a workspace below
+ *   skf_path_flatten_workspace_bytes(G, S) bytes (0 = bad sizes) or not 16-byte aligned. */
+#define SKF_FLATTEN_MAX_N 4096
+size_t skf_path_flatten_workspace_bytes(long long G, int S);
+int skf_path_flatten_count(const double* ctrl, const int* kind, long long G, const long long* path_offsets, int S, double tol,
+                           long long* out_offsets, void* workspace, size_t workspace_bytes, skf_stream_t stream);
+int skf_path_flatten_emit(const double* ctrl, const int* kind, long long G, const long long* path_offsets, int S, double tol,
+                          const long long* out_offsets, float* out_xy, long long out_rows, void* workspace, size_t workspace_bytes,
+                          skf_stream_t stream);
+
 /* ------------------------------------------------------------------ Stroke edits (permute, reverse, drop)
  * New sketches built out of the strokes of old ones: the strokes in any order, forwards or backwards, some left out or repeated,
  * the pen jumps between them recomputed.  It is what the reference loader's shuffle_stroke option does on the host through

@@ -306,6 +306,9 @@ SIGNATURES = {
     "skf_polyline_resample_count": (_I, [_P, _I, _L, _P, _I, _D, _P, _P, _Z, _P]),
     "skf_polyline_resample_emit": (_I, [_P, _I, _L, _P, _I, _D, _P, _P, _L, _P, _Z, _P]),
     "skf_polyline_resample_n": (_I, [_P, _I, _L, _P, _I, _I, _P, _P, _Z, _P]),
+    "skf_path_flatten_workspace_bytes": (_Z, [_L, _I]),
+    "skf_path_flatten_count": (_I, [_P, _P, _L, _P, _I, _D, _P, _P, _Z, _P]),
+    "skf_path_flatten_emit": (_I, [_P, _P, _L, _P, _I, _D, _P, _P, _L, _P, _Z, _P]),
     "skf_stroke_table_workspace_bytes": (_Z, [_L, _I]),
     "skf_stroke_table": (_I, [_P, _L, _P, _I, _U, _P, _P, _P, _P, _Z, _P]),
     "skf_stroke_edit_workspace_bytes": (_Z, [_L, _I, _I, _L]),

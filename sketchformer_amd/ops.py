@@ -1195,6 +1195,60 @@ def polyline_resample_n(xy, stroke_offsets, n_out):
     return out
 
 
+FLATTEN_MAX_N = 4096                                             # SKF_FLATTEN_MAX_N of include/skf.h
+
+
+def _flatten_args(ctrl, kind, path_offsets, who):
+    """The checks the flattening entry points share -> (G, S)"""
+    _p(ctrl); _p(kind); _p(path_offsets)                         # CPU tensors: SkfError before anything is allocated
+    if ctrl.dtype != torch.float64 or ctrl.dim() != 3 or tuple(ctrl.shape[1:]) != (4, 2) or not ctrl.is_contiguous():
+        raise TypeError("ctrl must be a contiguous float64 tensor of shape (G, 4, 2)")
+    if kind.dtype != torch.int32 or kind.dim() != 1 or kind.shape[0] != ctrl.shape[0] or not kind.is_contiguous() \
+            or kind.device != ctrl.device:
+        raise TypeError("kind must be a contiguous int32 tensor of shape (G,) on the device of ctrl")
+    return _ragged_offsets(path_offsets, ctrl, who, names=("path_offsets", "S", "ctrl", "subpath"))
+
+
+def _flatten_tol(tol):
+    tol = float(tol)
+    if not 0.0 < tol < float("inf"):                             # (false for a NaN)
+        raise ValueError("tol must be finite and above 0 (got %r)" % tol)
+    return tol
+
+
+def path_flatten_offsets(ctrl, kind, path_offsets, tol, return_workspace=False):
+    """The count phase of path_flatten alone (skf_path_flatten_count): -> out_offsets (S + 1) int64 on the device, the offsets of
+    the flattened subpaths, out_offsets[S] = the number of rows path_flatten would return.  Nothing is read back.
+    return_workspace: also (workspace, its size), holding the running piece counts the emit phase reads."""
+    G, S = _flatten_args(ctrl, kind, path_offsets, "path_flatten")
+    tol = _flatten_tol(tol)
+    out_offsets = torch.empty(S + 1, dtype=torch.int64, device=ctrl.device)
+    ws, nbytes = _workspace_for("skf_path_flatten_workspace_bytes", ctrl.device, G, S)
+    _lib.call("skf_path_flatten_count", _p(ctrl), _p(kind), G, _p(path_offsets), S, tol, _p(out_offsets), _p(ws), nbytes, _stream())
+    return (out_offsets, ws, nbytes) if return_workspace else out_offsets
+
+
+def path_flatten(ctrl, kind, path_offsets, tol):
+    """S subpaths of lines and cubic Bezier segments flattened to polylines that stay within `tol` of the curves
+    (skf_path_flatten_count / _emit), bit-equal to the host restatement of the rule in include/skf.h.  ctrl (G, 4, 2) float64
+    control points p0 .. p3, absolute; kind (G,) int32, 1 = cubic, anything else a line from p0 to p3; path_offsets (S + 1) int64
+    on the same device, non-decreasing from 0 to G; tol finite, > 0, in the units of ctrl.  -> (out_xy (P', 2) float32, out_offsets
+    (S + 1) int64): a subpath gives 1 + the sum of its segments' piece counts rows, the segment ends bit for bit; an empty one
+    gives none.  The pair is a valid (xy, stroke_offsets) for rdp_keep, polyline_resample and polyline_resample_n.  Two phases with
+    one 8-byte read-back of P' = out_offsets[S] between them, which waits for the current stream: the rows cannot be allocated
+    before their number is known."""
+    G, S = _flatten_args(ctrl, kind, path_offsets, "path_flatten")
+    out_offsets, ws, nbytes = path_flatten_offsets(ctrl, kind, path_offsets, tol, return_workspace=True)
+    rows = int(out_offsets[-1].item())
+    if rows >= (1 << 31) - 1:
+        raise ValueError("path_flatten: the result needs 2^31 rows or more; cut the batch or use a larger tol")
+    out_xy = torch.empty(rows, 2, dtype=torch.float32, device=ctrl.device)
+    if rows:
+        _lib.call("skf_path_flatten_emit", _p(ctrl), _p(kind), G, _p(path_offsets), S, float(tol), _p(out_offsets), _p(out_xy), rows,
+                  _p(ws), nbytes, _stream())
+    return out_xy, out_offsets
+
+
 def stroke_table(flat, offsets):
     """The strokes of a ragged batch of stroke-3 sketches (skf_stroke_table; the rule is in include/skf.h).  flat (P, 3) float32
     and offsets (N + 1) int64 as for sketch_encode.  -> (sketch_strokes (N + 1) int64: sketch s owns the global strokes
