@@ -403,6 +403,7 @@ int skf_adam_step(float* w, const float* g, float* m, float* v, size_t n, const 
 /* tf.keras.optimizers.SGD(lr_schedule, momentum), nesterov=False: velocity = momentum*velocity - lr*g*grad_scale; w += velocity */
 int skf_sgd_momentum_step(float* w, const float* g, float* velocity, size_t n, const void* step_state, float grad_scale,
                           float momentum, skf_stream_t stream);
+
 /* y = inverted dropout of x (n floats, y may alias x) with the mask of (step key, site, element index);
  * applied to an upstream gradient it is the backward.  rate 0 = copy. */
 int skf_dropout(const float* x, float* y, size_t n, float rate, unsigned site, const void* step_state, skf_stream_t stream);
@@ -727,6 +728,74 @@ int skf_model_grad_buckets(SkfModel* m, int max_buckets, size_t* offsets_host, s
 int skf_model_wait_grad_bucket(SkfModel* m, int bucket, skf_stream_t stream);
 int skf_model_apply_gradients_range(SkfModel* m, size_t offset, size_t count, float grad_scale, int last,
                                     skf_stream_t stream);
+
+/* ------------------------------------------------------------------ gradient norms and clipping (skf_gradnorm.hip)
+ * tf.keras optimizers' clipnorm / global_clipnorm / clipvalue, a gradient-norm read-out and a guard against non-finite gradients,
+ * over ANY flat fp32 buffer described by SkfParamEntry rows (name unused; offset, rows, cols, row_stride as in the model's table:
+ * strided views are read as such, floats between entries are never read).  Everything the step decides is decided on the device.
+ *
+ * Segment plan: the host cuts every entry into chunks of SKF_SEGMENT_CHUNK logical elements (row-major; the last chunk of an entry
+ *   is ragged) - a constant, so no result depends on the grid or the device.  skf_segment_plan_chunks -> the chunk count (negative:
+ *   error); skf_segment_plan_build fills skf_segment_plan_bytes(n_entries, n_chunks) bytes of HOST memory, which the caller copies
+ *   to the device (16-byte aligned) once per layout.  Limits (SKF_EINVAL): offset >= 0, rows, cols >= 1, row_stride >= cols,
+ *   rows * cols < 2^31 - SKF_SEGMENT_CHUNK.
+ * skf_segment_norms: two launches.  (1) one workgroup per chunk: fp64 sum of squares (16-byte loads where offset, cols and
+ *   row_stride are multiples of 4 floats or the entry is contiguous; scalar loads otherwise and for tails) and the count of
+ *   non-finite elements, reduced in a fixed order, no atomics.  (2) one workgroup folds the partials of an entry in chunk order and
+ *   the entries in table order and writes `stats`, skf_segment_stats_floats(E) = 8 + 2 E 4-byte words:
+ *     [0] f32 global norm = (float)(sqrt(sum) * grad_scale)   [1] f32 applied global scale   [2] u32 non-finite elements
+ *     [3] u32 skip flag = skip_nonfinite && [2] != 0          [4] u32 skipped total (ONLY the clipped sweeps add to it; zero it once)
+ *     [5..7] reserved   [8 .. 8+E) f32 per-entry norms   [8+E .. 8+2E) f32 per-entry scales
+ *   grad_scale is a factor on the norms (1/world_size under data parallelism); the buffer itself is not rescaled.
+ *   Scales, fp32, each operation rounded once: SKF_CLIP_GLOBAL  [1] = c / max(norm, c), entry scales 1;
+ *   SKF_CLIP_PER_VARIABLE  s_e = c / max(norm_e, c), [1] = 1; SKF_CLIP_NONE  all 1 (norms only).  norm <= c gives exactly 1.
+ *   workspace: skf_segment_norms_workspace_bytes(E, n_chunks), 256-byte aligned.  SKF_EINVAL: threshold <= 0 or non-finite in a norm mode.
+ * skf_segment_scale: one launch over the plan, every element of entry e times scales[e] in place; skip != NULL and *skip != 0:
+ *   nothing is written.
+ * skf_gradient_clip_validate: the rule of the settings (host only): at most one of {per-variable, global, clipvalue > 0}; the
+ *   threshold of a norm mode and a clipvalue finite and > 0 (clipvalue 0 = off). */
+#define SKF_SEGMENT_CHUNK 16384
+#define SKF_CLIP_NONE 0
+#define SKF_CLIP_PER_VARIABLE 1
+#define SKF_CLIP_GLOBAL 2
+int skf_segment_plan_chunks(const SkfParamEntry* entries_host, int n_entries);
+size_t skf_segment_plan_bytes(int n_entries, int n_chunks);
+int skf_segment_plan_build(const SkfParamEntry* entries_host, int n_entries, void* plan_host, size_t plan_bytes);
+size_t skf_segment_norms_workspace_bytes(int n_entries, int n_chunks);
+size_t skf_segment_stats_floats(int n_entries);
+int skf_gradient_clip_validate(int mode, float threshold, float clipvalue);
+int skf_segment_norms(const float* flat, const void* plan_dev, int n_entries, int n_chunks, float grad_scale, int mode,
+                      float threshold, int skip_nonfinite, void* workspace, size_t workspace_bytes, float* stats,
+                      skf_stream_t stream);
+int skf_segment_scale(float* flat, const void* plan_dev, int n_entries, int n_chunks, const float* scales, const void* skip,
+                      skf_stream_t stream);
+/* The sweeps with device-side control: skf_adam_step / skf_sgd_momentum_step on the gradient
+ *   gg = (g * grad_scale) * s;  clipvalue > 0: gg = min(max(gg, -clipvalue), clipvalue)
+ * s = *scale (device float; NULL = 1), every product rounded on its own: the update equals the plain sweep over a gradient scaled /
+ * clamped in memory bit for bit.  skip (NULL = never): two device words {flag, total}, e.g. stats + 3: with the flag set the sweep
+ * writes nothing, `iterations` is not advanced and the total goes up by one.  advance != 0: the sweep also closes the step
+ * (iterations += 1, what skf_step_epilogue does) unless it is skipped. */
+int skf_adam_step_clipped(float* w, const float* g, float* m, float* v, size_t n, void* step_state, float grad_scale,
+                          const float* scale, float clipvalue, void* skip, float beta1, float beta2, float eps, int advance,
+                          skf_stream_t stream);
+int skf_sgd_momentum_step_clipped(float* w, const float* g, float* velocity, size_t n, void* step_state, float grad_scale,
+                                  const float* scale, float clipvalue, void* skip, float momentum, int advance,
+                                  skf_stream_t stream);
+/* The train step with the above.  skf_model_set_gradient_clip configures THIS model: mode / threshold / clipvalue as in
+ * skf_gradient_clip_validate (SKF_EINVAL with a message otherwise), skip_nonfinite: a step whose gradient holds an inf or NaN changes
+ * nothing (parameters, moments, iterations) and counts as skipped; monitor: compute the norms even when nothing else needs them.
+ * workspace: skf_model_clip_workspace_bytes(cfg) bytes of caller-owned device memory, 256-byte aligned, which starts with the stats
+ * words of skf_segment_norms for the model's entry table (skf_model_param_entries order) - read them from there, no call needed; the
+ * call uploads the segment plan behind them and zeroes the stats (it synchronises the device: a step in flight may read the old
+ * settings).  Mode none, clipvalue 0, skip_nonfinite 0 and monitor 0 switch everything off again (workspace may be NULL).
+ * skf_model_apply_gradients_clipped: skf_model_apply_gradients for a configured model (SKF_EINVAL for an unconfigured one): the two
+ * norm launches (not with clipvalue alone), the segment scale in per-variable mode, then ONE clipped sweep that also closes the step -
+ * a constant launch sequence with no host synchronisation; under use_graph it is captured once and re-captured when grad_scale or
+ * a setting changes.  skf_model_apply_gradients / _range never clip. */
+size_t skf_model_clip_workspace_bytes(const SkfConfig* cfg);
+int skf_model_set_gradient_clip(SkfModel* m, int mode, float threshold, float clipvalue, int skip_nonfinite, int monitor,
+                                void* workspace, size_t workspace_bytes);
+int skf_model_apply_gradients_clipped(SkfModel* m, float grad_scale, skf_stream_t stream);
 /* ---- inference API of the plugin (models/sketchformer.py:162-168, 201-311) ----
  * skf_model_encode: encode_from_seq / predict_class - encoder + bottleneck + classifier with dropout off; results in
  *   the buffers "embedding" (B,d), "class_probs" (B,C), "enc_output" (B*L,d).

@@ -207,6 +207,16 @@ SIGNATURES = {
     "skf_step_epilogue": (_I, [_P, _P]),
     "skf_adam_step": (_I, [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _P]),
     "skf_sgd_momentum_step": (_I, [_P, _P, _P, _Z, _P, _F, _F, _P]),
+    "skf_segment_plan_chunks": (_I, [_P, _I]),
+    "skf_segment_plan_bytes": (_Z, [_I, _I]),
+    "skf_segment_plan_build": (_I, [_P, _I, _P, _Z]),
+    "skf_segment_norms_workspace_bytes": (_Z, [_I, _I]),
+    "skf_segment_stats_floats": (_Z, [_I]),
+    "skf_gradient_clip_validate": (_I, [_I, _F, _F]),
+    "skf_segment_norms": (_I, [_P, _P, _I, _I, _F, _I, _F, _I, _P, _Z, _P, _P]),
+    "skf_segment_scale": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "skf_adam_step_clipped": (_I, [_P, _P, _P, _P, _Z, _P, _F, _P, _F, _P, _F, _F, _F, _I, _P]),
+    "skf_sgd_momentum_step_clipped": (_I, [_P, _P, _P, _Z, _P, _F, _P, _F, _P, _F, _I, _P]),
     "skf_dropout": (_I, [_P, _P, _Z, _F, _U, _P, _P]),
     "skf_dropout_keep_mask": (_I, [_U, _U, _F, _Z, _P]),
     "skf_attention_decode": (_I, [_P, _I, _P, _P, _I, C.c_longlong, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I,
@@ -277,6 +287,9 @@ SIGNATURES = {
     "skf_model_beam_prefix_decode": (_I, [_P, _P, C.POINTER(_I), _I, C.c_longlong, C.c_longlong, _I, _P, _P, _P, C.POINTER(_I),
                                           C.POINTER(SkfBeam), C.POINTER(SkfPrefix), _P]),
     "skf_model_apply_gradients": (_I, [_P, _F, _P]),
+    "skf_model_clip_workspace_bytes": (_Z, [_P]),
+    "skf_model_set_gradient_clip": (_I, [_P, _I, _F, _F, _I, _I, _P, _Z]),
+    "skf_model_apply_gradients_clipped": (_I, [_P, _F, _P]),
     "skf_model_buffer": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]),
     "skf_model_buffer_info": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "skf_knn_workspace_bytes": (_Z, [_I, _I, _I]),

@@ -140,6 +140,7 @@ extern "C" int skf_model_set_flags(SkfModel* M, uint32_t flags) {
     SKF_HIP(hipDeviceSynchronize());     // steps in flight still read the descriptor table the next step uploads again
     if (M->g_fb) { (void)hipGraphExecDestroy(M->g_fb); M->g_fb = nullptr; }
     if (M->g_opt) { (void)hipGraphExecDestroy(M->g_opt); M->g_opt = nullptr; }
+    if (M->g_clip) { (void)hipGraphExecDestroy(M->g_clip); M->g_clip = nullptr; }
     M->red.reset();
   }
   M->flags = flags;
@@ -311,6 +312,7 @@ extern "C" void skf_model_destroy(SkfModel* m) {
   if (!m) return;
   if (m->g_fb) (void)hipGraphExecDestroy(m->g_fb);
   if (m->g_opt) (void)hipGraphExecDestroy(m->g_opt);
+  if (m->g_clip) (void)hipGraphExecDestroy(m->g_clip);
   if (m->g_dec) (void)hipGraphExecDestroy(m->g_dec);
   for (int i = 0; i < 2; ++i) if (m->bucket_ready[i]) (void)hipEventDestroy(m->bucket_ready[i]);
   if (m->inputs_staged) (void)hipEventDestroy(m->inputs_staged);
@@ -328,6 +330,7 @@ extern "C" int skf_model_bind(SkfModel* m, float* params, float* grads, float* a
   m->ws = (char*)workspace; m->metrics = metrics; m->state = step_state;
   if (m->g_fb) { (void)hipGraphExecDestroy(m->g_fb); m->g_fb = nullptr; }
   if (m->g_opt) { (void)hipGraphExecDestroy(m->g_opt); m->g_opt = nullptr; }
+  if (m->g_clip) { (void)hipGraphExecDestroy(m->g_clip); m->g_clip = nullptr; }
   if (m->g_dec) { (void)hipGraphExecDestroy(m->g_dec); m->g_dec = nullptr; }
   m->red.reset();      // (the cursors as well: every backward starts them at zero anyway)
   return SKF_OK;
@@ -544,6 +547,87 @@ extern "C" int skf_model_apply_gradients(SkfModel* m, float grad_scale, skf_stre
     else      // (the Adam sweep of a whole step also advances optimizer.iterations: one launch instead of two)
       return skf_adam_step_launch(m->params, m->grads, m->m, m->v, m->lay.total, m->state, grad_scale, m->cfg.beta1, m->cfg.beta2, m->cfg.eps, 1, s);
     return skf_step_epilogue(m->state, s);
+  });
+}
+
+// ---- gradient clipping / monitoring (include/skf.h; kernels in skf_gradnorm.hip and skf_optimizer.hip)
+namespace {
+// the clip workspace: the stats words first (a caller reads them at offset 0), then the uploaded segment plan, then the scratch of the norms
+struct ClipAreas { float* stats; void* plan; void* norm_ws; size_t plan_bytes, norm_ws_bytes, used; };
+ClipAreas carve_clip(void* ws, int n_entries, int n_chunks) {
+  SkfWsCarver c(ws);
+  ClipAreas a;
+  a.stats = c.take<float>(skf_segment_stats_floats(n_entries));
+  a.plan_bytes = skf_segment_plan_bytes(n_entries, n_chunks);
+  a.plan = c.take<char>(a.plan_bytes);
+  a.norm_ws_bytes = skf_segment_norms_workspace_bytes(n_entries, n_chunks);
+  a.norm_ws = c.take<char>(a.norm_ws_bytes);
+  a.used = c.used;
+  return a;
+}
+}  // namespace
+
+extern "C" size_t skf_model_clip_workspace_bytes(const SkfConfig* cfg) {
+  if (skf_config_validate(cfg) != SKF_OK) return 0;
+  const Layout L = build_layout(*cfg);
+  const int n_chunks = skf_segment_plan_chunks(L.entries.data(), (int)L.entries.size());
+  if (n_chunks < 0) return 0;
+  return carve_clip(nullptr, (int)L.entries.size(), n_chunks).used;
+}
+
+extern "C" int skf_model_set_gradient_clip(SkfModel* m, int mode, float threshold, float clipvalue, int skip_nonfinite, int monitor,
+                                           void* workspace, size_t workspace_bytes) {
+  SKF_CHECK_ARG(m, "null model");
+  SKF_TRY(skf_gradient_clip_validate(mode, threshold, clipvalue));
+  const bool on = mode != SKF_CLIP_NONE || clipvalue > 0.f || skip_nonfinite || monitor;
+  SkfModel::Clip c;
+  if (on) {
+    const int E = (int)m->lay.entries.size();
+    const int n_chunks = skf_segment_plan_chunks(m->lay.entries.data(), E);
+    if (n_chunks < 0) return n_chunks;
+    SKF_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "the clip workspace must be 256-byte aligned device memory");
+    const ClipAreas a = carve_clip(workspace, E, n_chunks);
+    SKF_CHECK_ARG(workspace_bytes >= a.used, "clip workspace too small (skf_model_clip_workspace_bytes)");
+    std::vector<char> plan(a.plan_bytes);
+    SKF_TRY(skf_segment_plan_build(m->lay.entries.data(), E, plan.data(), plan.size()));
+    SKF_HIP(hipDeviceSynchronize());      // a step in flight may still read the old plan / write the old stats
+    SKF_HIP(hipMemcpy(a.plan, plan.data(), plan.size(), hipMemcpyHostToDevice));
+    std::vector<float> stats(skf_segment_stats_floats(E), 0.f);      // norms 0, counters 0, every scale 1
+    stats[1] = 1.f;
+    for (int e = 0; e < E; ++e) stats[8 + E + e] = 1.f;
+    SKF_HIP(hipMemcpy(a.stats, stats.data(), stats.size() * sizeof(float), hipMemcpyHostToDevice));
+    c.on = true; c.mode = mode; c.threshold = threshold; c.clipvalue = clipvalue; c.skip_nonfinite = skip_nonfinite != 0; c.monitor = monitor != 0;
+    c.n_chunks = n_chunks; c.stats = a.stats; c.plan = a.plan; c.norm_ws = a.norm_ws; c.norm_ws_bytes = a.norm_ws_bytes;
+  } else {
+    SKF_HIP(hipDeviceSynchronize());
+  }
+  if (m->g_clip) { (void)hipGraphExecDestroy(m->g_clip); m->g_clip = nullptr; }
+  m->clip = c;
+  return SKF_OK;
+}
+
+extern "C" int skf_model_apply_gradients_clipped(SkfModel* m, float grad_scale, skf_stream_t stream) {
+  SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(m->clip.on, "no gradient clip is configured (skf_model_set_gradient_clip); the plain sweep is skf_model_apply_gradients");
+  hipStream_t s = (hipStream_t)stream;
+  if (m->g_clip && m->g_clip_scale != grad_scale) { (void)hipGraphExecDestroy(m->g_clip); m->g_clip = nullptr; }
+  m->g_clip_scale = grad_scale;
+  return capture_or_run(m, &m->g_clip, s, [&]() -> int {
+    const SkfModel::Clip& c = m->clip;
+    const int E = (int)m->lay.entries.size();
+    // clipvalue alone needs no reduction; everything else reads the norms / the skip decision
+    const bool norms = c.mode != SKF_CLIP_NONE || c.skip_nonfinite || c.monitor;
+    if (norms)
+      SKF_TRY(skf_segment_norms(m->grads, c.plan, E, c.n_chunks, grad_scale, c.mode, c.threshold, c.skip_nonfinite, c.norm_ws, c.norm_ws_bytes,
+                                c.stats, s));
+    void* skip = norms ? (void*)(c.stats + 3) : nullptr;
+    if (c.mode == SKF_CLIP_PER_VARIABLE) SKF_TRY(skf_segment_scale(m->grads, c.plan, E, c.n_chunks, c.stats + 8 + E, skip, s));
+    const float* scale = c.mode == SKF_CLIP_GLOBAL ? c.stats + 1 : nullptr;
+    if (m->cfg.optimizer == 1)      // (the Adam m buffer is the velocity slot)
+      return skf_sgd_momentum_step_clipped(m->params, m->grads, m->m, m->lay.total, m->state, grad_scale, scale, c.clipvalue, skip,
+                                           m->cfg.momentum, 1, s);
+    return skf_adam_step_clipped(m->params, m->grads, m->m, m->v, m->lay.total, m->state, grad_scale, scale, c.clipvalue, skip, m->cfg.beta1,
+                                 m->cfg.beta2, m->cfg.eps, 1, s);
   });
 }
 

@@ -268,6 +268,13 @@ struct SkfModel {
   std::vector<int> dec_stream_host;  // stream ids of a sampled decode on their way to the device
   std::vector<int> dec_pfx_len_host; // prefix lengths of a completion on their way to the device
   float g_opt_scale = 0.f;
+  // gradient clipping / monitoring (skf_model_set_gradient_clip): the settings, the regions of the caller's clip workspace and the
+  // captured clipped step (g_clip, re-captured when grad_scale or a setting changes, like g_opt)
+  struct Clip { bool on = false; int mode = 0, skip_nonfinite = 0, monitor = 0, n_chunks = 0; float threshold = 0.f, clipvalue = 0.f;
+                float* stats = nullptr; void* plan = nullptr; void* norm_ws = nullptr; size_t norm_ws_bytes = 0; };
+  Clip clip;
+  hipGraphExec_t g_clip = nullptr;
+  float g_clip_scale = 0.f;
   skf_model_detail::SideSched sched;                   // the side stream and everything that orders the two streams
   hipEvent_t inputs_staged = nullptr;                         // recorded behind the staging copies of every call (skf_model_wait_inputs_staged)
   bool inputs_staged_valid = false;

@@ -96,6 +96,82 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ w
   }
 }
 
+// ---- the sweeps with device-side control (gradient clipping, include/skf.h: skf_adam_step_clipped).  The gradient an element sees is
+//   gg = (g * grad_scale) * s, then with clipvalue > 0  gg = min(max(gg, -clipvalue), clipvalue)
+// with s read from device memory (null = 1): every product rounded on its own (the pragma: no product may fuse into the moment
+// update behind it), so that the update equals the plain sweep over a gradient that was scaled / clamped in memory, bit for bit.
+// skip (null = never) points at two words {skip flag, skipped total}: with the flag set the sweep writes nothing, the step-closing
+// increment of `iterations` does not happen and the total goes up by one (tf LossScaleOptimizer: a skipped step is no iteration).
+__device__ __forceinline__ float clipped_grad(float g, float grad_scale, float s, float clipvalue) {
+#pragma clang fp contract(off)
+  float gg = (g * grad_scale) * s;
+  if (clipvalue > 0.0f) gg = fminf(fmaxf(gg, -clipvalue), clipvalue);
+  return gg;
+}
+// -> true when this step is skipped; thread 0 of block 0 closes the step either way (the total, or with `advance` the iterations)
+__device__ __forceinline__ bool sweep_skipped(SkfStepState* st, unsigned* skip, bool advance) {
+  const bool skipped = skip != nullptr && skip[0] != 0u;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (skipped) skip[1] += 1u;
+    else if (advance) st->iterations += 1;
+  }
+  return skipped;
+}
+
+template <bool ADVANCE>
+__global__ __launch_bounds__(256) void adam_clipped_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, size_t n,
+                                                           SkfStepState* st, float grad_scale, const float* scale, float clipvalue,
+                                                           unsigned* skip, float one_minus_b1, float one_minus_b2, float eps) {
+  const float alpha = st->alpha;
+  if (sweep_skipped(st, skip, ADVANCE)) return;
+  const float s = scale ? *scale : 1.0f;
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    float4 wv = reinterpret_cast<float4*>(w)[i];
+    float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+#define SKF_ADAM1(c)                                                   \
+    {                                                                  \
+      const float gg = clipped_grad(gv.c, grad_scale, s, clipvalue);   \
+      mv.c += (gg - mv.c) * one_minus_b1;                              \
+      vv.c += (gg * gg - vv.c) * one_minus_b2;                         \
+      wv.c -= alpha * mv.c / (sqrtf(vv.c) + eps);                      \
+    }
+    SKF_ADAM1(x) SKF_ADAM1(y) SKF_ADAM1(z) SKF_ADAM1(w)
+#undef SKF_ADAM1
+    reinterpret_cast<float4*>(w)[i] = wv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  for (size_t i = (n4 << 2) + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float gg = clipped_grad(g[i], grad_scale, s, clipvalue);
+    float mm = m[i], vv = v[i];
+    mm += (gg - mm) * one_minus_b1;
+    vv += (gg * gg - vv) * one_minus_b2;
+    m[i] = mm; v[i] = vv;
+    w[i] -= alpha * mm / (sqrtf(vv) + eps);
+  }
+}
+
+__global__ __launch_bounds__(256) void sgd_momentum_clipped_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                                   float* __restrict__ vel, size_t n, SkfStepState* st,
+                                                                   float grad_scale, const float* scale, float clipvalue,
+                                                                   unsigned* skip, float momentum, int advance) {
+  const float lr = st->lr;
+  if (sweep_skipped(st, skip, advance != 0)) return;
+  const float s = scale ? *scale : 1.0f;
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float gg = clipped_grad(g[i], grad_scale, s, clipvalue);
+    const float v = momentum * vel[i] - lr * gg;
+    vel[i] = v;
+    w[i] += v;
+  }
+}
+
 }  // namespace
 
 extern "C" int skf_sgd_momentum_step(float* w, const float* g, float* velocity, size_t n, const void* step_state,
@@ -151,4 +227,43 @@ int skf_adam_step_launch(float* w, const float* g, float* m, float* v, size_t n,
 extern "C" int skf_adam_step(float* w, const float* g, float* m, float* v, size_t n, const void* step_state,
                              float grad_scale, float beta1, float beta2, float eps, skf_stream_t stream) {
   return skf_adam_step_launch(w, g, m, v, n, const_cast<void*>(step_state), grad_scale, beta1, beta2, eps, 0, (hipStream_t)stream);
+}
+
+// the clipped forms: same grids as the plain sweeps
+extern "C" int skf_adam_step_clipped(float* w, const float* g, float* m, float* v, size_t n, void* step_state, float grad_scale,
+                                     const float* scale, float clipvalue, void* skip, float beta1, float beta2, float eps, int advance,
+                                     skf_stream_t stream) {
+  SKF_CHECK_ARG(w && g && m && v && step_state, "null operand");
+  SKF_CHECK_ARG((((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "buffers must be 16-byte aligned");
+  SKF_CHECK_ARG((((uintptr_t)scale | (uintptr_t)skip) & 3) == 0, "scale and skip must be 4-byte aligned");
+  SKF_CHECK_ARG(clipvalue >= 0.0f && clipvalue <= 3.402823466e+38f, "clipvalue must be finite and > 0, or 0 for off");
+  size_t blocks = ((n >> 2) + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipStream_t s = (hipStream_t)stream;
+  SkfProfScope ps(s, "adam_clipped", 0.0, 28.0 * n);
+  if (advance)
+    hipLaunchKernelGGL(adam_clipped_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, w, g, m, v, n, (SkfStepState*)step_state, grad_scale,
+                       scale, clipvalue, (unsigned*)skip, 1.0f - beta1, 1.0f - beta2, eps);
+  else
+    hipLaunchKernelGGL(adam_clipped_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, w, g, m, v, n, (SkfStepState*)step_state, grad_scale,
+                       scale, clipvalue, (unsigned*)skip, 1.0f - beta1, 1.0f - beta2, eps);
+  SKF_LAUNCH_CHECK();
+  return SKF_OK;
+}
+
+extern "C" int skf_sgd_momentum_step_clipped(float* w, const float* g, float* velocity, size_t n, void* step_state, float grad_scale,
+                                             const float* scale, float clipvalue, void* skip, float momentum, int advance,
+                                             skf_stream_t stream) {
+  SKF_CHECK_ARG(w && g && velocity && step_state, "null operand");
+  SKF_CHECK_ARG((((uintptr_t)scale | (uintptr_t)skip) & 3) == 0, "scale and skip must be 4-byte aligned");
+  SKF_CHECK_ARG(clipvalue >= 0.0f && clipvalue <= 3.402823466e+38f, "clipvalue must be finite and > 0, or 0 for off");
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  SkfProfScope ps((hipStream_t)stream, "sgd_momentum_clipped", 0.0, 20.0 * n);
+  hipLaunchKernelGGL(sgd_momentum_clipped_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, g, velocity, n,
+                     (SkfStepState*)step_state, grad_scale, scale, clipvalue, (unsigned*)skip, momentum, advance);
+  SKF_LAUNCH_CHECK();
+  return SKF_OK;
 }

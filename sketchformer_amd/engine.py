@@ -152,6 +152,25 @@ def check_beam(beam_width, length_alpha, vocab_size=None, batch=None):
         raise ValueError("length_alpha must be a finite number >= 0 (got %r)" % (length_alpha,))
 
 
+def check_gradient_clip(clipnorm=None, global_clipnorm=None, clipvalue=None):
+    """The rule of the clip settings (tf.keras optimizers': at most one of the three; include/skf.h: skf_gradient_clip_validate),
+    free of the device.  None or 0 = not set.  -> (mode, threshold, clipvalue) as the C entries take them: mode 0 none, 1 per
+    variable (clipnorm), 2 global (global_clipnorm).  ValueError for two settings at once and for a value that is not a finite
+    number > 0."""
+    given = {k: float(v) for k, v in (("clipnorm", clipnorm), ("global_clipnorm", global_clipnorm), ("clipvalue", clipvalue))
+             if v is not None and v != 0}
+    if len(given) > 1:
+        raise ValueError("at most one of clipnorm, global_clipnorm and clipvalue may be set (got %s)" % ", ".join(sorted(given)))
+    for k, v in given.items():
+        if not 1e-38 <= v <= 3.4028234663852886e38:      # (a normal float32: the library takes it as one)
+            raise ValueError("%s must be a finite number > 0 (got %r)" % (k, v))
+    if "clipnorm" in given:
+        return 1, given["clipnorm"], 0.0
+    if "global_clipnorm" in given:
+        return 2, given["global_clipnorm"], 0.0
+    return 0, 0.0, given.get("clipvalue", 0.0)
+
+
 COMPLETION_NEEDS_TOKENS = ("sketch completion is built for token models: a prefix is a sequence of tokens, and continuous (stroke-5) "
                            "prefixes are not built")
 
@@ -249,6 +268,7 @@ class TrainEngine:
         # backward / the optimizer sweep of the previous piece); "single": ONE all-reduce of the whole buffer after
         # backward (the literal north-star schedule) - bench.py --allreduce single|bucketed A/Bs the two
         self.dp_mode = "bucketed"
+        self._clip = None                # set_gradient_clip: the settings, the clip workspace and its stats words
 
     # The buffers live on the engine's stream.  A step no longer makes the caller's stream wait for it (that hand-over, and the
     # one back at the start of the next step, were two cross-stream hops = ~25-40 us of idle GPU between steps,
@@ -667,10 +687,14 @@ class TrainEngine:
         """optimizer.apply_gradients (models/sketchformer.py:348).  Data parallel: every gradient bucket is all-reduced
         on a communication stream as soon as backward has finished it (bucket 0 = decoder part, overlaps the encoder
         backward; bucket 1 overlaps the optimizer sweep of bucket 0), then the optimizer runs per bucket with the 1/W
-        factor fused.  ``bucketed=True`` forces that schedule without a process group (single-GPU test of the plumbing)."""
+        factor fused.  ``bucketed=True`` forces that schedule without a process group (single-GPU test of the plumbing).
+        With ``set_gradient_clip`` configured the gradients are all-reduced the same way, but the engine's stream then waits for
+        ALL buckets and issues one skf_model_apply_gradients_clipped: a norm needs every gradient before the first update, so the
+        overlap of bucket 1's all-reduce with bucket 0's sweep is given up (the overlap with the backward stays)."""
         from . import parallel
         if bucketed is None:
             bucketed = self.world_size > 1 and self.dp_mode == "bucketed"
+        sweep = "skf_model_apply_gradients" if self._clip is None else "skf_model_apply_gradients_clipped"
         self._enter()
         try:
             if not bucketed:
@@ -678,7 +702,7 @@ class TrainEngine:
                 if self.world_size > 1:       # one all-reduce of the whole flat buffer, ordered after backward on the step's stream
                     with torch.cuda.stream(self.stream):
                         scale = parallel.allreduce_flat_gradients(self._grads, self.pg)
-                _lib.call("skf_model_apply_gradients", self.handle, scale, self._stream())
+                _lib.call(sweep, self.handle, scale, self._stream())
                 return
             if self._comm is None:
                 self._comm = torch.cuda.Stream(device=self.device)
@@ -699,9 +723,80 @@ class TrainEngine:
                         works[i].wait()                      # engine stream waits for this bucket's all-reduce
                     else:
                         self.stream.wait_stream(self._comm)
-                _lib.call("skf_model_apply_gradients_range", self.handle, off, cnt, scale, int(i == len(buckets) - 1), self._stream())
+                if self._clip is None:
+                    _lib.call("skf_model_apply_gradients_range", self.handle, off, cnt, scale, int(i == len(buckets) - 1), self._stream())
+            if self._clip is not None:       # a norm needs every gradient before the first update: ALL buckets, then the one clipped call
+                _lib.call(sweep, self.handle, scale, self._stream())
         finally:
             self._leave()
+
+    def set_gradient_clip(self, clipnorm=None, global_clipnorm=None, clipvalue=None, skip_nonfinite=False, monitor=False):
+        """tf.keras optimizers' clipnorm (every variable's gradient scaled to an L2 norm of at most clipnorm), global_clipnorm (all
+        gradients by one factor, to a global norm of at most global_clipnorm) or clipvalue (every element clamped to +-clipvalue):
+        at most one of them (``check_gradient_clip``).  skip_nonfinite: a step whose gradient holds an inf or NaN leaves parameters,
+        moments and ``iterations`` untouched and is counted (tf LossScaleOptimizer's rule).  monitor: compute the norms even when
+        nothing else needs them (``gradient_stats``).  Everything is decided on the device: a configured step is a constant launch
+        sequence without a host sync (skf_model_apply_gradients_clipped; two norm launches, the segment scale in per-variable
+        mode, one sweep).  Under data parallelism every rank computes the same norms from the same all-reduced buffer (1/world_size
+        enters as a factor on the norms): no extra collective.  Nothing set = the unconfigured step, launch for launch."""
+        mode, threshold, cv = check_gradient_clip(clipnorm, global_clipnorm, clipvalue)
+        on = bool(mode or cv or skip_nonfinite or monitor)
+        self.synchronize()
+        if not on:
+            _lib.call("skf_model_set_gradient_clip", self.handle, 0, 0.0, 0.0, 0, 0, None, 0)
+            self._clip = None
+            return
+        E = len(self.entries)
+        nbytes = int(self.lib.skf_model_clip_workspace_bytes(C.byref(self.cfg)))
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-ws.data_ptr()) % 256
+        torch.cuda.synchronize(self.device)
+        _lib.call("skf_model_set_gradient_clip", self.handle, mode, threshold, cv, int(bool(skip_nonfinite)), int(bool(monitor)),
+                  C.c_void_p(ws.data_ptr() + off), nbytes)
+        stats = ws[off:off + 4 * (8 + 2 * E)].view(torch.float32)      # the stats words lead the workspace (include/skf.h)
+        self._clip = {"mode": mode, "threshold": threshold, "clipvalue": cv, "skip_nonfinite": bool(skip_nonfinite),
+                      "monitor": bool(monitor), "workspace": ws, "stats": stats,
+                      "norms": bool(mode or skip_nonfinite or monitor)}
+
+    def _clip_stats(self):
+        if self._clip is None:
+            raise _lib.SkfError("no gradient clip / monitor is configured (set_gradient_clip)")
+        self._publish()
+        return self._clip["stats"]
+
+    def gradient_stats(self):
+        """The statistics of the last configured step (host sync): dict(global_norm, scale, nonfinite, skipped, skipped_total,
+        norms {variable: L2 norm of its gradient}, scales {variable: the factor applied to it}).  Norms are those of the gradient
+        as the optimizer saw it (after the all-reduce, times 1/world_size), before clipping; with clipvalue alone no norm is
+        computed and the norm fields stay 0."""
+        from . import ops
+        st = ops.read_segment_stats(self._clip_stats(), len(self.entries))
+        names = [e["name"] for e in self.entries]
+        st["norms"] = dict(zip(names, (float(x) for x in st["norms"])))
+        st["scales"] = dict(zip(names, (float(x) for x in st["scales"])))
+        return st
+
+    def gradient_report(self):
+        """Per variable: {'grad_norm', 'weight_norm', 'ratio'} - the gradient norm of the last configured step, the L2 norm of the
+        variable itself (the same two launches over ``params``) and grad_norm / weight_norm (inf for an all-zero variable with a
+        gradient, 0 when both are zero).  One extra read-back."""
+        from . import ops
+        stats = self._clip_stats()
+        if getattr(self, "_report_plan", None) is None:
+            self._report_plan = ops.segment_plan(self.entries, self.device)
+        with torch.cuda.stream(self.stream):
+            wst = ops.segment_norms(self._params, self._report_plan)
+            both = torch.cat([stats, wst])
+        self.stream.synchronize()
+        E = len(self.entries)
+        g = ops.read_segment_stats(both[:8 + 2 * E], E)
+        w = ops.read_segment_stats(both[8 + 2 * E:], E)
+        out = {}
+        for i, e in enumerate(self.entries):
+            gn, wn = float(g["norms"][i]), float(w["norms"][i])
+            out[e["name"]] = {"grad_norm": gn, "weight_norm": wn, "ratio": gn / wn if wn else (float("inf") if gn else 0.0)}
+        return {"global_norm": g["global_norm"], "weight_global_norm": w["global_norm"], "scale": g["scale"],
+                "skipped_total": g["skipped_total"], "variables": out}
 
     def train_step(self, inp, labels, tar=None):
         """model_trainer(inp, tar, lab) (models/sketchformer.py:325-349); no host sync."""
@@ -769,7 +864,10 @@ class TrainEngine:
         """Device copy of the 32 metric floats as they stand after the steps queued so far (no host sync): what
         ``train_on_batch`` hands back; ``resolve_metrics`` turns a list of them into floats with ONE read-back."""
         with torch.cuda.stream(self.stream):
-            snap = self._metrics.clone()
+            if self._clip is None:
+                snap = self._metrics.clone()
+            else:      # + the 8 leading statistics words (bit copies: three of them are integers), still one read-back at log time
+                snap = torch.cat([self._metrics, self._clip["stats"][:8]])
         return snap
 
     def resolve_metrics(self, snaps, reduce=True):
@@ -788,7 +886,12 @@ class TrainEngine:
                 m[:, 8:13], m[:, 16:21] = acc[:, :5], acc[:, 5:]
         self.stream.synchronize()
         rows = m.cpu().numpy()
-        return [{n: float(r[8 + i] / r[16 + i]) if r[16 + i] else 0.0 for i, n in enumerate(METRIC_NAMES)} for r in rows]
+        out = [{n: float(r[8 + i] / r[16 + i]) if r[16 + i] else 0.0 for i, n in enumerate(METRIC_NAMES)} for r in rows]
+        if rows.shape[1] > 32:      # snapshots of a configured engine carry the statistics words (metrics_snapshot)
+            for res, r in zip(out, rows):
+                res["grad_norm"] = float(r[32])
+                res["skipped_steps"] = float(np.ascontiguousarray(r[32:40]).view(np.uint32)[4])
+        return out
 
     def assert_replicas_equal(self):
         """Data parallelism keeps W copies of the parameters / optimizer state in step only if they start equal: compare

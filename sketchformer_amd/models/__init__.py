@@ -1,6 +1,7 @@
 """Model registry (models/__init__.py:9-17 of the reference)."""
 from ..core.models import BaseModel
 from . import sketchformer  # noqa: F401
+from . import sketchformer_clip  # noqa: F401
 
 
 def _all():

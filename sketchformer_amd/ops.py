@@ -549,6 +549,103 @@ def adam_step(w, g, m, v, state, grad_scale=1.0, beta1=0.9, beta2=0.98, eps=1e-9
     _lib.call("skf_adam_step", _p(w), _p(g), _p(m), _p(v), w.numel(), _p(state), grad_scale, beta1, beta2, eps, _stream())
 
 
+def sgd_momentum_step(w, g, velocity, state, grad_scale=1.0, momentum=0.9):
+    _lib.call("skf_sgd_momentum_step", _p(w), _p(g), _p(velocity), w.numel(), _p(state), grad_scale, momentum, _stream())
+
+
+# ---- gradient norms and clipping (include/skf.h: skf_segment_*, skf_adam_step_clipped)
+CLIP_MODES = {"none": 0, "per_variable": 1, "global": 2}         # SKF_CLIP_*
+SEGMENT_CHUNK = 16384                                            # SKF_SEGMENT_CHUNK
+
+
+class SegmentPlan:
+    """What ``segment_plan`` returns: the uploaded chunk table of one entry layout (``dev``, a uint8 tensor) and its counts."""
+    __slots__ = ("dev", "n_entries", "n_chunks", "entries")
+
+    def __init__(self, dev, n_entries, n_chunks, entries):
+        self.dev, self.n_entries, self.n_chunks, self.entries = dev, n_entries, n_chunks, entries
+
+
+def _entry_array(entries):
+    arr = (_lib.SkfParamEntry * len(entries))()
+    for a, e in zip(arr, entries):
+        if isinstance(e, dict):
+            e = (e["offset"], e["rows"], e["cols"], e["row_stride"])
+        a.offset, a.rows, a.cols, a.row_stride = (int(x) for x in e)
+    return arr
+
+
+def segment_plan(entries, device):
+    """The segment plan of an entry table, built on the host and uploaded once per layout.  entries: the dicts of
+    ``engine.param_entries`` or (offset, rows, cols, row_stride) tuples, in floats; strided entries are read as strided views and
+    the floats between entries are never read."""
+    lib = _lib.load()
+    arr = _entry_array(entries)
+    n = len(entries)
+    n_chunks = lib.skf_segment_plan_chunks(arr, n)
+    if n_chunks < 0:
+        _lib.check(n_chunks, "skf_segment_plan_chunks")
+    nbytes = lib.skf_segment_plan_bytes(n, n_chunks)
+    host = torch.zeros(nbytes, dtype=torch.uint8)
+    _lib.call("skf_segment_plan_build", arr, n, C.c_void_p(host.data_ptr()), nbytes)
+    return SegmentPlan(host.to(device), n, n_chunks, list(entries))
+
+
+def new_segment_stats(plan):
+    """The 8 + 2 E stats words of ``segment_norms`` as a float32 tensor: norms and counters 0, every scale 1."""
+    st = torch.zeros(8 + 2 * plan.n_entries, dtype=torch.float32, device=plan.dev.device)
+    st[1] = 1.0
+    st[8 + plan.n_entries:] = 1.0
+    return st
+
+
+def segment_norms(flat, plan, grad_scale=1.0, mode="none", threshold=0.0, skip_nonfinite=False, stats=None, workspace=None):
+    """Per-entry and global L2 norms of a flat float32 buffer, the clip scales and the skip decision: skf_segment_norms, two
+    launches, deterministic.  mode: 'none' | 'per_variable' | 'global'.  Returns the stats tensor (layout in include/skf.h;
+    ``read_segment_stats`` turns it into a dict): pass the same tensor again to keep its skipped total."""
+    _f32(flat, "flat")
+    if stats is None:
+        stats = new_segment_stats(plan)
+    nbytes = _lib.load().skf_segment_norms_workspace_bytes(plan.n_entries, plan.n_chunks)
+    ws = _ws(nbytes + 256, flat.device) if workspace is None else workspace
+    off = (-ws.data_ptr()) % 256
+    _lib.call("skf_segment_norms", _p(flat), _p(plan.dev), plan.n_entries, plan.n_chunks, float(grad_scale), CLIP_MODES[mode],
+              float(threshold), int(bool(skip_nonfinite)), C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _p(stats), _stream())
+    return stats
+
+
+def read_segment_stats(stats, n_entries=None):
+    """The stats words on the host (one copy; waits for the stream) -> dict(global_norm, scale, nonfinite, skipped, skipped_total,
+    norms (E,), scales (E,))."""
+    raw = stats.detach().cpu().numpy()
+    E = (len(raw) - 8) // 2 if n_entries is None else int(n_entries)
+    words = raw[:8].view("uint32")
+    return {"global_norm": float(raw[0]), "scale": float(raw[1]), "nonfinite": int(words[2]), "skipped": bool(words[3]),
+            "skipped_total": int(words[4]), "norms": raw[8:8 + E].copy(), "scales": raw[8 + E:8 + 2 * E].copy()}
+
+
+def segment_scale_(flat, plan, scales, skip=None):
+    """In place: every element of entry e times scales[e] (one launch over the plan).  skip: a device word; non-zero = write nothing."""
+    _f32(flat, "flat")
+    _lib.call("skf_segment_scale", _p(flat), _p(plan.dev), plan.n_entries, plan.n_chunks, _p(scales), _p(skip), _stream())
+    return flat
+
+
+def adam_step_clipped(w, g, m, v, state, grad_scale=1.0, scale=None, clipvalue=0.0, skip=None, beta1=0.9, beta2=0.98, eps=1e-9,
+                      advance=False):
+    """adam_step on gg = (g * grad_scale) * scale[0], clamped to +-clipvalue when clipvalue > 0.  scale: a device float (None = 1);
+    skip: two device words {flag, skipped total} such as ``stats[3:5]`` - with the flag set nothing is written, ``iterations`` stays
+    and the total goes up; advance: the sweep also closes the step (iterations += 1) unless it is skipped."""
+    _lib.call("skf_adam_step_clipped", _p(w), _p(g), _p(m), _p(v), w.numel(), _p(state), float(grad_scale), _p(scale), float(clipvalue),
+              _p(skip), beta1, beta2, eps, int(bool(advance)), _stream())
+
+
+def sgd_momentum_step_clipped(w, g, velocity, state, grad_scale=1.0, scale=None, clipvalue=0.0, skip=None, momentum=0.9, advance=False):
+    """sgd_momentum_step with the gradient formed as in ``adam_step_clipped``."""
+    _lib.call("skf_sgd_momentum_step_clipped", _p(w), _p(g), _p(velocity), w.numel(), _p(state), float(grad_scale), _p(scale),
+              float(clipvalue), _p(skip), momentum, int(bool(advance)), _stream())
+
+
 def dropout(x, rate, site=0, state=None):
     """Inverted dropout (tf.keras.layers.Dropout in training mode) with the kernels' counter-based mask of (step key, site, element):
     skf_dropout.  rate 0 or no state = the input itself."""
