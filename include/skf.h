@@ -83,7 +83,21 @@ int skf_gemm_f32(int a_kcontig, int b_kcontig, int M, int N, int K, const float*
 /* wgrad split into its two phases so that a caller can run MANY wgrads and reduce all their slabs with one launch:
  * skf_gemm_wgrad_partial = the partial-tile kernel only (A = X [K][M], B = dY [K][N]; slab layout
  * [splits][M][N] followed by [splits][N] column sums), skf_splitk_reduce_batch = one launch over a DEVICE array of
- * descriptors whose block_begin fields are the running sum of skf_splitk_reduce_blocks(M, N). */
+ * descriptors whose block_begin fields are the running sum of skf_splitk_reduce_blocks(M, N).
+ * Contract of one descriptor.  The launch cannot check a device array.  Every descriptor with a bias gradient that the model
+ * builds goes through ReduceBatch::add on the host (skf_model_sched.hip), which refuses one that breaks the bias_grad rule below, so
+ * the seam group cannot be reached from a train step (tests/test_cabi_cpu.py keeps the refusal in add and the other tables free
+ * of bias gradients); a caller of this entry point owes the same check.
+ *   - C = sum over the splits (never accumulated), ldc >= N.
+ *   - bias_grad != NULL: the [splits][N] column sums follow the tiles; slab must be 16-byte aligned and M*N a multiple of 4 -
+ *     the kernel reads float4 groups of [M*N | N] and has no scalar path, a group astride the seam would sum the wrong addresses.
+ *   - bias_grad == NULL: slab needs 4-byte alignment only and any M*N is accepted (the 1 x L partials of the expander and the
+ *     pooling: rows of odd length, blocks that start at any float - float4 loads at 4-byte granularity, which gfx950 global
+ *     loads allow).
+ *   - the float4 group that holds the last element is read whole for every split: when M*N (and, with a bias gradient, N) is not a
+ *     multiple of 4 the launch READS up to 12 bytes past the last split's tile (column-sum row); the values are discarded, the
+ *     bytes must be mapped (the model's slabs lie inside its workspace arena).  Nothing is written outside C / bias_grad.
+ * skf_splitk_reduce (one slab) has a scalar path for N % 4 != 0, reads nothing past the slab and refuses M*N % 4 != 0. */
 typedef struct SkfReduceDesc {
   const float* slab; float* C; float* bias_grad; /* bias_grad may be NULL */
   int32_t splits, M, N, ldc, block_begin, pad;
@@ -366,6 +380,7 @@ int skf_embed_continuous_fwd(const float* x, int x_ld_rows, int B, int L, const 
                              const float* pos, float* out, float rate, unsigned site, const void* step_state,
                              skf_stream_t stream);
 size_t skf_embed_continuous_bwd_workspace_bytes(int rows, int d);
+/* d <= 682: the backward keeps [4 waves][6][d] floats in LDS (4 * 6 * d * 4 bytes <= 64 KB); a wider d is refused */
 int skf_embed_continuous_bwd(const float* x, int x_ld_rows, int B, int L, const float* dx, int d, float* dW, float* dbias,
                              float rate, unsigned site, const void* step_state, void* workspace, size_t workspace_bytes,
                              skf_stream_t stream);
@@ -419,6 +434,8 @@ int skf_dropout_keep_mask(unsigned drop_key, unsigned site, float rate, size_t n
  *   row *step_dev; limit_from_step: keys >= *step_dev + 1 are masked where key_limit is NULL or negative.
  * skf_decode_init: column 0 of the output = SOS (tokens) or (0,0,1,0,0) (continuous); clears the flags (and *step_dev).
  * skf_decode_embed: decoder input of position *step_dev: table[token] (or Dense(5->d) of the stroke-5 row) * sqrt(d) + pos.
+ *   A token id outside [0, vocab) takes the row of id 0 here and in the one-launch decode (both decode paths clamp); the training
+ *   side's skf_embed_fwd stores a ZERO embedding vector for such an id instead (its backward skips it).
  * skf_decode_select_tokens / _continuous: models/sketchformer.py:285-301 - append argmax (first index on ties) or
  *   (x, y, softmax(pen)); maintain the target padding mask, the sticky EOS flags and done_step (-1 until the stop test
  *   holds).  With step_dev/dyn non-NULL the step, n_valid (dyn[0]) and eos (dyn[1]) are read from device memory and

@@ -112,6 +112,20 @@ class SkfPrefix(C.Structure):
             self.struct_size = C.sizeof(SkfPrefix)
 
 
+class SkfReduceDesc(C.Structure):
+    """include/skf.h: struct SkfReduceDesc, field for field (skf_splitk_reduce_batch; a DEVICE array of these)."""
+    _fields_ = [("slab", C.c_void_p), ("C", C.c_void_p), ("bias_grad", C.c_void_p),
+                ("splits", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("ldc", C.c_int32), ("block_begin", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class SkfCastDesc(C.Structure):
+    """include/skf.h: struct SkfCastDesc, field for field (skf_cast_weight_bf16_batch; a DEVICE array of these)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("dst_t", C.c_void_p),
+                ("R", C.c_int32), ("C", C.c_int32), ("ld_src", C.c_int32), ("ld_dst", C.c_int32), ("ld_t", C.c_int32),
+                ("block_begin", C.c_int32), ("blocks_x", C.c_int32), ("pad", C.c_int32)]
+
+
 BEAM_MAX = 8                                          # SKF_BEAM_MAX
 
 

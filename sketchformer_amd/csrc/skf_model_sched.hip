@@ -281,6 +281,9 @@ void ReduceBatch::reset() {
   slab_cursor = 0; desc_cursor = 0; ln_cursor = 0; reduce_blocks = 0; phase_desc_begin = 0;
 }
 int ReduceBatch::add(const SkfReduceDesc& d, int blocks) {
+  // skf.h, SkfReduceDesc: the batched kernel has no scalar path - with column sums behind the tiles M*N must be a multiple of 4
+  SKF_CHECK_ARG(!d.bias_grad || (((uintptr_t)d.slab & 15) == 0 && (((size_t)d.M * d.N) & 3) == 0),
+                "reduce descriptor with a bias gradient: slab must be 16-byte aligned and M*N a multiple of 4");
   if (!descs_uploaded) descs.push_back(d);
   else {
     const SkfReduceDesc& o = descs[desc_cursor];

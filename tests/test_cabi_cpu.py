@@ -85,6 +85,11 @@ def test_config_struct_layout_matches_header_binding_and_integration_doc(lib):
     assert _ctypes_fields(_lib.SkfConfig) == _canon(header)
     assert C.sizeof(_lib.SkfConfig) == lib.skf_config_size() == 4 * len(header)
     assert _ctypes_fields(_lib.SkfParamEntry) == _canon(_header_struct_fields("SkfParamEntry"))
+    # the descriptor arrays that the batched reduction / weight-cast launches read from device memory
+    for name, nbytes in (("SkfReduceDesc", 48), ("SkfCastDesc", 56)):
+        fields = _header_struct_fields(name)
+        assert _ctypes_fields(getattr(_lib, name)) == _canon(fields), name
+        assert C.sizeof(getattr(_lib, name)) == nbytes == 8 * 3 + 4 * (len(fields) - 3), name
     # the `_fields_ = [...]` block of its SkfConfig
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     block = re.search(r"class SkfConfig\(C\.Structure\):.*?_fields_ = \[(.*?)\n    \]", doc, flags=re.S).group(1)
@@ -446,6 +451,28 @@ def test_param_count_matches_survey(lib):
     for C_, want in ((345, 2316117), (1, 2271741)):
         cfg = engine.make_config(batch=128, n_classes=C_)
         assert sum(e["rows"] * e["cols"] for e in engine.param_entries(cfg)) == want
+
+
+def test_reduce_batch_add_checks_the_bias_gradient_contract_before_anything_else():
+    """include/skf.h, SkfReduceDesc: the batched reduction has no scalar path, so a descriptor with a bias gradient needs a 16-byte
+    aligned slab and M*N % 4 == 0.  The launch cannot check a device array; ReduceBatch::add is the one place every descriptor of
+    the model passes on the host, and the refusal is its first statement (before the descriptor is stored or counted)."""
+    text = open(os.path.join(ROOT, "sketchformer_amd", "csrc", "skf_model_sched.hip")).read()
+    body = re.search(r"int ReduceBatch::add\(const SkfReduceDesc& d, int blocks\) \{(.*?)\n\}", text, flags=re.S).group(1)
+    code = re.sub(r"//[^\n]*", "", body).strip()
+    first = code.split(";")[0]
+    assert first.startswith("SKF_CHECK_ARG("), first
+    assert "!d.bias_grad ||" in first and "(uintptr_t)d.slab & 15" in first and "(size_t)d.M * d.N) & 3" in first, first
+    # and no descriptor with a bias gradient is built around it: the only one that names a gradient is the weight-gradient
+    # descriptor of skf_model_sched.hip, handed to add in the next statement; the tables built elsewhere carry nullptr
+    csrc = os.path.join(ROOT, "sketchformer_amd", "csrc")
+    named = []
+    for f in sorted(f for f in os.listdir(csrc) if f.startswith("skf_model")):       # the units that build SkfReduceDesc tables
+        for value in re.findall(r"\.bias_grad = ([^;]+);", open(os.path.join(csrc, f)).read()):
+            if value.strip() != "nullptr":
+                named.append(f)
+    assert named == ["skf_model_sched.hip"], named
+    assert re.search(r"d\.bias_grad = M->G\(w\.b\);[^\n]*\n[^\n]*\n\s*SKF_TRY\(M->red\.add\(d,", text)
 
 
 def test_no_cpu_fallback():

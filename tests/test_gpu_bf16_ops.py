@@ -229,7 +229,7 @@ def test_attention_bf16_fully_padded_sample_is_uniform(lib):
 
 
 # ------------------------------------------------------------------ row kernels
-@pytest.mark.parametrize("d", [128, 512])
+@pytest.mark.parametrize("d", [128, 256, 512, 1024])        # every width skf.h promises: ldrow / strow <2>, <4>, <8>, <16>
 @pytest.mark.parametrize("rate", [0.0, 0.1])
 def test_layernorm_bf16_fwd_bwd(lib, d, rate):
     from sketchformer_amd import ops
@@ -436,3 +436,133 @@ def test_gemm_bf16_wgrad_over_live_row_blocks(lib, P, Q):
         err = np.abs(_np(dw) - want.cpu().numpy()) / scale
         assert err.max() < 2e-6, err.max()                       # fp32 accumulation of exact bf16 products
         _close(db, dy.double().sum(0).cpu().numpy(), 1e-5, "bias grad")
+
+
+# ------------------------------------------------------------------ LayerNorm backward with a live-row list
+@pytest.mark.parametrize("rate", [pytest.param(0.0, id="no-dropout"), pytest.param(0.1, id="dropout")])
+@pytest.mark.parametrize("d", [pytest.param(128, id="d128-ldrow<2>"), pytest.param(1024, id="d1024-ldrow<16>-widest-lds-tile")])
+def test_layernorm_bf16_bwd_rows_with_live_len(lib, d, rate):
+    """Rows behind a sample's live length carry dout == 0 exactly: with the list zeros are stored for them without reading - dz, dy and
+    dgamma | dbeta equal the dense call bit for bit."""
+    from sketchformer_amd import ops
+    B, rps, site = 6, 37, 4
+    live = np.array([0, 37, 1, 36, 5, 20], np.int32)
+    rows = B * rps
+    dead = (np.arange(rps)[None, :] >= live[:, None]).reshape(-1)
+    rng = np.random.RandomState(d + 7)
+    X, _ = _bf(rng.randn(rows, d)); Y, _ = _bf(rng.randn(rows, d))
+    DO, _ = _bf(rng.randn(rows, d) * ~dead[:, None])
+    gd, bd = _f(1 + 0.1 * rng.randn(d)), _f(0.1 * rng.randn(d))
+    st = ops.new_step_state("cuda", iterations=5)
+    ops.step_prologue(st, seed=3)
+    out = torch.empty(rows, d, dtype=BF, device="cuda")
+    stats = torch.empty(rows, 2, dtype=torch.float32, device="cuda")
+    lib.call("skf_layernorm_residual_fwd_bf16", _p(X), _p(Y), _p(gd), _p(bd), _p(out), _p(stats), rows, d, rate, site, _p(st), _s())
+    wsb = lib.load().skf_layernorm_bwd_bf16_workspace_bytes(rows, d)
+    ll = torch.as_tensor(live).cuda()
+    res = []
+    for counts in (None, ll):
+        ws = torch.full((wsb // 4,), 3.0, dtype=torch.float32, device="cuda")
+        dz, dy = (torch.full((rows + 1, d), 3.0, dtype=BF, device="cuda") for _ in range(2))
+        dgb = torch.full((2 * d + 2,), 3.0, dtype=torch.float32, device="cuda")
+        lib.call("skf_layernorm_residual_bwd_bf16_rows", _p(DO), _p(Y), _p(stats), _p(gd), _p(dz), _p(dy), _p(dgb), C.c_void_p(dgb.data_ptr() + 4 * d),
+                 rows, d, rate, site, _p(st), _p(ws), wsb, _p(counts), rps if counts is not None else 0, _s())
+        res.append((dz, dy, dgb))
+    for a, b_ in zip(res[0], res[1]):
+        assert torch.equal(a, b_)
+    dz, dy, dgb = res[1]
+    dd = torch.as_tensor(dead).cuda()
+    assert float(dz[:rows][dd].float().abs().max()) == 0.0 and float(dy[:rows][dd].float().abs().max()) == 0.0
+    assert float(dz[:rows][~dd].float().abs().max()) > 0.0
+    assert float(dz[rows].float().min()) == float(dz[rows].float().max()) == 3.0 and float(dy[rows].float().min()) == float(dy[rows].float().max()) == 3.0
+    assert dgb[2 * d:].tolist() == [3.0, 3.0]
+
+
+# ------------------------------------------------------------------ casts at the fp32 <-> bf16 seams
+def _special_floats():
+    """+-0, subnormals, +-inf, the largest finite float (rounds to inf), exact ties with an even and an odd kept bit, neighbours of a
+    tie, NaNs (their payload is not compared)"""
+    bits = np.array([0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x007fffff, 0x00008000, 0x00018000, 0x00017fff, 0x7f800000, 0xff800000,
+                     0x7f7fffff, 0xff7fffff, 0x3f808000, 0x3f818000, 0xbf808000, 0xbf818000, 0x3f808001, 0x3f807fff, 0x3f818001, 0x3f817fff,
+                     0x7fc00000, 0x7f800001, 0xffc12345], np.uint32)
+    return bits.view(np.float32)
+
+
+@pytest.mark.parametrize("n", [pytest.param(1, id="n1-odd-tail-only"), pytest.param(2, id="n2-one-pair"), pytest.param(511, id="n511-pairs-and-tail"),
+                               pytest.param(512, id="n512-one-workgroup"), pytest.param(513, id="n513-second-workgroup-tail"),
+                               pytest.param(524289, id="n524289-second-grid-sweep-tail")])
+def test_cast_f32_to_bf16_rounds_to_nearest_even(lib, n):
+    rng = np.random.RandomState(n)
+    sp = _special_floats()
+    if n <= 2:
+        sources = [sp[k:k + n].copy() for k in range(len(sp) - n + 1)]   # every special value as the tail element / in a pair
+    else:
+        src = (rng.randn(n) * np.exp(4 * rng.randn(n))).astype(np.float32)
+        src[:len(sp)] = sp                                             # in the pairs (v_cvt_pk_bf16_f32) ...
+        src[n - len(sp):] = sp[::-1]                                   # ... and, n odd, sp[0] as the tail element (the integer rounding)
+        sources = [src]
+    for src in sources:
+        S = torch.as_tensor(src).cuda()
+        dst = torch.full((n + 3,), 5.0, dtype=BF, device="cuda")
+        lib.call("skf_cast_f32_to_bf16", _p(S), _p(dst), n, _s())
+        want = torch.as_tensor(src).to(BF)
+        got = dst[:n].cpu()
+        nan = torch.isnan(want)
+        assert torch.equal(torch.isnan(got), nan)
+        assert torch.equal(got.view(torch.int16)[~nan], want.view(torch.int16)[~nan])   # bit for bit, the sign of zero included
+        assert dst[n:].float().tolist() == [5.0] * 3
+    with pytest.raises(lib.SkfError):
+        lib.call("skf_cast_f32_to_bf16", _p(S), C.c_void_p(dst.data_ptr() + 2), 1, _s())  # dst at a 2-byte offset
+    back = torch.full((n + 3,), 5.0, dtype=torch.float32, device="cuda")
+    lib.call("skf_cast_bf16_to_f32", _p(dst), _p(back), n, _s())
+    assert torch.equal(back[:n].cpu().view(torch.int32), got.float().view(torch.int32)) and back[n:].tolist() == [5.0] * 3
+
+
+def test_cast_bf16_to_f32_is_exact_for_every_bit_pattern(lib):
+    n = 65536 + 1                                                      # every pattern once, and an odd count
+    bits = np.arange(n, dtype=np.int64).astype(np.uint16).view(np.int16)
+    src = torch.as_tensor(bits).view(BF).cuda()
+    dst = torch.full((n + 3,), 5.0, dtype=torch.float32, device="cuda")
+    lib.call("skf_cast_bf16_to_f32", _p(src), _p(dst), n, _s())
+    want = (np.arange(n, dtype=np.int64).astype(np.uint16).astype(np.uint32) << 16).view(np.int32)
+    assert np.array_equal(dst[:n].cpu().view(torch.int32).numpy(), want) and dst[n:].tolist() == [5.0] * 3
+
+
+def test_cast_weight_bf16_batch_equals_the_single_calls(lib):
+    """Four descriptors in one launch (the descriptor search, a 1 x 1 problem, dst only, dst_t only): every image equals the one
+    skf_cast_weight_bf16 writes, pad columns are zero, the row behind each image keeps its sentinel."""
+    rng = np.random.RandomState(8)
+    l = lib.load()
+    forms = [("130x1004-both", 130, 1004, 1010, 1008, 136), ("1x1-both", 1, 1, 3, 8, 8), ("33x65-dst-only", 33, 65, 65, 72, 0),
+             ("64x32-dst_t-only", 64, 32, 40, 0, 72)]
+    descs = (lib.SkfCastDesc * len(forms))()
+    keep, begin = [], 0
+    for i, (name, R, Cc, lds, ldd, ldt) in enumerate(forms):
+        src = np.zeros((R, lds), np.float32); src[:, :Cc] = rng.randn(R, Cc); src[:, Cc:] = 9.0     # (the source's own pad is never read)
+        S = torch.as_tensor(src).cuda()
+        imgs = []
+        for _ in range(2):                                               # batch, single
+            dst = torch.full((R + 1, ldd), 5.0, dtype=BF, device="cuda") if ldd else None
+            dst_t = torch.full((Cc + 1, ldt), 5.0, dtype=BF, device="cuda") if ldt else None
+            imgs.append((dst, dst_t))
+        bx = C.c_int(0)
+        blocks = l.skf_cast_weight_bf16_blocks(R, Cc, ldd, ldt, C.byref(bx))
+        d = descs[i]
+        d.src, d.dst, d.dst_t = S.data_ptr(), (imgs[0][0].data_ptr() if ldd else None), (imgs[0][1].data_ptr() if ldt else None)
+        d.R, d.C, d.ld_src, d.ld_dst, d.ld_t, d.block_begin, d.blocks_x, d.pad = R, Cc, lds, ldd, ldt, begin, bx.value, 0
+        begin += blocks
+        lib.call("skf_cast_weight_bf16", _p(S), R, Cc, lds, _p(imgs[1][0]), ldd, _p(imgs[1][1]), ldt, _s())
+        keep.append((name, R, Cc, src, S, imgs))
+    table = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).cuda()
+    lib.call("skf_cast_weight_bf16_batch", _p(table), len(forms), begin, _s())
+    for name, R, Cc, src, S, imgs in keep:
+        want = torch.as_tensor(src[:, :Cc]).to(BF)
+        for k, (a, b_) in enumerate(zip(imgs[0], imgs[1])):
+            if a is None:
+                continue
+            assert torch.equal(a, b_), name                              # bit for bit the single call
+            w = want if k == 0 else want.t()
+            rr, cc = w.shape
+            assert torch.equal(a[:rr, :cc].cpu(), w), name
+            assert float(a[:rr, cc:].float().abs().max() if a.shape[1] > cc else 0.0) == 0.0, name       # pad columns
+            assert float(a[rr].float().min()) == float(a[rr].float().max()) == 5.0, name                 # sentinel row behind the image

@@ -1405,3 +1405,127 @@ def test_gemm_wgrad_partial_group_equals_single_launches(ops):
         assert probs[i].splits_used == used
         n = used * (inf * outf + outf)
         assert torch.equal(slab_s[:n], slab_g[:n])
+
+
+# ------------------------------------------------------------------ LayerNorm branches that torch allocations never reach
+@pytest.fixture(scope="module", autouse=True)
+def _report_entry_point_errors():
+    import entry_point_checks as epc
+    yield
+    epc.report()
+
+
+def _ln_case(ops, rows, d, rate, site, seed, dead=None):
+    """x, y, dout (zero on the `dead` rows), gamma, beta on the device; the forward's z and stats; the float64 oracle of both passes"""
+    rng = np.random.RandomState(seed)
+    x, y, dout = rng.randn(rows, d), rng.randn(rows, d), rng.randn(rows, d)
+    if dead is not None:
+        dout[dead] = 0.0
+    gamma, beta = 1 + 0.1 * rng.randn(d), 0.1 * rng.randn(d)
+    st = ops.new_step_state("cuda", iterations=3)
+    ops.step_prologue(st, seed=5)
+    keep = np.ones((rows, d), bool)
+    if rate > 0:
+        keep = ops.dropout_keep_mask(ops.read_step_state(st)["drop_key"], site, rate, rows * d).reshape(rows, d)
+    z = x + oracle.dropout_fwd(y, keep, rate)
+    want, cache = oracle.layernorm_fwd(z, gamma, beta)
+    return dict(x=x, y=y, dout=dout, gamma=gamma, beta=beta, st=st, keep=keep, z=z, want=want, grads=oracle.layernorm_bwd(dout, cache))
+
+
+@pytest.mark.parametrize("rate", [pytest.param(0.0, id="no-dropout"), pytest.param(0.1, id="dropout")])
+@pytest.mark.parametrize("d", [pytest.param(64, id="d64-ln_kernel<1>"), pytest.param(128, id="d128-ln_kernel<2>"),
+                               pytest.param(256, id="d256-ln_kernel<4>")])
+def test_layernorm_residual_unaligned_operands_take_the_scalar_kernels(ops, d, rate):
+    """x (forward) and dout (backward) handed over at data_ptr() + 4: not 16-byte aligned, so ln_fwd_kernel<1|2|4> / ln_bwd_kernel<1|2|4>
+    run instead of the float4 kernels.  Same oracle comparison and bars as test_layernorm_residual_fwd_bwd."""
+    from entry_point_checks import SENTINEL, close, filled, ptr, stream
+    lib = ops._lib
+    rows, site = 1031, 9
+    c = _ln_case(ops, rows, d, rate, site, seed=d + 1)
+    n = rows * d
+    xbuf, dobuf = filled(n + 4), filled(n + 4)
+    xbuf[1:n + 1] = _dev(c["x"]).view(-1); dobuf[1:n + 1] = _dev(c["dout"]).view(-1)
+    assert xbuf.data_ptr() % 16 == 0 and dobuf.data_ptr() % 16 == 0
+    gamma, beta = _dev(c["gamma"]), _dev(c["beta"])
+    zz, out, stats = filled(n + 4), filled(n + 4), filled(2 * rows + 4)
+    zz[:n] = _dev(c["y"]).view(-1)
+    lib.call("skf_layernorm_residual_fwd", ptr(xbuf, 4), ptr(zz), ptr(gamma), ptr(beta), ptr(out), ptr(stats), rows, d, rate, site,
+             ptr(c["st"]), stream())
+    close(out[:n].view(rows, d), c["want"], RTOL, "skf_layernorm_residual_fwd (unaligned)", "out")
+    close(zz[:n].view(rows, d), c["z"], RTOL, "skf_layernorm_residual_fwd (unaligned)", "z")
+    close(stats[:2 * rows].view(rows, 2)[:, 0], c["z"].mean(-1), RTOL, "skf_layernorm_residual_fwd (unaligned)", "mean")
+    # backward on the z / stats the device stored, like test_layernorm_residual_fwd_bwd
+    nbytes = lib.load().skf_layernorm_bwd_workspace_bytes(rows, d)
+    ws = filled(nbytes // 4 + 4)
+    dz, dy, dgb = filled(n + 4), filled(n + 4), filled(2 * d + 4)
+    lib.call("skf_layernorm_residual_bwd", ptr(dobuf, 4), ptr(zz), ptr(stats), ptr(gamma), ptr(dz), ptr(dy) if rate > 0 else None,
+             ptr(dgb), ptr(dgb, 4 * d), rows, d, rate, site, ptr(c["st"]), ptr(ws), nbytes, stream())
+    gz, gg, gb = c["grads"]
+    close(dz[:n].view(rows, d), gz, 5e-5, "skf_layernorm_residual_bwd (unaligned)", "dz")
+    if rate > 0:
+        close(dy[:n].view(rows, d), oracle.dropout_fwd(gz, c["keep"], rate), 5e-5, "skf_layernorm_residual_bwd (unaligned)", "dy")
+    close(dgb[:d], gg, 5e-5, "skf_layernorm_residual_bwd (unaligned)", "dgamma")
+    close(dgb[d:2 * d], gb, 5e-5, "skf_layernorm_residual_bwd (unaligned)", "dbeta")
+    for t, used in ((zz, n), (out, n), (stats, 2 * rows), (dz, n), (dy, n if rate > 0 else 0), (dgb, 2 * d), (ws, nbytes // 4)):
+        assert float(t[used:].min()) == float(t[used:].max()) == SENTINEL
+
+
+def _ln_bwd_rows(ops, c, rows, d, rate, site, z, stats, live, rps):
+    """-> dz, dy (None without dropout), dgamma|dbeta; every buffer has a slack row / elements that must keep the sentinel"""
+    from entry_point_checks import SENTINEL, filled, ptr, stream
+    lib = ops._lib
+    nbytes = lib.load().skf_layernorm_bwd_workspace_bytes(rows, d)
+    ws = filled(nbytes // 4 + 4)
+    dz, dy, dgb = filled(rows + 1, d), (filled(rows + 1, d) if rate > 0 else None), filled(2 * d + 4)
+    lib.call("skf_layernorm_residual_bwd_rows", ptr(c["dout_dev"]), ptr(z), ptr(stats), ptr(c["gamma_dev"]), ptr(dz), ptr(dy), ptr(dgb),
+             ptr(dgb, 4 * d), rows, d, rate, site, ptr(c["st"]), ptr(ws), nbytes, ptr(live), rps if live is not None else 0, stream())
+    for slack in (ws[nbytes // 4:], dz[rows], dgb[2 * d:]) + ((dy[rows],) if dy is not None else ()):
+        assert float(slack.min()) == float(slack.max()) == SENTINEL
+    return dz[:rows], (dy[:rows] if dy is not None else None), dgb[:2 * d]
+
+
+@pytest.mark.parametrize("rate", [pytest.param(0.0, id="no-dropout"), pytest.param(0.1, id="dropout")])
+@pytest.mark.parametrize("d", [pytest.param(64, id="d64-v4<16>"), pytest.param(128, id="d128-v4<32>"), pytest.param(256, id="d256-v4<64>"),
+                               pytest.param(512, id="d512-dense-kernel-ignores-the-list")])
+def test_layernorm_residual_bwd_rows_with_live_len(ops, d, rate):
+    """Rows behind a sample's live length carry dout == 0 exactly: with the list they are not read and zeros are stored - dz and dy equal
+    the dense call bit for bit; dgamma | dbeta against the oracle at the bar of test_layernorm_residual_fwd_bwd."""
+    from entry_point_checks import close
+    B, rps, site = 6, 37, 9
+    live = np.array([0, 37, 1, 36, 5, 20], np.int32)
+    rows = B * rps
+    dead = (np.arange(rps)[None, :] >= live[:, None]).reshape(-1)
+    c = _ln_case(ops, rows, d, rate, site, seed=d + 2, dead=dead)
+    c["dout_dev"], c["gamma_dev"] = _dev(c["dout"]), _dev(c["gamma"])
+    _, z, stats = ops.layernorm_residual_fwd(_dev(c["x"]), _dev(c["y"]), c["gamma_dev"], _dev(c["beta"]), rate=rate, site=site, state=c["st"])
+    dense = _ln_bwd_rows(ops, c, rows, d, rate, site, z, stats, None, 0)
+    listed = _ln_bwd_rows(ops, c, rows, d, rate, site, z, stats, _dev(live, torch.int32), rps)
+    dead_dev = torch.as_tensor(dead).cuda()
+    for a, b in zip(dense[:2], listed[:2]):
+        if a is not None:
+            assert torch.equal(a, b)
+            assert float(b[dead_dev].abs().max()) == 0.0
+    _, gg, gb = c["grads"]
+    for name, dgb in (("dense", dense[2]), ("live_len", listed[2])):
+        close(dgb[:d], gg, 5e-5, "skf_layernorm_residual_bwd_rows", "dgamma (%s)" % name)
+        close(dgb[d:], gb, 5e-5, "skf_layernorm_residual_bwd_rows", "dbeta (%s)" % name)
+
+
+def test_layernorm_residual_bwd_rows_past_the_prefetched_live_flags(ops):
+    """d = 256, 48 x 448 = 21504 rows > 640 workgroups x 4 waves x 8 prefetched sweeps = 20480: the last sweep reads every row, dead
+    ones included (their dout is zero).  Against the dense call only."""
+    B, rps, d, rate, site = 48, 448, 256, 0.1, 9
+    rng = np.random.RandomState(11)
+    live = rng.randint(0, rps + 1, size=B).astype(np.int32)
+    live[0], live[1], live[-1], live[-2] = 0, rps, rps // 2, 0            # (the rows past 20480 belong to the last two samples)
+    rows = B * rps
+    dead = (np.arange(rps)[None, :] >= live[:, None]).reshape(-1)
+    c = _ln_case(ops, rows, d, rate, site, seed=3, dead=dead)
+    c["dout_dev"], c["gamma_dev"] = _dev(c["dout"]), _dev(c["gamma"])
+    _, z, stats = ops.layernorm_residual_fwd(_dev(c["x"]), _dev(c["y"]), c["gamma_dev"], _dev(c["beta"]), rate=rate, site=site, state=c["st"])
+    dense = _ln_bwd_rows(ops, c, rows, d, rate, site, z, stats, None, 0)
+    listed = _ln_bwd_rows(ops, c, rows, d, rate, site, z, stats, _dev(live, torch.int32), rps)
+    dead_dev = torch.as_tensor(dead).cuda()
+    for a, b in zip(dense, listed):
+        assert torch.equal(a, b)
+    assert float(listed[0][dead_dev].abs().max()) == 0.0 and float(listed[1][dead_dev].abs().max()) == 0.0
