@@ -407,17 +407,34 @@ int skf_expander_bwd(const float* dpre, const float* emb, const float* w, int B,
 
 /* ------------------------------------------------------------------ optimizer
  * builders/schedulers.py:13-46 + tf.keras.optimizers.Adam (models/sketchformer.py:112-124,348).
- * step_state is skf_step_state_bytes() of device memory {int64 iterations; float lr, alpha; u32 drop_key}.
- * schedule 0: WarmupDecay p0=d_model, p1=warmup^-1.5; 1: StepDecay p0=init_lr p1=rate p2=steps p3=min_ratio; 2: const p0 */
+ * step_state is skf_step_state_bytes() of device memory {int64 iterations; float lr, alpha; u32 drop_key, micro}.
+ * schedule 0: WarmupDecay p0=d_model, p1=warmup^-1.5; 1: StepDecay p0=init_lr p1=rate p2=steps p3=min_ratio; 2: const p0
+ * micro (zero unless gradient accumulation moves it, skf_grad_accumulate) counts the micro-batches already summed into the open
+ * optimizer step.  The prologue derives lr and alpha from `iterations` alone and the dropout key from (seed, iterations, micro):
+ * micro == 0 gives hash(seed, iterations), the key of a step without accumulation; micro = j > 0 hashes j into that key with a
+ * further round, so the micro-steps of one optimizer step draw different masks and none of them draws those of a later step. */
 size_t skf_step_state_bytes(void);
 int skf_step_prologue(void* step_state, int schedule, float p0, float p1, float p2, float p3, float beta1, float beta2,
                       unsigned seed, skf_stream_t stream);
 int skf_step_epilogue(void* step_state, skf_stream_t stream);
+/* host helper: the dropout key the prologue writes for (seed, iterations, micro) */
+unsigned skf_step_drop_key(unsigned seed, long long iterations, unsigned micro);
 int skf_adam_step(float* w, const float* g, float* m, float* v, size_t n, const void* step_state, float grad_scale,
                   float beta1, float beta2, float eps, skf_stream_t stream);
 /* tf.keras.optimizers.SGD(lr_schedule, momentum), nesterov=False: velocity = momentum*velocity - lr*g*grad_scale; w += velocity */
 int skf_sgd_momentum_step(float* w, const float* g, float* velocity, size_t n, const void* step_state, float grad_scale,
                           float momentum, skf_stream_t stream);
+/* Gradient accumulation (skf_accum.hip): dst[i] = a[i] + b[i] over n floats, dst[i] = a[i] with b == NULL.  One fp32 add per
+ * element, rounded once - the bits of a host a + b; inf and NaN pass through.  dst may be a or b.  One launch: 16-byte loads and
+ * stores, at most 2048 workgroups striding over the buffer, a scalar tail for n % 4; no atomics, no workspace.
+ * micro_op: what one thread of the same launch does to step_state's `micro` word - SKF_MICRO_KEEP nothing (step_state may be NULL),
+ * SKF_MICRO_NEXT micro += 1, SKF_MICRO_ZERO micro = 0.  n == 0 with a micro_op moves the counter alone (dst, a may be NULL).
+ * SKF_EINVAL with a message: dst, a or b not 16-byte aligned, a null dst or a with n > 0, an unknown micro_op, a micro_op other
+ * than KEEP without a step state. */
+#define SKF_MICRO_KEEP 0
+#define SKF_MICRO_NEXT 1
+#define SKF_MICRO_ZERO 2
+int skf_grad_accumulate(float* dst, const float* a, const float* b, size_t n, void* step_state, int micro_op, skf_stream_t stream);
 
 /* y = inverted dropout of x (n floats, y may alias x) with the mask of (step key, site, element index);
  * applied to an upstream gradient it is the backward.  rate 0 = copy. */
@@ -813,6 +830,24 @@ size_t skf_model_clip_workspace_bytes(const SkfConfig* cfg);
 int skf_model_set_gradient_clip(SkfModel* m, int mode, float threshold, float clipvalue, int skip_nonfinite, int monitor,
                                 void* workspace, size_t workspace_bytes);
 int skf_model_apply_gradients_clipped(SkfModel* m, float grad_scale, skf_stream_t stream);
+/* Gradient accumulation in the train step: k micro-batches, one optimizer step.  acc: skf_model_param_floats floats of caller-owned
+ * device memory, 16-byte aligned.  After every skf_model_forward_backward (which overwrites `grads`) the caller issues one phase on
+ * the stream the step ran on (backward leaves `grads` complete there):
+ *   SKF_ACCUM_FIRST  acc = grads          micro += 1     the first micro-batch of an optimizer step (acc's old contents are dropped)
+ *   SKF_ACCUM_ADD    acc += grads         micro += 1     micro-batches 2 .. k-1
+ *   SKF_ACCUM_CLOSE  grads = acc + grads  micro  = 0     the last one: `grads` holds the SUM of the k micro-batch gradients
+ *   SKF_ACCUM_RESET  nothing              micro  = 0     drop what is pending
+ * and after CLOSE the unchanged skf_model_apply_gradients[_clipped | _range] with grad_scale = 1 / (world_size * k): the sweep,
+ * the norms, the clip scale, the skip rule and iterations += 1 then act on the mean gradient.  A non-finite micro-gradient poisons
+ * the sum: with skip_nonfinite the whole accumulated step is skipped and counted once; `micro` is already 0 by then, so the next
+ * step starts clean either way.  Each phase is ONE launch (skf_grad_accumulate), no host synchronisation, and is issued eagerly
+ * also under use_graph (its operands would make one captured graph per phase and buffer; the captured step graphs on either side
+ * read `micro` and `grads` from device memory and replay unchanged).  A model that never calls this runs the step it always ran. */
+#define SKF_ACCUM_FIRST 0
+#define SKF_ACCUM_ADD 1
+#define SKF_ACCUM_CLOSE 2
+#define SKF_ACCUM_RESET 3
+int skf_model_accumulate_gradients(SkfModel* m, float* acc, int phase, skf_stream_t stream);
 /* ---- inference API of the plugin (models/sketchformer.py:162-168, 201-311) ----
  * skf_model_encode: encode_from_seq / predict_class - encoder + bottleneck + classifier with dropout off; results in
  *   the buffers "embedding" (B,d), "class_probs" (B,C), "enc_output" (B*L,d).

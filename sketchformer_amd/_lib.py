@@ -126,6 +126,8 @@ class SkfCastDesc(C.Structure):
                 ("block_begin", C.c_int32), ("blocks_x", C.c_int32), ("pad", C.c_int32)]
 
 
+MICRO_KEEP, MICRO_NEXT, MICRO_ZERO = 0, 1, 2                          # SKF_MICRO_* (skf_grad_accumulate)
+ACCUM_FIRST, ACCUM_ADD, ACCUM_CLOSE, ACCUM_RESET = 0, 1, 2, 3         # SKF_ACCUM_* (skf_model_accumulate_gradients)
 BEAM_MAX = 8                                          # SKF_BEAM_MAX
 
 
@@ -219,8 +221,10 @@ SIGNATURES = {
     "skf_step_state_bytes": (_Z, []),
     "skf_step_prologue": (_I, [_P, _I, _F, _F, _F, _F, _F, _F, _U, _P]),
     "skf_step_epilogue": (_I, [_P, _P]),
+    "skf_step_drop_key": (_U, [_U, _L, _U]),
     "skf_adam_step": (_I, [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _P]),
     "skf_sgd_momentum_step": (_I, [_P, _P, _P, _Z, _P, _F, _F, _P]),
+    "skf_grad_accumulate": (_I, [_P, _P, _P, _Z, _P, _I, _P]),
     "skf_segment_plan_chunks": (_I, [_P, _I]),
     "skf_segment_plan_bytes": (_Z, [_I, _I]),
     "skf_segment_plan_build": (_I, [_P, _I, _P, _Z]),
@@ -304,6 +308,7 @@ SIGNATURES = {
     "skf_model_clip_workspace_bytes": (_Z, [_P]),
     "skf_model_set_gradient_clip": (_I, [_P, _I, _F, _F, _I, _I, _P, _Z]),
     "skf_model_apply_gradients_clipped": (_I, [_P, _F, _P]),
+    "skf_model_accumulate_gradients": (_I, [_P, _P, _I, _P]),
     "skf_model_buffer": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]),
     "skf_model_buffer_info": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "skf_knn_workspace_bytes": (_Z, [_I, _I, _I]),

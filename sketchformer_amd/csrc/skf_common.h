@@ -278,6 +278,14 @@ struct SkfStepState {
   long long iterations;   // optimizer.iterations (pre-increment value used this step)
   float lr;               // schedule(iterations)
   float alpha;            // lr * sqrt(1-b2^t)/(1-b1^t)
-  uint32_t drop_key;      // hash(seed, iterations)
-  uint32_t pad;
+  uint32_t drop_key;      // hash(seed, iterations) at micro == 0, hash(seed, iterations, micro) behind it (skf_drop_key)
+  uint32_t micro;         // micro-batches already summed into the open optimizer step (gradient accumulation, skf_accum.hip); 0 without it
 };
+static_assert(sizeof(SkfStepState) == 24, "step state layout (include/skf.h, ops.read_step_state)");
+// The dropout key of micro-step `micro` of optimizer step `it`.  micro == 0 is the key every step had before accumulation existed;
+// micro = j > 0 hashes j (under a constant of its own) INTO that key: a third hash round over (seed, iterations, j), not a shift of
+// `iterations` - key(it, j) and key(it + j, 0) are unrelated words, so no micro-step redraws the masks of a later optimizer step.
+__host__ __device__ __forceinline__ uint32_t skf_drop_key(uint32_t seed, long long it, uint32_t micro) {
+  const uint32_t key = skf_hash32(seed ^ skf_hash32((uint32_t)it + 0x632be5abU));
+  return micro == 0 ? key : skf_hash32(key ^ skf_hash32(micro + 0x5bd1e995U));
+}

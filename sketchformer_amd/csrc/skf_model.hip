@@ -631,6 +631,22 @@ extern "C" int skf_model_apply_gradients_clipped(SkfModel* m, float grad_scale, 
   });
 }
 
+// ---- gradient accumulation (include/skf.h; the kernel is skf_accum.hip).  One eager launch per phase on the step's stream: the
+// step graphs on either side read `grads` and the step state from device memory, so nothing captured changes with the phase.
+extern "C" int skf_model_accumulate_gradients(SkfModel* m, float* acc, int phase, skf_stream_t stream) {
+  SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(phase == SKF_ACCUM_FIRST || phase == SKF_ACCUM_ADD || phase == SKF_ACCUM_CLOSE || phase == SKF_ACCUM_RESET,
+                "phase must be SKF_ACCUM_FIRST, _ADD, _CLOSE or _RESET");
+  SKF_CHECK_ARG(acc || phase == SKF_ACCUM_RESET, "null accumulation buffer");
+  const size_t n = m->lay.total;
+  switch (phase) {
+    case SKF_ACCUM_FIRST: return skf_grad_accumulate(acc, m->grads, nullptr, n, m->state, SKF_MICRO_NEXT, stream);
+    case SKF_ACCUM_ADD:   return skf_grad_accumulate(acc, acc, m->grads, n, m->state, SKF_MICRO_NEXT, stream);
+    case SKF_ACCUM_CLOSE: return skf_grad_accumulate(m->grads, acc, m->grads, n, m->state, SKF_MICRO_ZERO, stream);
+    default:              return skf_grad_accumulate(nullptr, nullptr, nullptr, 0, m->state, SKF_MICRO_ZERO, stream);
+  }
+}
+
 extern "C" int skf_model_grad_buckets(SkfModel* m, int max_buckets, size_t* offsets_host, size_t* counts_host) {
   SKF_CHECK_ARG(m && offsets_host && counts_host && max_buckets >= 2, "bad argument");
   const size_t dec_off = m->lay.dec_off;

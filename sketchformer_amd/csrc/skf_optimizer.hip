@@ -35,7 +35,7 @@ __global__ void step_prologue_kernel(SkfStepState* st, int schedule, float p0, f
   const double b1p = pow((double)beta1, t), b2p = pow((double)beta2, t);
   st->lr = lr;
   st->alpha = lr * (float)(sqrt(1.0 - b2p) / (1.0 - b1p));
-  st->drop_key = skf_hash32(seed ^ skf_hash32((uint32_t)it + 0x632be5abU));
+  st->drop_key = skf_drop_key(seed, it, st->micro);      // (lr and alpha above depend on `iterations` alone)
 }
 
 __global__ void step_epilogue_kernel(SkfStepState* st) {
@@ -198,6 +198,8 @@ extern "C" int skf_step_prologue(void* step_state, int schedule, float p0, float
   SKF_LAUNCH_CHECK();
   return SKF_OK;
 }
+
+extern "C" unsigned skf_step_drop_key(unsigned seed, long long iterations, unsigned micro) { return skf_drop_key(seed, iterations, micro); }
 
 extern "C" int skf_step_epilogue(void* step_state, skf_stream_t stream) {
   SKF_CHECK_ARG(step_state, "null step state");

@@ -171,6 +171,23 @@ def check_gradient_clip(clipnorm=None, global_clipnorm=None, clipvalue=None):
     return 0, 0.0, given.get("clipvalue", 0.0)
 
 
+# The most micro-batches one optimizer step may sum.  The sum is carried in fp32: its rounding error grows like k * 2^-24 relative to
+# the largest partial sum, 2^-14 (6e-5) at 1024 - still an order of magnitude below the 2^-9 of the bf16 activations the cfg-5
+# gradients are computed from - and 1 / (world_size * k) stays far inside the normal float32 range.  Beyond it a value is far more
+# likely a slip (a batch size in the wrong field) than a plan.
+ACCUM_STEPS_MAX = 1024
+
+
+def check_gradient_accumulation(steps):
+    """The rule of ``accum_steps`` (host only): an integer in [1, ACCUM_STEPS_MAX]; 1 = no accumulation.  bool and float are refused
+    (True is not a count, and 2.0 usually is the result of a division that may as well give 2.5).  -> int; ValueError otherwise."""
+    if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)):
+        raise ValueError("accum_steps must be an integer (got %r of type %s)" % (steps, type(steps).__name__))
+    if not 1 <= int(steps) <= ACCUM_STEPS_MAX:
+        raise ValueError("accum_steps must be in [1, %d] (got %r)" % (ACCUM_STEPS_MAX, steps))
+    return int(steps)
+
+
 COMPLETION_NEEDS_TOKENS = ("sketch completion is built for token models: a prefix is a sequence of tokens, and continuous (stroke-5) "
                            "prefixes are not built")
 
@@ -269,6 +286,7 @@ class TrainEngine:
         # backward (the literal north-star schedule) - bench.py --allreduce single|bucketed A/Bs the two
         self.dp_mode = "bucketed"
         self._clip = None                # set_gradient_clip: the settings, the clip workspace and its stats words
+        self._accum = None               # set_gradient_accumulation: {"k", "acc", "pending"}
 
     # The buffers live on the engine's stream.  A step no longer makes the caller's stream wait for it (that hand-over, and the
     # one back at the start of the next step, were two cross-stream hops = ~25-40 us of idle GPU between steps,
@@ -683,14 +701,17 @@ class TrainEngine:
             _lib.check(n if n < 0 else -1, "skf_model_grad_buckets")
         return [(int(off[i]), int(cnt[i])) for i in range(n)]
 
-    def apply_gradients(self, bucketed=None):
+    def apply_gradients(self, bucketed=None, micro=None):
         """optimizer.apply_gradients (models/sketchformer.py:348).  Data parallel: every gradient bucket is all-reduced
         on a communication stream as soon as backward has finished it (bucket 0 = decoder part, overlaps the encoder
         backward; bucket 1 overlaps the optimizer sweep of bucket 0), then the optimizer runs per bucket with the 1/W
         factor fused.  ``bucketed=True`` forces that schedule without a process group (single-GPU test of the plumbing).
         With ``set_gradient_clip`` configured the gradients are all-reduced the same way, but the engine's stream then waits for
         ALL buckets and issues one skf_model_apply_gradients_clipped: a norm needs every gradient before the first update, so the
-        overlap of bucket 1's all-reduce with bucket 0's sweep is given up (the overlap with the backward stays)."""
+        overlap of bucket 1's all-reduce with bucket 0's sweep is given up (the overlap with the backward stays).
+        ``micro`` is set by the accumulation path alone (train_step, flush_accumulation, a caller's CLOSE): `grads` then holds the sum of that many micro-batch
+        gradients, written by a launch on the engine's stream behind the backward - the factor becomes 1 / (world_size * micro)
+        and the communication stream waits for the engine's stream instead of for the per-bucket events of the last backward."""
         from . import parallel
         if bucketed is None:
             bucketed = self.world_size > 1 and self.dp_mode == "bucketed"
@@ -702,19 +723,23 @@ class TrainEngine:
                 if self.world_size > 1:       # one all-reduce of the whole flat buffer, ordered after backward on the step's stream
                     with torch.cuda.stream(self.stream):
                         scale = parallel.allreduce_flat_gradients(self._grads, self.pg)
+                if micro is not None:
+                    scale = 1.0 / (max(self.world_size, 1) * micro)
                 _lib.call(sweep, self.handle, scale, self._stream())
                 return
             if self._comm is None:
                 self._comm = torch.cuda.Stream(device=self.device)
             buckets = self.grad_buckets()
-            scale = 1.0 / max(self.world_size, 1)
+            scale = 1.0 / (max(self.world_size, 1) * (micro or 1))
             works = []
-            if self.cfg.use_graph:
+            if self.cfg.use_graph or micro is not None:
                 # a step replayed from a hipGraph records no per-bucket events (one bucket): the communication stream must be
-                # ordered after the whole captured forward/backward, or the all-reduce would race with the gradient writes
+                # ordered after the whole captured forward/backward, or the all-reduce would race with the gradient writes.
+                # An accumulated gradient is finished by the closing launch on the engine's stream, behind every bucket event
                 self._comm.wait_stream(self.stream)
             for i, (off, cnt) in enumerate(buckets):
-                _lib.call("skf_model_wait_grad_bucket", self.handle, i, C.c_void_p(self._comm.cuda_stream))
+                if micro is None:
+                    _lib.call("skf_model_wait_grad_bucket", self.handle, i, C.c_void_p(self._comm.cuda_stream))
                 with torch.cuda.stream(self._comm):
                     works.append(parallel.allreduce_bucket(self._grads[off:off + cnt], self.pg))
             for i, (off, cnt) in enumerate(buckets):
@@ -804,9 +829,81 @@ class TrainEngine:
         self._enter()                                # the hand-over below is what orders the step behind them
         try:
             self._forward_backward_staged(staged)
-            self.apply_gradients()
+            if self._accum is None:
+                self.apply_gradients()
+            else:
+                self._accumulate_micro_step()
         finally:
             self._leave()
+
+    # ---- gradient accumulation: k micro-batches, one optimizer step (include/skf.h: skf_model_accumulate_gradients)
+    def set_gradient_accumulation(self, steps):
+        """``steps`` = k micro-batches per optimizer step (``check_gradient_accumulation``); 1 switches everything off and train_step
+        issues the launches it always issued.  With k > 1 train_step runs forward and backward, sums the gradient into an
+        accumulation buffer of ``n_floats`` floats (allocated here) and returns - no all-reduce, no bucket wait, no sweep - until
+        the k-th call, which closes the sum into ``grads`` and runs ``apply_gradients`` with 1 / (world_size * k): clipping, the
+        norms, skip_nonfinite, ``iterations``, the learning-rate schedule and ``skipped_total`` all see ONE optimizer step on the
+        mean gradient of k * batch * world_size rows.  Every micro-step draws its own dropout masks.  The running metrics go on
+        accumulating per micro-batch.  Pending micro-batches of an earlier setting are discarded (``reset_accumulation``)."""
+        k = check_gradient_accumulation(steps)
+        self.reset_accumulation()
+        self.synchronize()
+        if k == 1:
+            self._accum = None
+            return
+        self._accum = {"k": k, "acc": torch.empty(self.n_floats, dtype=torch.float32, device=self.device), "pending": 0}
+        torch.cuda.current_stream(self.device).synchronize()      # (the allocation is the caller stream's, the launches the engine's)
+
+    @property
+    def accumulation_pending(self):
+        """micro-batches summed so far into the open optimizer step (0 .. k-1; 0 without accumulation)"""
+        return 0 if self._accum is None else self._accum["pending"]
+
+    def accumulate_gradients(self, phase):
+        """One phase of skf_model_accumulate_gradients behind a ``forward_backward`` (what train_step issues; by hand for a caller
+        that drives the pieces itself): _lib.ACCUM_FIRST acc = grads, ACCUM_ADD acc += grads, ACCUM_CLOSE grads = acc + grads - then
+        ``apply_gradients(micro=j)`` for the j micro-batches summed - and ACCUM_RESET.  Keeps ``accumulation_pending`` in step."""
+        a = self._accum
+        if a is None:
+            raise _lib.SkfError("no gradient accumulation is configured (set_gradient_accumulation)")
+        self._enter()
+        try:
+            _lib.call("skf_model_accumulate_gradients", self.handle, self._p(a["acc"]), int(phase), self._stream())
+            a["pending"] = {_lib.ACCUM_FIRST: 1, _lib.ACCUM_ADD: a["pending"] + 1}.get(int(phase), 0)
+        finally:
+            self._leave()
+
+    def _accumulate_micro_step(self):
+        """behind a forward_backward: sum this micro-batch, and close the optimizer step if it is the k-th"""
+        a = self._accum
+        if a["pending"] < a["k"] - 1:
+            self.accumulate_gradients(_lib.ACCUM_FIRST if a["pending"] == 0 else _lib.ACCUM_ADD)
+            return
+        micro = a["pending"] + 1
+        self.accumulate_gradients(_lib.ACCUM_CLOSE)      # grads = acc + grads, micro = 0
+        self.apply_gradients(micro=micro)
+
+    def flush_accumulation(self):
+        """Apply what is pending as an optimizer step of its own: j < k micro-batches with 1 / (world_size * j) (the end of an epoch
+        whose batch count is no multiple of k).  Nothing pending: nothing happens.  Collective under data parallelism."""
+        from . import ops
+        a = self._accum
+        if a is None or a["pending"] == 0:
+            return
+        self._enter()
+        try:
+            with torch.cuda.stream(self.stream):       # grads = acc (the last micro-batch is already part of it), micro = 0
+                ops.grad_accumulate(self._grads, a["acc"], None, self._state, _lib.MICRO_ZERO)
+            micro, a["pending"] = a["pending"], 0
+            self.apply_gradients(micro=micro)
+        finally:
+            self._leave()
+
+    def reset_accumulation(self):
+        """Discard the pending micro-batches (a restored checkpoint carries none): the next train_step opens a new optimizer step."""
+        if self._accum is None:
+            return
+        self.accumulate_gradients(_lib.ACCUM_RESET)
 
     def buffer(self, name):
         """(rows, cols) view of an internal activation.  fp32 models: a float32 view of the workspace; bf16 models keep

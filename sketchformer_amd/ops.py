@@ -82,7 +82,7 @@ def _centers(centers, beside=None):
 
 
 def new_step_state(device, iterations=0):
-    """Device-resident per-step scalars {int64 iterations; f32 lr, alpha; u32 drop_key, pad}."""
+    """Device-resident per-step scalars {int64 iterations; f32 lr, alpha; u32 drop_key, micro}."""
     n = _lib.load().skf_step_state_bytes()
     st = torch.zeros(n // 8 + 1, dtype=torch.int64, device=device)
     st[0] = iterations
@@ -98,11 +98,37 @@ def step_epilogue(state):
 
 
 def read_step_state(state):
-    """-> dict(iterations, lr, alpha, drop_key) (host sync)."""
+    """-> dict(iterations, lr, alpha, drop_key, micro) (host sync)."""
     raw = state.cpu().numpy().tobytes()
     import struct
-    it, lr, alpha, key, _ = struct.unpack("<qffII", raw[:24])
-    return {"iterations": it, "lr": lr, "alpha": alpha, "drop_key": key}
+    it, lr, alpha, key, micro = struct.unpack("<qffII", raw[:24])
+    return {"iterations": it, "lr": lr, "alpha": alpha, "drop_key": key, "micro": micro}
+
+
+def step_drop_key(seed, iterations, micro=0):
+    """The dropout key the prologue writes for (seed, iterations, micro) (host only; skf_step_drop_key)."""
+    return int(_lib.load().skf_step_drop_key(int(seed) & 0xffffffff, int(iterations), int(micro)))
+
+
+def grad_accumulate(dst, a, b=None, state=None, micro_op=0):
+    """dst = a + b (dst = a with b None) over flat float32 tensors of one size, on the current stream; dst may be a or b
+    (skf_grad_accumulate: one fp32 add per element, the bits of torch's a + b).  micro_op: _lib.MICRO_KEEP / MICRO_NEXT / MICRO_ZERO on
+    the `micro` word of the step state ``state`` (needed unless MICRO_KEEP).  Pointers that are not 16-byte aligned are refused by
+    the library (SkfError, rc = SKF_EINVAL)."""
+    for t, name in ((dst, "dst"), (a, "a"), (b, "b")):
+        if t is None and name == "b":
+            continue
+        _p(t)
+        if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.device != dst.device:
+            raise TypeError("%s must be a contiguous 1-D float32 tensor on the device of dst" % name)
+        if t.numel() != dst.numel():
+            raise ValueError("dst, a and b must have the same number of elements")
+    if micro_op not in (_lib.MICRO_KEEP, _lib.MICRO_NEXT, _lib.MICRO_ZERO):
+        raise ValueError("micro_op must be 0 (leave the counter), 1 (micro += 1) or 2 (micro = 0)")
+    if micro_op != _lib.MICRO_KEEP and state is None:
+        raise ValueError("a micro_op that moves the counter needs the step state")
+    _lib.call("skf_grad_accumulate", _p(dst), _p(a), _p(b), dst.numel(), _p(state), int(micro_op), _stream())
+    return dst
 
 
 def target_live_len(tar, Ld):
