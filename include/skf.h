@@ -435,6 +435,22 @@ int skf_sgd_momentum_step(float* w, const float* g, float* velocity, size_t n, c
 #define SKF_MICRO_NEXT 1
 #define SKF_MICRO_ZERO 2
 int skf_grad_accumulate(float* dst, const float* a, const float* b, size_t n, void* step_state, int micro_op, skf_stream_t stream);
+/* Weight averaging (skf_ema.hip): tf.train.ExponentialMovingAverage / tfa.optimizers.MovingAverage without zero-debias.
+ * skf_ema_update: shadow[i] -= (shadow[i] - w[i]) * (1 - d) over n floats - three fp32 operations per element, each rounded once,
+ * nothing fused: the bits of TensorFlow's assign_moving_average and of a float32 host restatement.  d = decay with num_updates == 0,
+ * otherwise min(decay, (1 + n) / (10 + n)) with n = (float)iterations read from step_state BY THE KERNEL (no host read, no launch
+ * in front); skf_ema_decay_at is the same fp32 expression on the host.  skip (NULL = never): a device word - the skip flag of the
+ * clipped sweeps - with skip[0] != 0 the launch writes nothing.  It writes `shadow` alone, never w, the step state or skip.  One
+ * launch: 16-byte loads and stores, at most 2048 workgroups striding over the buffer, a scalar tail for n % 4; no atomics, no
+ * workspace; 12 B of traffic per element.
+ * skf_buffer_swap: exchanges a and b (n floats each) in place as 16-byte words of bits - NaN payloads survive.  Same launch shape.
+ * SKF_EINVAL with a message: a decay that is not finite or not inside (0, 1), pointers not 16-byte aligned, operands that are the
+ * same buffer or overlap, num_updates without a step state. */
+int skf_weight_average_validate(float decay);
+float skf_ema_decay_at(float decay, int num_updates, long long iterations);
+int skf_ema_update(float* shadow, const float* w, size_t n, float decay, int num_updates, const void* step_state, const void* skip,
+                   skf_stream_t stream);
+int skf_buffer_swap(float* a, float* b, size_t n, skf_stream_t stream);
 
 /* y = inverted dropout of x (n floats, y may alias x) with the mask of (step key, site, element index);
  * applied to an upstream gradient it is the backward.  rate 0 = copy. */
@@ -848,6 +864,25 @@ int skf_model_apply_gradients_clipped(SkfModel* m, float grad_scale, skf_stream_
 #define SKF_ACCUM_CLOSE 2
 #define SKF_ACCUM_RESET 3
 int skf_model_accumulate_gradients(SkfModel* m, float* acc, int phase, skf_stream_t stream);
+/* Weight averaging in the train step: an exponential moving average of `params` that evaluation and sampling run on.
+ * skf_model_set_weight_average: shadow = skf_model_param_floats floats of caller-owned device memory, 16-byte aligned (NULL = off);
+ *   decay in (0, 1); num_updates != 0 = the warm-up rule min(decay, (1 + n) / (10 + n)) over n = iterations.  It does NOT initialise
+ *   the shadow: tf starts a shadow at the variable's value, so copy `params` into it.
+ * skf_model_update_weight_average: ONE eager launch (skf_ema_update) on the stream the step ran on, issued behind
+ *   skf_model_apply_gradients, skf_model_apply_gradients_clipped or the last skf_model_apply_gradients_range: the sweep has advanced
+ *   `iterations` by then, so n is the number of updates applied (tfa: num_updates = optimizer.iterations).  With a clip configuration
+ *   that computes norms it reads the sweep's skip flag: a skipped step leaves the shadow untouched, as it leaves parameters, moments
+ *   and `iterations` untouched.  Under gradient accumulation: once per optimizer step.  It is not part of the captured step graphs:
+ *   under use_graph it follows the replay, as the accumulate phases do.
+ * skf_model_swap_weight_average: params <-> shadow in place (skf_buffer_swap), toggles "average live".  Every forward rebuilds its
+ *   weight images from `params`, so every inference entry then runs on the average.  While the average is live
+ *   skf_model_forward_backward, the three apply_gradients entries, skf_model_accumulate_gradients and
+ *   skf_model_update_weight_average return SKF_EINVAL with a message (one host branch on a flag no other model ever sets).
+ * skf_model_weight_average_live: 1 while live, else 0.  A model that never calls these runs the step it always ran. */
+int skf_model_set_weight_average(SkfModel* m, float* shadow, float decay, int num_updates);
+int skf_model_update_weight_average(SkfModel* m, skf_stream_t stream);
+int skf_model_swap_weight_average(SkfModel* m, skf_stream_t stream);
+int skf_model_weight_average_live(SkfModel* m);
 /* ---- inference API of the plugin (models/sketchformer.py:162-168, 201-311) ----
  * skf_model_encode: encode_from_seq / predict_class - encoder + bottleneck + classifier with dropout off; results in
  *   the buffers "embedding" (B,d), "class_probs" (B,C), "enc_output" (B*L,d).

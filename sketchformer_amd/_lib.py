@@ -225,6 +225,10 @@ SIGNATURES = {
     "skf_adam_step": (_I, [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _P]),
     "skf_sgd_momentum_step": (_I, [_P, _P, _P, _Z, _P, _F, _F, _P]),
     "skf_grad_accumulate": (_I, [_P, _P, _P, _Z, _P, _I, _P]),
+    "skf_weight_average_validate": (_I, [_F]),
+    "skf_ema_decay_at": (_F, [_F, _I, _L]),
+    "skf_ema_update": (_I, [_P, _P, _Z, _F, _I, _P, _P, _P]),
+    "skf_buffer_swap": (_I, [_P, _P, _Z, _P]),
     "skf_segment_plan_chunks": (_I, [_P, _I]),
     "skf_segment_plan_bytes": (_Z, [_I, _I]),
     "skf_segment_plan_build": (_I, [_P, _I, _P, _Z]),
@@ -309,6 +313,10 @@ SIGNATURES = {
     "skf_model_set_gradient_clip": (_I, [_P, _I, _F, _F, _I, _I, _P, _Z]),
     "skf_model_apply_gradients_clipped": (_I, [_P, _F, _P]),
     "skf_model_accumulate_gradients": (_I, [_P, _P, _I, _P]),
+    "skf_model_set_weight_average": (_I, [_P, _P, _F, _I]),
+    "skf_model_update_weight_average": (_I, [_P, _P]),
+    "skf_model_swap_weight_average": (_I, [_P, _P]),
+    "skf_model_weight_average_live": (_I, [_P]),
     "skf_model_buffer": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I)]),
     "skf_model_buffer_info": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "skf_knn_workspace_bytes": (_Z, [_I, _I, _I]),

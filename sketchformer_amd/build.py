@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libskf.so")
 SOURCES = ["skf_model.hip", "skf_model_prof.hip", "skf_model_layout.hip", "skf_model_sched.hip", "skf_model_fwd.hip", "skf_model_bwd.hip",
-           "skf_model_decode.hip", "skf_model_bf16.hip", "skf_gemm.hip", "skf_gemm_ws.hip", "skf_gemm_small.hip", "skf_gemm_wsx.hip", "skf_gemm_wgrad.hip", "skf_ffn_fused.hip", "skf_attention.hip", "skf_attention_bwd2.hip", "skf_attention_bwd3.hip", "skf_rowops.hip", "skf_continuous.hip", "skf_optimizer.hip", "skf_decode.hip", "skf_decode_fused.hip", "skf_beam.hip", "skf_row_blocks.hip", "skf_generic.hip", "skf_bf16_gemm.hip", "skf_bf16_attention.hip", "skf_bf16_rowops.hip", "skf_retrieval.hip", "skf_kmeans.hip", "skf_interp.hip", "skf_tsne.hip", "skf_raster.hip", "skf_tokenize.hip", "skf_align.hip", "skf_augment.hip", "skf_simplify.hip", "skf_ragged.hip", "skf_score.hip", "skf_chamfer.hip", "skf_resample.hip", "skf_strokes.hip", "skf_flatten.hip", "skf_gradnorm.hip", "skf_accum.hip"]
+           "skf_model_decode.hip", "skf_model_bf16.hip", "skf_gemm.hip", "skf_gemm_ws.hip", "skf_gemm_small.hip", "skf_gemm_wsx.hip", "skf_gemm_wgrad.hip", "skf_ffn_fused.hip", "skf_attention.hip", "skf_attention_bwd2.hip", "skf_attention_bwd3.hip", "skf_rowops.hip", "skf_continuous.hip", "skf_optimizer.hip", "skf_decode.hip", "skf_decode_fused.hip", "skf_beam.hip", "skf_row_blocks.hip", "skf_generic.hip", "skf_bf16_gemm.hip", "skf_bf16_attention.hip", "skf_bf16_rowops.hip", "skf_retrieval.hip", "skf_kmeans.hip", "skf_interp.hip", "skf_tsne.hip", "skf_raster.hip", "skf_tokenize.hip", "skf_align.hip", "skf_augment.hip", "skf_simplify.hip", "skf_ragged.hip", "skf_score.hip", "skf_chamfer.hip", "skf_resample.hip", "skf_strokes.hip", "skf_flatten.hip", "skf_gradnorm.hip", "skf_accum.hip", "skf_ema.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          # f32-input MFMA shares the VALU pipe on gfx950 (tools/micro/mfma_valu_overlap.hip): keep accumulators in VGPRs so
          # the epilogues need no v_accvgpr_read/write moves (they were ~30 % of the VALU instructions of the attention loops)
@@ -30,10 +30,13 @@ FLAGS += os.environ.get("SKF_EXTRA_HIPCC_FLAGS", "").split()   # extra compiler 
 # the de Casteljau lerps are rounded operation by operation
 # skf_gradnorm.hip: the clip scales c / max(norm, c) and the in-place x * s_e are bit-equal to the float32 restatement
 # (DESIGN.md section 3w): no multiply may fuse into an add
+# skf_ema.hip: shadow -= (shadow - w) * (1 - d) is bit-equal to TensorFlow's assign_moving_average and to the float32 restatement
+# (DESIGN.md section 3y): the multiply must not fuse into the subtract behind it
 SOURCE_FLAGS = {"skf_kmeans.hip": ["-fno-slp-vectorize"], "skf_tokenize.hip": ["-ffp-contract=off"], "skf_align.hip": ["-ffp-contract=off"],
                 "skf_augment.hip": ["-ffp-contract=off"], "skf_simplify.hip": ["-ffp-contract=off"],
                 "skf_chamfer.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "skf_resample.hip": ["-ffp-contract=off"],
-                "skf_strokes.hip": ["-ffp-contract=off"], "skf_flatten.hip": ["-ffp-contract=off"], "skf_gradnorm.hip": ["-ffp-contract=off"]}
+                "skf_strokes.hip": ["-ffp-contract=off"], "skf_flatten.hip": ["-ffp-contract=off"], "skf_gradnorm.hip": ["-ffp-contract=off"],
+                "skf_ema.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -507,9 +507,14 @@ extern "C" int skf_model_greedy_decode(SkfModel* m, const float* embedding, cons
                                       stream);
 }
 
+// what the training entries answer while a swap has the weight average in `params` (skf_model_swap_weight_average): a step would
+// train the average and leave the raw weights behind in the shadow
+static const char kAvgLive[] = "the weight average is live in `params` (skf_model_swap_weight_average): swap back before training";
+
 extern "C" int skf_model_forward_backward(SkfModel* m, const void* inp, const void* tar, int tar_ld,
                                           const long long* labels, skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(!m->avg.live, kAvgLive);
   SKF_CHECK_ARG(labels, "null labels");
   hipStream_t s = (hipStream_t)stream;
   SKF_TRY(stage_batch(m, inp, tar, tar_ld, labels, s));
@@ -538,6 +543,7 @@ extern "C" int skf_model_wait_inputs_staged(SkfModel* m, skf_stream_t stream) {
 
 extern "C" int skf_model_apply_gradients(SkfModel* m, float grad_scale, skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(!m->avg.live, kAvgLive);
   hipStream_t s = (hipStream_t)stream;
   if (m->g_opt && m->g_opt_scale != grad_scale) { (void)hipGraphExecDestroy(m->g_opt); m->g_opt = nullptr; }
   m->g_opt_scale = grad_scale;
@@ -608,6 +614,7 @@ extern "C" int skf_model_set_gradient_clip(SkfModel* m, int mode, float threshol
 
 extern "C" int skf_model_apply_gradients_clipped(SkfModel* m, float grad_scale, skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(!m->avg.live, kAvgLive);
   SKF_CHECK_ARG(m->clip.on, "no gradient clip is configured (skf_model_set_gradient_clip); the plain sweep is skf_model_apply_gradients");
   hipStream_t s = (hipStream_t)stream;
   if (m->g_clip && m->g_clip_scale != grad_scale) { (void)hipGraphExecDestroy(m->g_clip); m->g_clip = nullptr; }
@@ -635,6 +642,7 @@ extern "C" int skf_model_apply_gradients_clipped(SkfModel* m, float grad_scale, 
 // step graphs on either side read `grads` and the step state from device memory, so nothing captured changes with the phase.
 extern "C" int skf_model_accumulate_gradients(SkfModel* m, float* acc, int phase, skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(!m->avg.live, kAvgLive);
   SKF_CHECK_ARG(phase == SKF_ACCUM_FIRST || phase == SKF_ACCUM_ADD || phase == SKF_ACCUM_CLOSE || phase == SKF_ACCUM_RESET,
                 "phase must be SKF_ACCUM_FIRST, _ADD, _CLOSE or _RESET");
   SKF_CHECK_ARG(acc || phase == SKF_ACCUM_RESET, "null accumulation buffer");
@@ -646,6 +654,43 @@ extern "C" int skf_model_accumulate_gradients(SkfModel* m, float* acc, int phase
     default:              return skf_grad_accumulate(nullptr, nullptr, nullptr, 0, m->state, SKF_MICRO_ZERO, stream);
   }
 }
+
+// ---- weight averaging (include/skf.h; the kernels are skf_ema.hip).  The update is one eager launch behind the sweep that advanced
+// `iterations`; the swap exchanges the contents of `params` and the shadow - every forward rebuilds its weight images from `params`,
+// so every entry point then runs on the average.
+extern "C" int skf_model_set_weight_average(SkfModel* m, float* shadow, float decay, int num_updates) {
+  SKF_CHECK_ARG(m, "null model");
+  SKF_CHECK_ARG(!m->avg.live, "the weight average is live in `params`: swap back before changing or dropping the shadow");
+  if (shadow) {
+    SKF_TRY(skf_weight_average_validate(decay));
+    SKF_CHECK_ARG(((uintptr_t)shadow & 15) == 0, "the shadow must be 16-byte aligned device memory");
+  }
+  SKF_HIP(hipDeviceSynchronize());      // an update in flight may still write the old shadow
+  SkfModel::Avg a;
+  if (shadow) { a.shadow = shadow; a.decay = decay; a.num_updates = num_updates != 0; }
+  m->avg = a;
+  return SKF_OK;
+}
+
+extern "C" int skf_model_update_weight_average(SkfModel* m, skf_stream_t stream) {
+  SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(m->avg.shadow, "no weight average is configured (skf_model_set_weight_average)");
+  SKF_CHECK_ARG(!m->avg.live, kAvgLive);
+  const SkfModel::Clip& c = m->clip;
+  const bool norms = c.on && (c.mode != SKF_CLIP_NONE || c.skip_nonfinite || c.monitor);      // as in skf_model_apply_gradients_clipped
+  return skf_ema_update(m->avg.shadow, m->params, m->lay.total, m->avg.decay, m->avg.num_updates, m->state,
+                        norms ? (const void*)(c.stats + 3) : nullptr, stream);
+}
+
+extern "C" int skf_model_swap_weight_average(SkfModel* m, skf_stream_t stream) {
+  SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(m->avg.shadow, "no weight average is configured (skf_model_set_weight_average)");
+  SKF_TRY(skf_buffer_swap(m->params, m->avg.shadow, m->lay.total, stream));
+  m->avg.live = !m->avg.live;
+  return SKF_OK;
+}
+
+extern "C" int skf_model_weight_average_live(SkfModel* m) { return m && m->avg.live ? 1 : 0; }
 
 extern "C" int skf_model_grad_buckets(SkfModel* m, int max_buckets, size_t* offsets_host, size_t* counts_host) {
   SKF_CHECK_ARG(m && offsets_host && counts_host && max_buckets >= 2, "bad argument");
@@ -668,6 +713,7 @@ extern "C" int skf_model_wait_grad_bucket(SkfModel* m, int bucket, skf_stream_t 
 extern "C" int skf_model_apply_gradients_range(SkfModel* m, size_t offset, size_t count, float grad_scale, int last,
                                                skf_stream_t stream) {
   SKF_CHECK_ARG(m && m->ws, "model not bound");
+  SKF_CHECK_ARG(!m->avg.live, kAvgLive);
   SKF_CHECK_ARG((offset & 3) == 0 && offset + count <= m->lay.total, "range must start on a multiple of 4 floats inside the buffer");
   hipStream_t s = (hipStream_t)stream;
   if (count) {

@@ -275,6 +275,10 @@ struct SkfModel {
   Clip clip;
   hipGraphExec_t g_clip = nullptr;
   float g_clip_scale = 0.f;
+  // weight averaging (skf_model_set_weight_average): the caller's shadow buffer and the rule of its update.  live: a swap has put the
+  // average into `params` (and the raw weights into `shadow`) - the training entries refuse to run until a second swap
+  struct Avg { float* shadow = nullptr; float decay = 0.f; int num_updates = 0; bool live = false; };
+  Avg avg;
   skf_model_detail::SideSched sched;                   // the side stream and everything that orders the two streams
   hipEvent_t inputs_staged = nullptr;                         // recorded behind the staging copies of every call (skf_model_wait_inputs_staged)
   bool inputs_staged_valid = false;

@@ -188,6 +188,17 @@ def check_gradient_accumulation(steps):
     return int(steps)
 
 
+def check_weight_average(decay):
+    """The rule of a weight-average ``decay`` (host only; skf_weight_average_validate): a finite number strictly between 0 and 1 -
+    0 would make the average the weights themselves, 1 would freeze it.  bool is refused.  -> float; ValueError otherwise."""
+    if isinstance(decay, (bool, np.bool_)) or not isinstance(decay, (int, float, np.integer, np.floating)):
+        raise ValueError("the decay of a weight average must be a number (got %r of type %s)" % (decay, type(decay).__name__))
+    d = float(np.float32(decay))
+    if _lib.load().skf_weight_average_validate(d) != 0:
+        raise ValueError("the decay of a weight average must be finite and lie in (0, 1) as a float32 (got %r)" % (decay,))
+    return d
+
+
 COMPLETION_NEEDS_TOKENS = ("sketch completion is built for token models: a prefix is a sequence of tokens, and continuous (stroke-5) "
                            "prefixes are not built")
 
@@ -287,6 +298,7 @@ class TrainEngine:
         self.dp_mode = "bucketed"
         self._clip = None                # set_gradient_clip: the settings, the clip workspace and its stats words
         self._accum = None               # set_gradient_accumulation: {"k", "acc", "pending"}
+        self._avg = None                 # set_weight_average: {"decay", "num_updates", "shadow", "live"}
 
     # The buffers live on the engine's stream.  A step no longer makes the caller's stream wait for it (that hand-over, and the
     # one back at the start of the next step, were two cross-stream hops = ~25-40 us of idle GPU between steps,
@@ -308,6 +320,8 @@ class TrainEngine:
     metrics = property(lambda self: self._published(self._metrics))
     state = property(lambda self: self._published(self._state))
     workspace = property(lambda self: self._published(self._workspace))
+    # the averaged weights (set_weight_average), None without averaging; while ``average_live`` it holds the raw weights instead
+    weight_average = property(lambda self: None if self._avg is None else self._published(self._avg["shadow"]))
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -686,6 +700,7 @@ class TrainEngine:
         _lib.call("skf_model_wait_inputs_staged", self.handle, torch.cuda.current_stream(self.device).cuda_stream)
 
     def forward_backward(self, inp, tar, labels):
+        self._refuse_live("forward_backward")
         staged = self._stage(inp, tar, labels)
         self._enter()
         try:
@@ -713,6 +728,7 @@ class TrainEngine:
         gradients, written by a launch on the engine's stream behind the backward - the factor becomes 1 / (world_size * micro)
         and the communication stream waits for the engine's stream instead of for the per-bucket events of the last backward."""
         from . import parallel
+        self._refuse_live("apply_gradients")
         if bucketed is None:
             bucketed = self.world_size > 1 and self.dp_mode == "bucketed"
         sweep = "skf_model_apply_gradients" if self._clip is None else "skf_model_apply_gradients_clipped"
@@ -726,6 +742,7 @@ class TrainEngine:
                 if micro is not None:
                     scale = 1.0 / (max(self.world_size, 1) * micro)
                 _lib.call(sweep, self.handle, scale, self._stream())
+                self._update_weight_average()
                 return
             if self._comm is None:
                 self._comm = torch.cuda.Stream(device=self.device)
@@ -752,6 +769,7 @@ class TrainEngine:
                     _lib.call("skf_model_apply_gradients_range", self.handle, off, cnt, scale, int(i == len(buckets) - 1), self._stream())
             if self._clip is not None:       # a norm needs every gradient before the first update: ALL buckets, then the one clipped call
                 _lib.call(sweep, self.handle, scale, self._stream())
+            self._update_weight_average()
         finally:
             self._leave()
 
@@ -825,6 +843,7 @@ class TrainEngine:
 
     def train_step(self, inp, labels, tar=None):
         """model_trainer(inp, tar, lab) (models/sketchformer.py:325-349); no host sync."""
+        self._refuse_live("train_step")
         staged = self._stage(inp, tar, labels)       # host-to-device copies of the batch go to the caller's stream FIRST:
         self._enter()                                # the hand-over below is what orders the step behind them
         try:
@@ -904,6 +923,88 @@ class TrainEngine:
         if self._accum is None:
             return
         self.accumulate_gradients(_lib.ACCUM_RESET)
+
+    # ---- weight averaging: an exponential moving average of `params` for evaluation (include/skf.h: skf_model_set_weight_average)
+    def set_weight_average(self, decay=None, num_updates=False):
+        """tf.train.ExponentialMovingAverage(decay, num_updates=optimizer.iterations if num_updates else None) over the flat parameter
+        buffer, without zero-debias.  Allocates the shadow (``n_floats`` floats, ``weight_average``) and starts it at ``params`` -
+        tf's rule.  From then on ``apply_gradients`` - plain, clipped, bucketed, and under accumulation the one that closes an
+        optimizer step - ends with one more launch, shadow -= (shadow - params) * (1 - d); d = decay, or with ``num_updates``
+        min(decay, (1 + n) / (10 + n)) for n = ``iterations`` after the step, read by the kernel.  A step that skip_nonfinite skips
+        leaves the shadow untouched.  Under data parallelism every rank averages the same parameters: no collective.
+        ``decay=None`` switches averaging off and frees the shadow; an unconfigured engine issues the launches it always issued."""
+        if self.average_live:
+            raise _lib.SkfError("the weight average is live in `params` (swap_weight_average): swap back before reconfiguring it")
+        self.synchronize()
+        if decay is None:
+            _lib.call("skf_model_set_weight_average", self.handle, None, 0.0, 0)
+            self._avg = None
+            return
+        d = check_weight_average(decay)
+        shadow = torch.empty(self.n_floats, dtype=torch.float32, device=self.device)
+        _lib.call("skf_model_set_weight_average", self.handle, self._p(shadow), d, int(bool(num_updates)))
+        self._avg = {"decay": d, "num_updates": bool(num_updates), "shadow": shadow, "live": False}
+        self.reset_weight_average()
+
+    @property
+    def average_live(self):
+        """True between two ``swap_weight_average``: `params` holds the average, the shadow the raw weights; training is refused"""
+        return self._avg is not None and self._avg["live"]
+
+    def _refuse_live(self, what):
+        if self._avg is not None and self._avg["live"]:
+            raise _lib.SkfError("%s: the weight average is live in `params` (swap_weight_average / averaged_weights): swap back before "
+                                "training" % what)
+
+    def _need_average(self):
+        if self._avg is None:
+            raise _lib.SkfError("no weight average is configured (set_weight_average)")
+        return self._avg
+
+    def _update_weight_average(self):
+        """the tail of apply_gradients: one launch on the engine's stream behind the sweep; nothing without averaging"""
+        if self._avg is not None:
+            _lib.call("skf_model_update_weight_average", self.handle, self._stream())
+
+    def reset_weight_average(self):
+        """shadow = params: the average starts over from the current weights (what a fresh tf shadow variable holds)"""
+        a = self._need_average()
+        self._refuse_live("reset_weight_average")
+        self._enter()
+        try:
+            with torch.cuda.stream(self.stream):
+                a["shadow"].copy_(self._params)
+        finally:
+            self._leave()
+
+    def swap_weight_average(self):
+        """params <-> shadow in place, one launch on the engine's stream; toggles ``average_live``.  Every forward rebuilds its weight
+        images from `params`: after the swap every inference entry (forward, encode, the decoders, score) runs on the average."""
+        a = self._need_average()
+        self._enter()
+        try:
+            _lib.call("skf_model_swap_weight_average", self.handle, self._stream())
+            a["live"] = bool(self.lib.skf_model_weight_average_live(self.handle))
+        finally:
+            self._leave()
+
+    def averaged_weights(self):
+        """Context manager: the body runs with the averaged weights in `params`; the swap back happens also when the body raises.
+        Entered while the average is already live it changes nothing and leaves it live."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            self._need_average()
+            swapped = not self.average_live
+            if swapped:
+                self.swap_weight_average()
+            try:
+                yield self
+            finally:
+                if swapped and self.average_live:
+                    self.swap_weight_average()
+        return scope()
 
     def buffer(self, name):
         """(rows, cols) view of an internal activation.  fp32 models: a float32 view of the workspace; bf16 models keep
@@ -998,7 +1099,7 @@ class TrainEngine:
         import torch.distributed as dist
         src = dist.get_global_rank(self.pg, 0) if self.pg is not None else 0
         bad = torch.zeros(1, dtype=torch.int32, device=self.device)
-        for name in ("params", "adam_m", "adam_v"):
+        for name in ("params", "adam_m", "adam_v") + (("weight_average",) if self._avg is not None else ()):
             mine = getattr(self, name)
             ref = mine.clone()
             dist.broadcast(ref, src=src, group=self.pg)
@@ -1010,7 +1111,7 @@ class TrainEngine:
             bad += 1
         dist.all_reduce(bad, op=dist.ReduceOp.SUM, group=self.pg)
         if int(bad.item()):
-            raise _lib.SkfError("data-parallel replicas differ at start (parameters / optimizer state / iterations): "
+            raise _lib.SkfError("data-parallel replicas differ at start (parameters / optimizer state / weight average / iterations): "
                                 "every rank must build the model with the same init_seed and restore the same checkpoint")
 
     @property

@@ -3,6 +3,7 @@ from ..core.models import BaseModel
 from . import sketchformer  # noqa: F401
 from . import sketchformer_clip  # noqa: F401
 from . import sketchformer_accum  # noqa: F401
+from . import sketchformer_ema  # noqa: F401
 
 
 def _all():

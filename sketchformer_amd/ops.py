@@ -131,6 +131,46 @@ def grad_accumulate(dst, a, b=None, state=None, micro_op=0):
     return dst
 
 
+def _flat_f32_pair(a, b, na, nb):
+    for t, name in ((a, na), (b, nb)):
+        _p(t)
+        if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.device != a.device:
+            raise TypeError("%s must be a contiguous 1-D float32 tensor on the device of %s" % (name, na))
+        if t.numel() != a.numel():
+            raise ValueError("%s and %s must have the same number of elements" % (na, nb))
+
+
+def ema_decay_at(decay, num_updates=False, iterations=0):
+    """The decay an averaging update uses at ``iterations`` (host only; skf_ema_decay_at): ``decay``, or with ``num_updates``
+    min(decay, (1 + n) / (10 + n)) for n = float32(iterations), every operation in float32 - the expression the kernel evaluates."""
+    return float(_lib.load().skf_ema_decay_at(float(decay), int(bool(num_updates)), int(iterations)))
+
+
+def ema_update(shadow, w, decay, num_updates=False, state=None, skip=None):
+    """shadow -= (shadow - w) * (1 - d) over flat float32 tensors of one size, on the current stream (skf_ema_update: three fp32
+    operations per element, each rounded once - TensorFlow's assign_moving_average).  d = ``decay``, or with ``num_updates``
+    min(decay, (1 + n) / (10 + n)) with n = the `iterations` word of the step state ``state``, read by the kernel.  ``skip``: a device
+    tensor of 4-byte words (None = never); with skip[0] != 0 nothing is written.  Only ``shadow`` is written.  Pointers that are not
+    16-byte aligned, overlapping operands and a decay outside (0, 1) are refused by the library (SkfError, rc = SKF_EINVAL)."""
+    _flat_f32_pair(shadow, w, "shadow", "w")
+    if num_updates and state is None:
+        raise ValueError("num_updates reads `iterations`: it needs the step state")
+    if skip is not None:
+        _p(skip)
+        if skip.element_size() != 4 or skip.numel() < 1 or skip.device != shadow.device:
+            raise TypeError("skip must be a tensor of 4-byte words on the device of shadow")
+    _lib.call("skf_ema_update", _p(shadow), _p(w), shadow.numel(), float(decay), int(bool(num_updates)), _p(state), _p(skip), _stream())
+    return shadow
+
+
+def buffer_swap(a, b):
+    """Exchange the contents of two flat float32 tensors of one size in place, bit for bit (NaN payloads survive), on the current
+    stream (skf_buffer_swap).  The same tensor twice, overlapping views and pointers that are not 16-byte aligned are refused by the
+    library (SkfError, rc = SKF_EINVAL)."""
+    _flat_f32_pair(a, b, "a", "b")
+    _lib.call("skf_buffer_swap", _p(a), _p(b), a.numel(), _stream())
+
+
 def target_live_len(tar, Ld):
     """(B, >= Ld + 1) int64 target tokens -> int32 (B,): 1 + last decoder row t < Ld trained on a non-PAD token tar[b, t+1]."""
     assert tar.dtype == torch.int64 and tar.dim() == 2 and tar.shape[1] > Ld
